@@ -15,6 +15,11 @@ Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--model 
   N>1 is launched by the driver as
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...
 Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times the K steps and prints that line.  --dump-outputs DIR
+also writes the weights, momenta and loss counters the timed steps produced (DIR/<name>.npy);
+the timed steps restart from the initial weights, so two runs with the same arguments write
+the same arrays.  --full is where measurements beyond the headline figure belong (none today).
 """
 import argparse
 import json
@@ -47,6 +52,33 @@ MODELS = {
               "training samples/sec (whole node), synthetic 8-layer x 4096-wide ANN, global batch 8192",
               "synth_ann 4096^9 (ANN, BPM momentum 0.2, lr 0.01, batched mode)"),
 }
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, m, loss_sum, correct):
+    """--dump-outputs: what the timed steps left behind, as DIR/<name>.npy.  A training step
+    returns nothing; its results are the weights and momenta it updated and the loss / correct
+    counters it added to.  Arrays beyond their share of DUMP_MAX_BYTES are written as a sample
+    at fixed (seeded) flat indices, the same in every run.  Two runs give bitwise equal weights
+    and momenta; the loss sum is added up with floating-point atomics, so it agrees to rounding
+    (about 1e-8 of its value)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for l in range(m.L):
+        arrays[f"weights_{l}"] = m.W32[l]
+        if m.V32[l] is not None:
+            arrays[f"momentum_{l}"] = m.V32[l]
+    share = (DUMP_MAX_BYTES - 4096) // len(arrays) // 4  # FP32 elements per array
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), size=share))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+    np.save(os.path.join(path, "stats.npy"), np.array([loss_sum, correct], dtype=np.float64))
 
 
 def main():
@@ -83,6 +115,15 @@ def main():
                          "difference, profiles/r6/SUMMARY.md)")
     ap.add_argument("--replay-trace", default="",
                     help="diagnostics: write the GPU time of every timed graph replay (ms) to this JSON file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what they computed to DIR/<name>.npy: every layer's FP32 "
+                         "master weights and momenta (float32) and the loss sum / correct count of the timed steps "
+                         "(float64); a fixed seeded sample of arrays too large for 64 MB in all.  The timed steps "
+                         "start from the same weights and see the same batches in every run with the same arguments")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures beyond its headline figure.  A plain run sets "
+                         "up, warms up, times the steps and reports; nothing else is measured today, so this "
+                         "option adds nothing yet")
     args = ap.parse_args()
 
     # HPNN_BENCH_REHEARSE=1: rehearse the N > 1 path with several ranks on ONE GPU -- gloo
@@ -114,6 +155,9 @@ def main():
     dp = DataParallel(m, comm="xar" if rehearse and world > 1 else "auto",
                       grad_comm=args.grad_comm if m.fused_mode is None else "fp32")
     dp.broadcast_parameters()
+    # the timed steps restart from these weights: the settle phase runs for a time, not for a
+    # count of steps, so only a restart makes the timed steps' results the same in every run
+    start_state = [(w.clone(), None if v is None else v.clone()) for w, v in zip(m.W32, m.V32)]
 
     g = torch.Generator(device=dev).manual_seed(1234 + rank)
     Xs, Ls = [], []
@@ -257,6 +301,11 @@ def main():
     if not args.warmup_first:
         run_steps(0, args.warmup, eager=bool(args.eager_warmup))
     torch.cuda.synchronize()
+    for l, (w, v) in enumerate(start_state):
+        m.W32[l].copy_(w)
+        if v is not None:
+            m.V32[l].copy_(v)
+    m.refresh_bf16()
     if world > 1 and rank == world - 1 and native().fault_hit("weights"):
         # test hook (HPNN_FAULT=weights:1): one replica's weights drift from the others'
         m.W32[0].view(-1)[0] += 1.0
@@ -309,6 +358,11 @@ def main():
             dist.barrier()
         sys.exit(3)
     loss_sum, correct = m.read_stats()
+    if args.dump_outputs:
+        if dp.sharded:
+            dp.gather_masters()  # collective: the sharded optimizer keeps each rank's rows only
+        if rank == 0:
+            dump_outputs(args.dump_outputs, m, loss_sum, correct)
     samples = args.steps * m.Bp * world
     value = samples / elapsed
     if rank == 0:

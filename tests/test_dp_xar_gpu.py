@@ -5,7 +5,9 @@ fused front, G0 GEMM with the [G1|G2] reduction on its tail workgroups, ONE all-
 that also sums the local split-K slabs, the update.  Checked: both ranks end with
 bit-identical weights, equal (to FP32 summation order) to one process training on the
 concatenated batch; a HIP-graph-captured step gives the same result as eager steps."""
+import datetime
 import os
+import queue
 import socket
 
 import pytest
@@ -35,7 +37,9 @@ def _worker(rank, world, port, graph, q, u8=False, xar_mode=None, form="kernel",
             os.environ["HPNN_XAR_MODE"] = str(xar_mode)
         os.environ["HPNN_XAR_TIMEOUT_MS"] = "2000"
         torch.cuda.set_device(0)
-        dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
+        # a rank whose peer never arrives gives up (and reports) before the parent stops waiting
+        dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world,
+                                timeout=datetime.timedelta(seconds=90))
         from hpnn_amd.models import MLP
         from hpnn_amd.parallel import DataParallel
         dev = torch.device("cuda", 0)
@@ -81,7 +85,7 @@ def _worker(rank, world, port, graph, q, u8=False, xar_mode=None, form="kernel",
         # gradient into the all-reduce's buffer half; copy: the all-reduce copied it in
         assert dp.xar_inplace == (form if form != "copy" else False), (dp.xar_inplace, form)
         W = torch.cat([w.flatten() for w in m.W32] + [v.flatten() for v in m.V32]).cpu()
-        q.put((rank, W))
+        q.put((rank, W.numpy()))  # by value: no shared-memory fd that the parent must fetch from this process
         dist.barrier()
         dist.destroy_process_group()
     except Exception as e:  # noqa: BLE001
@@ -111,11 +115,26 @@ def _run(world, graph, u8, xar_mode=None, form="kernel", B=B, g0_mode=None, perm
           for r in range(world)]
     for p in ps:
         p.start()
-    res = dict(q.get(timeout=110 if world <= 2 else 250) for _ in ps)
-    for p in ps:
-        p.join(timeout=30)
-        if p.is_alive():
-            p.kill()
+    res = {}
+    try:
+        for _ in ps:
+            try:
+                r, w = q.get(timeout=110 if world <= 2 else 250)
+            except queue.Empty:
+                # say what did arrive (a rank that raised explains the one that waits for it)
+                pytest.fail(f"ranks {sorted(set(range(world)) - set(res))} sent nothing; "
+                            f"exit codes {[p.exitcode for p in ps]}; errors received: "
+                            f"{ {k: v for k, v in res.items() if isinstance(v, str)} }")
+            res[r] = w if isinstance(w, str) else torch.from_numpy(w)
+        for p in ps:
+            p.join(timeout=30)
+    finally:
+        # no rank outlives the test, whatever happened: a rank left waiting for a peer that
+        # failed would keep the GPU open and hold up the end of the whole pytest run
+        for p in ps:
+            if p.is_alive():
+                p.kill()
+                p.join(timeout=30)
     for r in range(world):
         assert isinstance(res[r], torch.Tensor), res[r]
     for r in range(1, world):

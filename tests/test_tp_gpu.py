@@ -3,6 +3,7 @@ one MI355X (gloo carries the activation all-gathers and partial-delta reduce-sca
 through host memory; RCCL refuses two ranks on one device): every step on the native
 kernels (gemm_nt / block_permute / dact_cast / gemm_tn / sgd_update_multi) == single-process
 GPU training."""
+import datetime
 import os
 import socket
 
@@ -23,7 +24,9 @@ def _inputs():
 def _worker(rank, world, port, q):
     try:
         torch.cuda.set_device(0)
-        dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
+        # a rank whose peer never arrives gives up (and reports) before the parent stops waiting
+        dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world,
+                                timeout=datetime.timedelta(seconds=90))
         from hpnn_amd.parallel import TensorParallelMLP
         dev = torch.device("cuda", 0)
         X, L = _inputs()
@@ -33,7 +36,7 @@ def _worker(rank, world, port, q):
         for _ in range(3):
             tp.train_step(Xp, labels=L.to(dev), lr=0.05, alpha=0.2)
         w = tp.full_weights()
-        q.put((rank, w))
+        q.put((rank, [t.numpy() for t in w]))  # by value: no shared-memory fd to outlive this process
         dist.barrier()
         dist.destroy_process_group()
     except Exception:  # noqa: BLE001
@@ -52,13 +55,18 @@ def test_tp_two_processes_on_gpu_equals_single(gpu):
     ps = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in ps:
         p.start()
-    res = dict(q.get(timeout=110) for _ in ps)
-    for p in ps:
-        p.join(timeout=30)
-        if p.is_alive():
-            p.kill()
+    try:
+        res = dict(q.get(timeout=110) for _ in ps)
+        for p in ps:
+            p.join(timeout=30)
+    finally:  # no rank outlives the test, whatever happened
+        for p in ps:
+            if p.is_alive():
+                p.kill()
+                p.join(timeout=30)
     assert isinstance(res[0], list), res[0]
     assert isinstance(res[1], list), res[1]
+    res = {r: [torch.from_numpy(a) for a in ws] for r, ws in res.items()}
     dev = torch.device("cuda", 0)
     X, L = _inputs()
     m = MLP(SIZES, "SNN", batch=B, device=dev, momentum=True, seed=21, fused=False)

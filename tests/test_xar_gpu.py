@@ -7,6 +7,7 @@ the same).  Checked: sums of several bucket sizes against the host sum, in-place
 the attach-time self-test, repeated calls (alternating buffer halves, mixed one-/two-shot calls in auto mode at 4
 ranks), slab-sum inputs, HIP-graph capture + replays, and the bounded barrier: a rank
 whose peer never arrives reports a timeout instead of hanging."""
+import datetime
 import os
 import socket
 
@@ -73,7 +74,9 @@ def _worker(rank, world, port, q, mode):
         os.environ["HPNN_XAR_TIMEOUT_MS"] = "400"
         os.environ["HPNN_XAR_MODE"] = mode
         torch.cuda.set_device(0)
-        dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
+        # a rank whose peer never arrives gives up (and reports) before the parent stops waiting
+        dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world,
+                                timeout=datetime.timedelta(seconds=90))
         from hpnn_amd._lib import native
         n = native()
         x = n.xar_create(rank, world, 1 << 20)
@@ -160,9 +163,13 @@ def test_xgmi_allreduce_processes(gpu, world, mode):
     ps = [ctx.Process(target=_worker, args=(r, world, port, q, mode)) for r in range(world)]
     for p in ps:
         p.start()
-    res = dict(q.get(timeout=110) for _ in ps)
-    for p in ps:
-        p.join(timeout=30)
-        if p.is_alive():
-            p.kill()
+    try:
+        res = dict(q.get(timeout=110) for _ in ps)
+        for p in ps:
+            p.join(timeout=30)
+    finally:  # no rank outlives the test, whatever happened
+        for p in ps:
+            if p.is_alive():
+                p.kill()
+                p.join(timeout=30)
     assert res == {r: [] for r in range(world)}, res
