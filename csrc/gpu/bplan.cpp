@@ -123,10 +123,10 @@ int BPlan::configure(const int *sizes, int n_layers, int net_type, int batch_siz
     mode = m;
     if (mode == 't') Bp = pad_to(Bp, TILE_T); /* whole tiles; padded rows are zero and masked by n_valid */
     for (int l = 0; l < L; l++) S[l] = (splits && splits[l] > 0) ? splits[l] : pick_splits(Np[l], Kp[l], Bp);
-    /* modes t / x: the first-layer gradient runs on the fused G0 launch's own tiles (160 or 80
-     * feature columns x 128): about one workgroup per CU of THOSE tiles */
+    /* modes t / x: the first-layer gradient runs on the fused G0 launch's own tiles (80 feature
+     * columns x 128): about one workgroup per CU of THOSE tiles */
     if ((mode == 't' || mode == 'x') && !(splits && splits[0] > 0) && !getenv("HPNN_TN_SPLITS")) {
-        const int tiles = hpnn_g0_tiles(1, Np[0], Kp[0]);
+        const int tiles = hpnn_g0_tiles(Np[0], Kp[0]);
         if (tiles > 0) {
             int s0 = (256 + tiles / 2) / tiles;
             if (s0 > Bp / 512) s0 = Bp / 512;
@@ -180,9 +180,6 @@ int BPlan::configure(const int *sizes, int n_layers, int net_type, int batch_siz
     if (mode == 't' || mode == 'x') {
         add("W0f", -1, BD_BF16, {(long)Np[0] * Kp[0]}, true);
         add("g0cnt", -1, BD_I32, {HPNN_G0CNT_WORDS}, true); /* fused G0 step: tile counters + error word */
-        /* its XCD-local first reduction level (HPNN_G0_XCD=1): protocol words + 8 group partials */
-        add("g0xw", -1, BD_I32, {HPNN_G0X_WORDS}, true);
-        add("g0xs", -1, BD_F32, {8, Np[0], Kp[0]}, false);
     }
     if (mode == 'w') {
         const long pb = wide_ksplit == 2 ? hpnn_wide2_pbuf_bytes(Bp) : 16;
@@ -219,8 +216,6 @@ void BPlan::name_pointers() {
     midtmp = (float *)buf("midtmp");
     W0f = buf("W0f");
     g0cnt = (unsigned int *)buf("g0cnt");
-    g0xw = (unsigned int *)buf("g0xw");
-    g0xs = (float *)buf("g0xs");
     tncnt = (unsigned int *)buf("tncnt");
     wpbuf = (float *)buf("wpbuf");
     wwords = (unsigned int *)buf("wwords");
@@ -404,7 +399,6 @@ int BPlan::g0_fused_step(const XIn &x, float lr, float alpha, float scale, hipSt
     u.W32 = W32[0], u.V32 = V32[0], u.Wb = Wb[0], u.Wt = Wt[0], u.Wf = W0f;
     u.cnt = g0cnt, u.err = g0cnt + HPNN_G0_ERR_WORD;
     u.perm = g0_perm;
-    if (g0_xcd && g0xw && g0xs) u.xw = g0xw, u.xslab = g0xs;
     u.fault = hpnn_fault_hit("handoff"); /* HPNN_FAULT=handoff:n: the n-th launch reports a timed-out wait */
     /* HPNN_FAULT=xsum:n: the n-th exchanging launch of the last rank sums one element wrong */
     u.xfault = xv && xv->world > 1 && xv->rank == xv->world - 1 && hpnn_fault_hit("xsum");
@@ -570,7 +564,7 @@ int BPlan::xchg_step(const XIn &x, const int *labels, const float *T, int ldt, i
                      float scale, const hpnn_xar_view &xv, hipStream_t s) {
     if (mode != 't' && mode != 'x' && mode != 'm') return -1;
     if (!fm_input(x) || !g0cnt || !g0_fused || !hpnn_gemm_fm_direct_update_ok(Kp[0], Np[0], Kp[0], Bp, S[0]) ||
-        S[0] * hpnn_g0_tiles(x.u8, Np[0], Kp[0]) > HPNN_XAR_MAX_BLOCKS || (long)goff[L] > xv.half)
+        S[0] * hpnn_g0_tiles(Np[0], Kp[0]) > HPNN_XAR_MAX_BLOCKS || (long)goff[L] > xv.half)
         return -1;
     int r;
     if ((r = front(x, labels, T, ldt, n_valid, s))) return r;
@@ -586,7 +580,7 @@ int BPlan::xchg_step(const XIn &x, const int *labels, const float *T, int ldt, i
 int BPlan::xchg_self_test(const hpnn_xar_view &xv, hipStream_t s) {
     if (mode != 't' && mode != 'x' && mode != 'm') return -1;
     if (!g0cnt || !g0_fused || !hpnn_gemm_fm_direct_update_ok(Kp[0], Np[0], Kp[0], Bp, S[0]) ||
-        S[0] * hpnn_g0_tiles(1, Np[0], Kp[0]) > HPNN_XAR_MAX_BLOCKS || (long)goff[L] > xv.half)
+        S[0] * hpnn_g0_tiles(Np[0], Kp[0]) > HPNN_XAR_MAX_BLOCKS || (long)goff[L] > xv.half)
         return -1;
     hpnn_g0_update u;
     memset(&u, 0, sizeof u);

@@ -165,11 +165,6 @@ typedef struct {
      * xfault: corrupt one element of this rank's exchanged sum (HPNN_FAULT=xsum:n) */
     int perm, xtest, xfault;
     float *xres;
-    long n12t; /* set by the launcher: [G1 | G2] floats summed by the tail workgroups */
-    /* XCD-local first level of the split-K reduction (HPNN_G0_XCD=1): xw = HPNN_G0X_WORDS
-     * protocol words (zeroed once), xslab = 8 partial G0 slabs (one per XCD group); NULL: off */
-    unsigned int *xw;
-    float *xslab;
     int fault; /* test hook (HPNN_FAULT=handoff:n): the split-K wait of that launch reports a
                 * timeout (sets *err) as a real one would */
 } hpnn_g0_update;
@@ -178,17 +173,12 @@ int hpnn_gemm_fm_direct_update(const void *Dg, const void *Hg, int h_u8, float h
 /* 1 when hpnn_gemm_fm_direct_update covers the shape (launch-free check), including the
  * residency its in-kernel hand-offs need: every workgroup of the grid co-resident */
 int hpnn_gemm_fm_direct_update_ok(int ldg, int N, int M, int Bt, int splits);
-/* output tiles of the fused G0 launch for these operands (h_u8: 8-bit H), 0 if not covered;
- * the launch's grid is tiles x splits */
-int hpnn_g0_tiles(int h_u8, int N, int M);
-/* feature columns of that launch's output tile (160, or 80 with HPNN_G0_TILE=80) */
-int hpnn_g0_tile_cols(int M);
-/* hpnn_g0_update.cnt: HPNN_G0CNT_WORDS words, 64-bit tile counters 32 words apart (tile < 
+/* output tiles (80 feature columns x 128) of the fused G0 launch for an N x M gradient, 0 if
+ * not covered; the launch's grid is tiles x splits GEMM workgroups plus its tail workgroups */
+int hpnn_g0_tiles(int N, int M);
+/* hpnn_g0_update.cnt: HPNN_G0CNT_WORDS words, 64-bit tile counters 32 words apart (tile <
  * HPNN_G0_MAX_TILES), the error word at HPNN_G0_ERR_WORD */
 #define HPNN_G0CNT_WORDS 1024
-/* hpnn_g0_update.xw layout: per-role epochs, per-(tile, group) member slots, group and tile
- * counters (64-bit); see kernels_g0.hip */
-#define HPNN_G0X_WORDS 4096
 #define HPNN_G0_MAX_TILES 31
 #define HPNN_G0_ERR_WORD 1000
 /* workgroups of `kernel` (threads per workgroup, dynamic LDS bytes) the device can hold at once:

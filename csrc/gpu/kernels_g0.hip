@@ -20,7 +20,7 @@
  * BF16 batch; cold 26.5 us vs 34 standalone (round-2 A/B scripts, since pruned).
  * Measured (48 splits): LDS-staged TN kernel 31.2 us (its LDS-DMA
  * fill, ~27 GB/s per CU, is the bound); this kernel 23.8 us, ~5.1 TB/s of HBM reads --
- * it streams at the memory rate.  Round 4, again: the same 160 x 128 tiles with the operands
+ * it streams at the memory rate.  Round 4, again: that round's 160 x 128 tiles with the operands
  * LDS-DMA staged (two k-steps of contiguous fragments per stage, 3-4 stages in flight, no VGPR
  * staging) took 72.9-74.1 vs 61.3-62.0 us per MNIST step (profiles/r4).  Rejected on the way: the same kernel on plain
  * batch-contiguous (transposed row-major) operands, 51 us -- each wave load then hits
@@ -28,11 +28,11 @@
  * rate (~1 lookup per clock per CU, TCP_TOTAL_CACHE_ACCESSES) is the limit; grouping 2-4
  * k-steps per row visit or padding the row pitch did not change that.
  *
- * Workgroup: 4 x KW waves.  Waves (wm, wn) in 2 x 2 cover a 32 WF x 32 WH output tile
- * (wave tile 16 WF x 16 WH); with KW = 2 a second group of 4 waves takes every other
- * 32-row k-step and the two partial tiles meet in LDS at the end (fixed order).  Each
- * wave keeps PD k-steps of operands in flight in a register ring (PD + 1 slots; the loop
- * is unrolled by PD + 1 so every slot index is static).
+ * Workgroup: WM x WN x KW waves.  The WM x WN waves (wm, wn) of a k-group cover a
+ * 16 WF WM x 16 WH WN output tile (wave tile 16 WF x 16 WH); group kg of KW takes the 32-row
+ * k-steps kg, kg + KW, ... of the workgroup's split and the groups' partial tiles meet in LDS
+ * at the end (fixed order).  Each wave keeps PD k-steps of operands in flight in a register
+ * ring (PD + 1 slots; the loop is unrolled by PD + 1 so every slot index is static).
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -66,8 +66,9 @@ using hpnn::st_sc1;
  * HU8: Hg holds unsigned bytes (8 per lane per fragment), multiplied as exact integers;
  * hscale scales the FP32 result (G = hscale * D^T H) */
 /* the workgroup's partial product over its split of the batch: on return the waves of group
- * kg == 0 hold the 32 WF x 32 WH tile (wave tile 16 WF x 16 WH) in acc; *tile_, *split_, m0 / n0
- * (this wave's tile origin) are set.  Every wave returns (the caller's barriers need them). */
+ * kg == 0 hold the 16 WF WM x 16 WH WN tile (wave tile 16 WF x 16 WH) in acc; tile, split and
+ * m0 / n0 (this wave's tile origin) are set.  Every wave returns (the caller's barriers need
+ * them). */
 /* workgroup role: (virtual) block b -> output tile and batch split.  xcd_map: the tiles of
  * one batch slice share b % 8, i.e. one XCD under the observed round-robin placement, so the
  * slice's Dt rows are fetched once into that L2 -- a speed assumption only: every result is
@@ -233,13 +234,15 @@ __global__ __launch_bounds__(64 * WM * WN * KW) void gemm_fm_direct_kernel(const
  * summed completely (fixed order) and layers 1 and 2 stepped by TAIL workgroups appended to
  * the grid, on the CUs the GEMM grid leaves idle (MNIST: 240 GEMM workgroups + 16 tails on 256
  * CUs): the 9 MB of slab reads run beside the GEMM instead of after every workgroup's publish
- * (-2.7 us per step on a slow box, profiles/r6); HPNN_G0_TAIL12 < 100 leaves part of the
- * columns to the GEMM workgroups, between their ticket and their wait.  Tails wait for
- * nothing, so any dispatch order is deadlock-free.  Output tiles are 80 x 128 (10 tiles x 24
- * splits on MNIST: half the split-K partial bytes of 160 x 128 x 48, HPNN_G0_TILE=160 the
- * old form).  Replaces the separate sgd_update_multi launch (6.2 us) and its kernel boundary
- * behind 20 MB of dirty slabs.  All GEMM workgroups are co-resident (grid <= CUs; a wait that
- * times out sets *err instead of hanging).  Reference: the per-layer update of
+ * (-2.7 us per step on a slow box, profiles/r6).  A launch without tails (no idle CU, or
+ * HPNN_G0_TAILS=0) leaves [G1 | G2] to the GEMM workgroups, a 1 / (tiles x splits) share
+ * each between their ticket and their wait.  Tails wait for nothing, so any dispatch order is
+ * deadlock-free.  Output tiles are 80 x 128 (10 tiles x 24 splits on MNIST): half the
+ * split-K partial bytes of 160 x 128 tiles x 48 splits (profiles/r6/SUMMARY.md).  Replaces
+ * the separate sgd_update_multi launch (6.2 us) and its kernel boundary behind 20 MB of dirty
+ * slabs.  All GEMM workgroups are co-resident (grid <= CUs; a wait that times out sets *err
+ * instead of hanging).  An XCD-local first level of the split-K reduction was tried and
+ * measured slower (profiles/r6/SUMMARY.md).  Reference: the per-layer update of
  * snn_kernel_train_momentum / cuda_snn.cu:2726-3717 (GER into dW, W += dW, dW *= alpha),
  * batched. */
 constexpr unsigned long long G0_TIMEOUT = 1000000000ULL; /* wall-clock ticks (~10 s) */
@@ -321,59 +324,18 @@ __device__ __forceinline__ Pre4 pre_load(const float *W32, const float *V32, siz
 }
 
 /* [G1 | G2]: float4 columns [c0, c1) of the front's block slabs summed over all mrows rows in
- * a fixed order (RG row groups of NT / 16 threads, met in LDS in order), then layers 1 / 2
- * stepped at those elements */
-template <int NT>
+ * a fixed order, then layers 1 / 2 stepped at those elements (or the sums stored into g12out).
+ * A pass takes C4 columns x RG = NT / C4 row groups, each thread with RB rows' loads in flight
+ * (a dependent one-at-a-time walk over the rows is latency-bound: a pass is one L2 / Infinity
+ * Cache round trip); the row groups meet in LDS in order.  GEMM workgroups (a launch without
+ * tails: ~11 columns each on MNIST, between their ticket and their wait): 16 x 8, and the
+ * first element's prefetched W / V (use, pre).  Tail workgroups (blocks past the GEMM grid,
+ * on the CUs it leaves idle, beside the GEMM instead of after it), 1 / ntail of all columns
+ * each: 32 columns (512 contiguous bytes of a row) x 16 rows */
+template <int NT, int C4, int RB>
 __device__ __forceinline__ void g12_share(const hpnn_g0_update &u, long c0, long c1, f32x4 *red, float *g12out,
                                           bool use = false, Pre4 pre = {}) {
-    constexpr int C4 = 16, RG = NT / C4;
-    const int t = threadIdx.x, c = t % C4, rg = t / C4;
-    for (long b0 = c0; b0 < c1; b0 += C4) {
-        const long e4 = b0 + c;
-        f32x4 a = {0.f, 0.f, 0.f, 0.f};
-        if (e4 < c1) {
-            /* 8 rows' loads in flight per batch (a dependent one-at-a-time walk over the rows is
-             * latency-bound: ~8 L2 / Infinity-Cache round trips back to back) */
-            const float *col = u.mslab + e4 * 4;
-            for (int r0 = rg; r0 < u.mrows; r0 += 8 * RG) {
-                f32x4 v[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const int r = r0 + k * RG;
-                    v[k] = r < u.mrows ? *(const f32x4 *)(col + (long)r * u.mstride) : f32x4{0.f, 0.f, 0.f, 0.f};
-                }
-#pragma unroll
-                for (int k = 0; k < 8; k++) a += v[k];
-            }
-        }
-        red[t] = a;
-        __syncthreads();
-        if (rg == 0 && e4 < c1) {
-            f32x4 g = red[c];
-            for (int r = 1; r < RG; r++) g += red[r * C4 + c];
-            long i = e4 * 4;
-            if (g12out) {
-                *(f32x4 *)(g12out + i) = g;
-            } else {
-                int n, k;
-                const int l = g12_elem(u, e4, n, k);
-                step_elem4(pick(u.W32b, l), pick(u.V32b, l), (__bf16 *)pick(u.Wbb, l), (__bf16 *)pick(u.Wtb, l), nullptr,
-                           pick(u.Nb, l), pick(u.Kb, l), n,
-                           k, g, u, use && b0 == c0 /* this thread's prefetched element */, pre);
-            }
-        }
-        __syncthreads();
-    }
-}
-
-/* [G1 | G2] on the tail workgroups (blocks past the GEMM grid, on the CUs it leaves idle; they
- * run beside the GEMM instead of after it): float4 columns [c0, c1) summed over all mrows rows,
- * 32 columns (512 contiguous bytes of a row) x NT / 32 row groups per pass and 16 rows of loads
- * in flight per thread (latency-bound otherwise: a pass is one memory round trip); the row
- * groups meet in LDS in a fixed order, then the layer-1/2 step (or the store into g12out) */
-template <int NT>
-__device__ __forceinline__ void g12_share_wide(const hpnn_g0_update &u, long c0, long c1, f32x4 *red, float *g12out) {
-    constexpr int C4 = 32, RG = NT / C4, RB = 16;
+    constexpr int RG = NT / C4;
     const int t = threadIdx.x, c = t % C4, rg = t / C4;
     for (long b0 = c0; b0 < c1; b0 += C4) {
         const long e4 = b0 + c;
@@ -403,7 +365,7 @@ __device__ __forceinline__ void g12_share_wide(const hpnn_g0_update &u, long c0,
                 const int l = g12_elem(u, e4, n, k);
                 step_elem4(pick(u.W32b, l), pick(u.V32b, l), (__bf16 *)pick(u.Wbb, l), (__bf16 *)pick(u.Wtb, l), nullptr,
                            pick(u.Nb, l), pick(u.Kb, l), n,
-                           k, g, u);
+                           k, g, u, use && b0 == c0 /* this thread's prefetched element */, pre);
             }
         }
         __syncthreads();
@@ -566,69 +528,6 @@ __device__ __forceinline__ f32x4 xtest_pattern(int rank, long i) {
     return v;
 }
 
-/* ---- XCD-local first level of the split-K reduction (u.xw, HPNN_G0_XCD=1) -------------
- * The splits of a tile form 8 static groups g = split % 8 of gsz = splits / 8 members (MNIST:
- * 24 splits, 3 a group).  Under the round-robin placement a group's members share one XCD, so
- * they can combine through that XCD's L2 instead of publishing write-through: every member
- * stores its partial tile PLAIN (it stays in the L2), the group's last arriver sums the gsz
- * partials (L1-bypassing loads served by the L2) and publishes ONE write-through partial per
- * (tile, group), and the tile's reducers then read 8 partials instead of `splits`.  The
- * placement is never assumed: at kernel start every member records (launch epoch, hardware
- * XCC_ID) in its group slot, and after its GEMM it stores plain only when every member of the
- * group has recorded this epoch on ITS XCD -- otherwise write-through, which any reader can
- * see.  All sums keep a fixed order (members, then groups): bitwise the same whichever block
- * takes which role and whichever store form ran. */
-constexpr int G0X_EP = 0, G0X_SLOTS = 256, G0X_GCNT = 2304, G0X_TCNT = 2816;
-static_assert(G0X_TCNT + 32 * HPNN_G0_MAX_TILES <= HPNN_G0X_WORDS, "xw layout");
-static_assert(G0X_SLOTS + 64 * HPNN_G0_MAX_TILES <= G0X_GCNT && G0X_GCNT + 16 * HPNN_G0_MAX_TILES <= G0X_TCNT,
-              "xw layout");
-
-__device__ __forceinline__ unsigned int xcc_id() {
-    return (unsigned int)__builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u; /* HW_REG_XCC_ID[3:0] */
-}
-
-/* the group leader: out[e] = sum over members m (in order) of part[m][e], float4 e of the tile
- * at offsets off(e); NT threads, NE4 float4, G members (static: every index below is
- * compile-time, no scratch); write-through stores */
-template <int NT, int NE4, int TMF, int G>
-__device__ __forceinline__ void xcd_group_sum_g(const float *slab0, size_t mstride, float *out, int ldg, int nt0,
-                                                int mt0) {
-    constexpr int KE = (NE4 + NT - 1) / NT, EPB = 16 / G; /* float4 per thread, per 16-load batch */
-    const int t = threadIdx.x;
-    auto off = [&](int c) __attribute__((always_inline)) {
-        return (size_t)(nt0 + c / (TMF / 4)) * ldg + mt0 + 4 * (c % (TMF / 4));
-    };
-#pragma unroll
-    for (int k0 = 0; k0 < KE; k0 += EPB) {
-        const float *q[16];
-        f32x4 v[16];
-#pragma unroll
-        for (int i = 0; i < 16; i++) {
-            const int k = k0 + i / G, m = i % G, c = t + k * NT;
-            const bool ok = i < EPB * G && k < KE && c < NE4;
-            q[i] = slab0 + (ok ? off(c) + (size_t)m * mstride : off(t < NE4 ? t : 0)); /* spares: a valid line */
-        }
-        hpnn::ld_sc1_x16(v, q);
-#pragma unroll
-        for (int j = 0; j < EPB; j++) {
-            const int k = k0 + j, c = t + k * NT;
-            if (k < KE && c < NE4) {
-                f32x4 a = v[j * G];
-#pragma unroll
-                for (int m = 1; m < G; m++) a += v[j * G + m];
-                st_sc1(out + off(c), a);
-            }
-        }
-    }
-}
-template <int NT, int NE4, int TMF>
-__device__ __forceinline__ void xcd_group_sum(const float *slab0, size_t mstride, float *out, int gsz, int ldg,
-                                              int nt0, int mt0) {
-    if (gsz == 2) xcd_group_sum_g<NT, NE4, TMF, 2>(slab0, mstride, out, ldg, nt0, mt0);
-    else if (gsz == 3) xcd_group_sum_g<NT, NE4, TMF, 3>(slab0, mstride, out, ldg, nt0, mt0);
-    else xcd_group_sum_g<NT, NE4, TMF, 4>(slab0, mstride, out, ldg, nt0, mt0);
-}
-
 /* HPNN_G0_TRACE=1 (profiling only): s_memtime stamps of every workgroup's thread 0 at the
  * phase boundaries, [block][mark]; read back with hpnn_g0_trace */
 constexpr int G0TR_BLOCKS = 512, G0TR_MARKS = 8;
@@ -653,10 +552,10 @@ __global__ __launch_bounds__(64 * WM * WN * KW) void g0_fused_kernel(const __bf1
     f32x4 acc[WF][WH];
     int tile, split, m0, n0;
     const long nb = (long)tiles * splits, nf = u.n12 / 4;
-    /* [G1 | G2] float4 columns [0, nt4) belong to the tail workgroups (blocks nb..), the rest to
-     * the GEMM workgroups after their publish */
+    /* [G1 | G2] float4 columns [0, nt4) belong to the tail workgroups (blocks nb..): all of them
+     * when the launch has tails, else the GEMM workgroups take them after their publish */
     const int ntail = (int)gridDim.x - (int)nb;
-    const long nt4 = ntail > 0 ? u.n12t / 4 : 0;
+    const long nt4 = ntail > 0 ? nf : 0;
     /* the exchange's parameters, set by whichever path this workgroup takes */
     bool xdo = false, xpf = false;
     int xb = 0, xe0 = 0, xe1 = 0, xnt0 = 0, xmt0 = 0;
@@ -685,27 +584,13 @@ __global__ __launch_bounds__(64 * WM * WN * KW) void g0_fused_kernel(const __bf1
                 }
             }
         } else {
-            g12_share_wide<NT>(u, tc0, tc1, red, gout ? gout + (size_t)N * ldg : nullptr);
+            g12_share<NT, 32, 16>(u, tc0, tc1, red, gout ? gout + (size_t)N * ldg : nullptr);
         }
         xdo = u.xchg != 0, xb = (int)blockIdx.x, xep = txe_s, xc0 = tc0, xc1 = tc1;
     } else {
         /* the workgroup's role: virtual block vb (u.perm > 0, tests: reversed and rotated order --
          * every result must stay bitwise the same) */
         const int vb = u.perm > 0 ? (int)((nb - 1 - (long)blockIdx.x + u.perm) % nb) : (int)blockIdx.x;
-        /* XCD-local first reduction level: this member's (epoch, XCC) in its group slot, before the
-         * GEMM (the members check each other's after theirs) */
-        const int gsz = splits / 8;
-        const bool xg = u.xw && !u.xtest && xcd_map && splits % 8 == 0 && gsz >= 2 && gsz <= 4;
-        unsigned int x_me = 0;
-        if (xg && threadIdx.x == 0) {
-            int tl, sp;
-            fm_role(vb, splits, tiles, xcd_map, tl, sp);
-            const unsigned int ep =
-                __hip_atomic_fetch_add(u.xw + G0X_EP + vb, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
-            x_me = (ep << 4) | xcc_id();
-            __hip_atomic_store(u.xw + G0X_SLOTS + (tl * 8 + (sp & 7)) * 8 + (sp >> 3), x_me, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-        }
         if (u.xtest) /* self-test of the in-kernel exchange: no GEMM (the role only) */
             fm_role(vb, splits, tiles, xcd_map, tile, split);
         else
@@ -760,30 +645,11 @@ __global__ __launch_bounds__(64 * WM * WN * KW) void g0_fused_kernel(const __bf1
                 pg12 = pre_load(pick(u.W32b, l), pick(u.V32b, l), (size_t)n * pick(u.Kb, l) + k, u.momentum);
             }
             /* publish this split's partial tile (write-through), then one ticket for the workgroup */
-            __shared__ int xloc_s, xlead_s;
-            const int xgrp = split & 7;
-            if (xg) {
-                if (t == 0) { /* every member of the group recorded this epoch on this XCD? */
-                    bool loc = true;
-                    for (int m = 0; m < gsz; m++)
-                        loc = loc && __hip_atomic_load(u.xw + G0X_SLOTS + (tile * 8 + xgrp) * 8 + m, __ATOMIC_RELAXED,
-                                                       __HIP_MEMORY_SCOPE_AGENT) == x_me;
-                    xloc_s = loc;
-                }
-                __syncthreads();
-            }
             if ((t >> 6) < GW) {
                 const int r16 = lane & 15, q = lane >> 4;
                 float *out = slab + (size_t)split * N * ldg;
                 if (G0_PROTO(u, 256)) {
                     /* timing ablation: no publish at all (wrong results) */
-                } else if (xg && xloc_s) { /* the group's leader reads it from this XCD's L2 */
-#pragma unroll
-                    for (int i = 0; i < WF; i++)
-#pragma unroll
-                        for (int j = 0; j < WH; j++)
-                            *(f32x4 *)(out + (size_t)(n0 + j * 16 + r16) * ldg + m0 + i * 16 + 4 * q) =
-                                HU8 ? acc[i][j] * hscale : acc[i][j];
                 } else {
 #pragma unroll
                     for (int i = 0; i < WF; i++)
@@ -796,39 +662,18 @@ __global__ __launch_bounds__(64 * WM * WN * KW) void g0_fused_kernel(const __bf1
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             __shared__ unsigned long long want_s;
-            unsigned int *const tcnt = xg ? u.xw + G0X_TCNT + 32 * tile : u.cnt + 32 * tile;
+            unsigned int *const tcnt = u.cnt + 32 * tile;
             if (t == 0) {
                 if (G0_PROTO(u, 1)) {
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 }
-                if (xg) {
-                    /* group ticket: the last arriver of the launch leads; the tile then waits for its 8
-                     * group partials (both counters monotonic: gsz and 8 per launch) */
-                    unsigned long long *const gc = (unsigned long long *)(u.xw + G0X_GCNT + 2 * (tile * 8 + xgrp));
-                    const unsigned long long old = atomicAdd(gc, 1ull);
-                    xlead_s = (int)(old % gsz) == gsz - 1;
-                    want_s = (old / gsz + 1) * 8ull;
-                } else {
-                    want_s = hpnn::ticket_arrive(u.cnt + 32 * tile, (unsigned)splits); /* this launch's last ticket */
-                }
-            }
-            if (xg) {
-                __syncthreads();
-                if (xlead_s) {
-                    /* the group's partial: its gsz member slots summed in member order (plain-stored ones
-                     * sit in this XCD's L2, write-through ones in memory; both visible to sc1 loads) */
-                    xcd_group_sum<NT, NE4, TMF>(slab + (size_t)xgrp * N * ldg, (size_t)8 * N * ldg,
-                                                u.xslab + (size_t)xgrp * N * ldg, gsz, ldg, nt0, mt0);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __syncthreads();
-                    if (t == 0) atomicAdd((unsigned long long *)tcnt, 1ull);
-                }
+                want_s = hpnn::ticket_arrive(tcnt, (unsigned)splits); /* this launch's last ticket */
             }
             mark(2);
             /* while the other splits finish: this workgroup's share of [G1 | G2] (no dependency on G0) */
             if (!G0_PROTO(u, 512) && c1 > c0) /* 512: timing ablation, no [G1 | G2] share */
-                g12_share<NT>(u, c0, c1, red, gout ? gout + (size_t)N * ldg : nullptr, pf && t < 16, pg12);
+                g12_share<NT, 16, 8>(u, c0, c1, red, gout ? gout + (size_t)N * ldg : nullptr, pf && t < 16, pg12);
             mark(3);
             if (t == 0) {
                 /* fault hook: this launch reports a timed-out wait (and, like one, reduces what is there) */
@@ -844,17 +689,14 @@ __global__ __launch_bounds__(64 * WM * WN * KW) void g0_fused_kernel(const __bf1
             /* this split's share of the tile: float4 e in [e0, e1), 128 at a time; PARTS threads per
              * float4, each summing a fixed run of splits; the runs meet in LDS in order */
             const int f = t % 128, part = t / 128;
-            /* the partials to sum: `splits` split slabs, or the 8 XCD-group partials */
-            const int rn = xg ? 8 : splits;
-            const float *const rbase = xg ? u.xslab : slab;
-            const int s0 = part * rn / PARTS, s1 = (part + 1) * rn / PARTS;
+            const int s0 = part * splits / PARTS, s1 = (part + 1) * splits / PARTS;
             const size_t ss = (size_t)N * ldg;
             for (int cc = e0; cc < e1; cc += 128) {
                 const int e = cc + f;
                 const int row = e / (TMF / 4), col = mt0 + 4 * (e % (TMF / 4));
                 f32x4 sum = {0.f, 0.f, 0.f, 0.f};
                 if (e < e1 && !G0_PROTO(u, 1024)) { /* 1024: timing ablation, no split loads */
-                    const float *p = rbase + (size_t)(nt0 + row) * ldg + col;
+                    const float *p = slab + (size_t)(nt0 + row) * ldg + col;
                     if (G0_PROTO(u, 4))
                         for (int s = s0; s < s1; s += 8) sum += sum_sc1_x8<true>(p + (size_t)s * ss, ss, s1 - s);
                     else
@@ -897,35 +739,19 @@ int launch_fm(const void *Dg, const void *Hg, float hscale, float *slab, int ldg
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
-/* feature columns per workgroup tile of the 8-bit-input G0 (HPNN_G0_TILE=80 | 160) */
-int g0_tile_m(int M) {
-    static const int want = [] { const char *e = getenv("HPNN_G0_TILE"); return e ? atoi(e) : 80; }();
-    return (want == 80 && M % 80 == 0) ? 80 : 160;
-}
-
 int fm_dispatch(const void *Dg, const void *Hg, int h_u8, float hscale, float *slab, int ldg, int N, int M, int Bt,
                 int splits, hipStream_t s, const TnTail &t) {
     if (N <= 0 || M <= 0 || Bt <= 0 || splits <= 0) return -1;
     if (Bt % 32 || splits > Bt / 32 || M % 32 || N % 32) return -2;
     if (ldg % 4 || ldg < M) return -3;
-    /* 160 x 128 tiles: measured alternatives (3 k-steps in flight; 8 waves as two k-interleaved
-     * groups with 2 / 1 in flight) were no faster: 23.8 / 25.1 / 24.3 us vs 23.8 us */
 #define HPNN_FM(...)                                                                                              \
     return h_u8 ? launch_fm<__VA_ARGS__, true>(Dg, Hg, hscale, slab, ldg, N, M, Bt, splits, s, t)                  \
                 : launch_fm<__VA_ARGS__, false>(Dg, Hg, hscale, slab, ldg, N, M, Bt, splits, s, t)
-    if (N % 128 == 0 && g0_tile_m(M) == 80) { /* 80 x 128: four k-interleaved groups of 1 x 2 waves */
+    /* 80 x 128: four k-interleaved groups of 1 x 2 waves; half the split-K partial bytes of
+     * 160 x 128 tiles (profiles/r6/SUMMARY.md) */
+    if (M % 80 == 0 && N % 128 == 0) {
         return h_u8 ? launch_fm<5, 4, 1, 4, true, 1, 2>(Dg, Hg, hscale, slab, ldg, N, M, Bt, splits, s, t)
                     : launch_fm<5, 4, 1, 4, false, 1, 2>(Dg, Hg, hscale, slab, ldg, N, M, Bt, splits, s, t);
-    }
-    if (M % 160 == 0 && N % 128 == 0) {
-        /* 8-bit H: 8 waves (two k-interleaved groups) hide the byte -> bf16 conversion
-         * (23.0 / 26.5 us hot / cold vs 27.0 / 27.2 with 4 waves); bf16 H: 4 waves.
-         * Round 3, in the MNIST step (tile front): 59.8-59.9 us per step with this one vs
-         * 60.0 with 2 k-steps in flight, 62.3 / 61.4 with 4 waves and 2 / 3 in flight. */
-        /* session 7: three k-interleaved groups (12 waves, 3 a SIMD) 24.9 vs 23.4 us in the
-         * step, 58.9-59.3 vs 56.2-58.5 us per step (profiles/r3/s7_g0_kw_ab.txt) */
-        if (h_u8) { HPNN_FM(5, 4, 1, 2); }
-        HPNN_FM(5, 4, 2, 1);
     }
     if (M % 64 == 0 && N % 64 == 0) { HPNN_FM(2, 2, 2, 1); }
     HPNN_FM(1, 1, 3, 1);
@@ -935,18 +761,11 @@ int fm_dispatch(const void *Dg, const void *Hg, int h_u8, float hscale, float *s
 }  // namespace
 
 /* the fused G0 grid (tiles x splits workgroups of 512 threads) fits on the device at once;
- * every instantiation checked (they differ in the operand conversion and the tile) */
+ * both instantiations checked (they differ in the operand conversion) */
 static bool g0_fused_resident(int blocks) {
-    static const int cap = [] {
-        int c = hpnn_resident_capacity((const void *)g0_fused_kernel<5, 4, 1, 2, true>, 512, 0);
-        for (const void *k : {(const void *)g0_fused_kernel<5, 4, 1, 2, false>,
-                              (const void *)g0_fused_kernel<5, 4, 1, 4, true, false, 1, 2>,
-                              (const void *)g0_fused_kernel<5, 4, 1, 4, false, false, 1, 2>}) {
-            const int a = hpnn_resident_capacity(k, 512, 0);
-            c = a < c ? a : c;
-        }
-        return c;
-    }();
+    static const int cap =
+        std::min(hpnn_resident_capacity((const void *)g0_fused_kernel<5, 4, 1, 4, true, false, 1, 2>, 512, 0),
+                 hpnn_resident_capacity((const void *)g0_fused_kernel<5, 4, 1, 4, false, false, 1, 2>, 512, 0));
     return blocks <= cap;
 }
 
@@ -955,39 +774,27 @@ static bool g0_fused_on() {
     return on;
 }
 
-/* the fused launch's tile (TMF feature columns x 128) for these operands */
-static int g0_fused_tm(int h_u8, int M) {
-    (void)h_u8;
-    return g0_tile_m(M);
-}
-
-extern "C" int hpnn_g0_tile_cols(int M) { return g0_tile_m(M); }
-
-extern "C" int hpnn_g0_tiles(int h_u8, int N, int M) {
-    const int tm = g0_fused_tm(h_u8, M);
-    return (M % tm || N % 128) ? 0 : (M / tm) * (N / 128);
-}
+/* the fused launch's output tiles: 80 feature columns x 128, as fm_dispatch's first choice */
+extern "C" int hpnn_g0_tiles(int N, int M) { return (M % 80 || N % 128) ? 0 : (M / 80) * (N / 128); }
 
 extern "C" int hpnn_gemm_fm_direct_update(const void *Dg, const void *Hg, int h_u8, float hscale, float *slab,
                                           int ldg, int N, int M, int Bt, int splits, const hpnn_g0_update *u,
                                           hipStream_t stream) {
-    /* the 8-wave tile configurations of fm_dispatch: 160 x 128, or 80 x 128 for 8-bit H */
-    const int tm = g0_fused_tm(h_u8, M);
-    if (!g0_fused_on() || !u || M % tm || N % 128 || Bt % 32 || splits < 1 || splits > Bt / 32 || ldg != M) return -1;
+    const int tiles = hpnn_g0_tiles(N, M), tiles_n = N / 128;
+    if (!g0_fused_on() || !u || !tiles || Bt % 32 || splits < 1 || splits > Bt / 32 || ldg != M) return -1;
     if (!u->cnt || !u->err) return -1;
     const bool steps = !u->gout || u->xchg;
     if (u->n12 % 4 || !u->mslab || u->mrows < 1 || (steps && u->momentum && (!u->V32 || !u->V32b[0] || !u->V32b[1])))
         return -2;
-    const int tiles_n = N / 128, tiles = (M / tm) * tiles_n;
     if (tiles > HPNN_G0_MAX_TILES) return -1; /* 64-bit counters 32 words apart, below the error word */
     /* every workgroup waits for the other splits of its tile: all must be resident at once
      * (more splits than that, e.g. forced by HPNN_TN_SPLITS, take the slab form instead of
      * stalling to the timeout) */
     if (!g0_fused_resident(tiles * splits)) return -1;
     /* tail workgroups for the [G1 | G2] share on the CUs the GEMM grid leaves idle (MNIST: 240
-     * GEMM workgroups, 16 tails on a 256-CU MI355X); HPNN_G0_TAILS overrides the count (0: off),
-     * HPNN_G0_TAIL12 the percentage of the [G1 | G2] columns they take (the GEMM workgroups sum
-     * the rest after their publish) */
+     * GEMM workgroups, 16 tails on a 256-CU MI355X); HPNN_G0_TAILS overrides the count (0: none,
+     * the GEMM workgroups sum [G1 | G2] after their publish -- the form for a device with no
+     * idle CU) */
     static const int cus = [] {
         int dev = 0, n = 0;
         return hipGetDevice(&dev) == hipSuccess &&
@@ -996,12 +803,11 @@ extern "C" int hpnn_gemm_fm_direct_update(const void *Dg, const void *Hg, int h_
                    : 0;
     }();
     static const int tails_env = [] { const char *e = getenv("HPNN_G0_TAILS"); return e ? atoi(e) : -1; }();
-    static const int tail_pct = [] { const char *e = getenv("HPNN_G0_TAIL12"); return e ? atoi(e) : 100; }();
     /* one tail per 16 slab rows (each sums ~16 x the [G1 | G2] block, 563 KB on MNIST), at most
      * the CUs the GEMM grid leaves idle: ranks sharing one GPU (tests, rehearsals) keep their
      * grids small enough to co-run */
     int ntail = tails_env >= 0 ? tails_env : std::min(cus - tiles * splits, std::max(1, u->mrows / 16));
-    if (ntail < 0 || tail_pct <= 0) ntail = 0;
+    if (ntail < 0) ntail = 0;
     if (ntail > 64) ntail = 64;
     while (ntail > 0 && !g0_fused_resident(tiles * splits + ntail)) ntail--;
     if (u->xchg && tiles * splits + ntail > HPNN_XAR_MAX_BLOCKS) ntail = HPNN_XAR_MAX_BLOCKS - tiles * splits;
@@ -1016,7 +822,6 @@ extern "C" int hpnn_gemm_fm_direct_update(const void *Dg, const void *Hg, int h_
     }
     const int xcd_map = (splits >= 8 && tiles > 1) ? 1 : 0;
     hpnn_g0_update uu = *u;
-    uu.n12t = ntail ? ((long)(u->n12 / 4) * (tail_pct > 100 ? 100 : tail_pct) / 100) * 4 : 0;
 #ifdef HPNN_ABLATIONS
     static const int proto = [] { const char *e = getenv("HPNN_G0_PROTO"); return e ? atoi(e) : 0; }();
     uu.proto |= proto;
@@ -1026,27 +831,23 @@ extern "C" int hpnn_gemm_fm_direct_update(const void *Dg, const void *Hg, int h_
     hipLaunchKernelGGL((g0_fused_kernel<__VA_ARGS__>), dim3(tiles * splits + ntail), dim3(512), 0, stream,           \
                        (const __bf16 *)Dg,                                                                         \
                        N / 16, Hg, M / 16, hscale, slab, ldg, N, Bt / 32, splits, tiles_n, tiles, xcd_map, uu)
-    if (tm == 80) {
-        /* HPNN_G0_PD=2 (ABLATIONS builds, tuning): two k-steps of operands in flight */
+    /* HPNN_G0_PD=2 (ABLATIONS builds, tuning): two k-steps of operands in flight */
 #ifdef HPNN_ABLATIONS
-        static const int pd = [] { const char *e = getenv("HPNN_G0_PD"); return e ? atoi(e) : 1; }();
-        static const bool x16 = [] { const char *e = getenv("HPNN_G0_X16"); return e && e[0] == '1'; }();
-        if (h_u8 && pd == 2) HPNN_G0F(5, 4, 2, 4, true, false, 1, 2);
-        else if (h_u8 && x16) HPNN_G0F(5, 4, 1, 4, true, false, 1, 2, true);
-        else
+    static const int pd = [] { const char *e = getenv("HPNN_G0_PD"); return e ? atoi(e) : 1; }();
+    static const bool x16 = [] { const char *e = getenv("HPNN_G0_X16"); return e && e[0] == '1'; }();
+    if (h_u8 && pd == 2) HPNN_G0F(5, 4, 2, 4, true, false, 1, 2);
+    else if (h_u8 && x16) HPNN_G0F(5, 4, 1, 4, true, false, 1, 2, true);
+    else
 #endif
-        if (h_u8 && trace) HPNN_G0F(5, 4, 1, 4, true, true, 1, 2);
-        else if (h_u8) HPNN_G0F(5, 4, 1, 4, true, false, 1, 2);
-        else HPNN_G0F(5, 4, 1, 4, false, false, 1, 2);
-    } else if (h_u8 && trace) HPNN_G0F(5, 4, 1, 2, true, true);
-    else if (h_u8) HPNN_G0F(5, 4, 1, 2, true, false);
-    else HPNN_G0F(5, 4, 1, 2, false, false);
+    if (h_u8 && trace) HPNN_G0F(5, 4, 1, 4, true, true, 1, 2);
+    else if (h_u8) HPNN_G0F(5, 4, 1, 4, true, false, 1, 2);
+    else HPNN_G0F(5, 4, 1, 4, false, false, 1, 2);
 #undef HPNN_G0F
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
 extern "C" int hpnn_gemm_fm_direct_update_ok(int ldg, int N, int M, int Bt, int splits) {
-    const int tiles = hpnn_g0_tiles(1, N, M);
+    const int tiles = hpnn_g0_tiles(N, M);
     if (!(g0_fused_on() && tiles > 0 && Bt % 32 == 0 && splits >= 1 && splits <= Bt / 32 && ldg == M &&
           tiles <= HPNN_G0_MAX_TILES))
         return 0;

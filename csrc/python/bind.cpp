@@ -182,7 +182,6 @@ void bind_plan(py::module_ &m) {
              })
         .def_readwrite("g0_fused", &BPlan::g0_fused)
         .def_readwrite("g0_perm", &BPlan::g0_perm)
-        .def_readwrite("g0_xcd", &BPlan::g0_xcd)
         .def_readwrite("tn_update", &BPlan::tn_update)
         .def_readwrite("tn8_side", &BPlan::tn8_side)
         .def_readwrite("side_launches", &BPlan::side_launches)

@@ -27,7 +27,7 @@ def main():
     torch.cuda.synchronize()
     import ctypes
     from hpnn_amd._lib import lib_path
-    G = ctypes.CDLL(lib_path()).hpnn_g0_tiles(1, m.Np[0], m.Kp[0]) * m.S[0]
+    G = ctypes.CDLL(lib_path()).hpnn_g0_tiles(m.Np[0], m.Kp[0]) * m.S[0]
     ta = torch.tensor(native().g0_trace(), dtype=torch.float64).view(512, 8)
     t = ta[:G]
     print(f"workgroups {G}; span median {float((t[:, 5] - t[:, 0]).median()):.0f} ticks")

@@ -212,8 +212,8 @@ def test_tn_update_fused_matches_separate(gpu, momentum):
 def test_production_step_matches_oracle(gpu, momentum):
     """The headline step itself (bench.py's config) against the FP64 oracle: MNIST
     784-128-64-10 SNN, batch 65 536, 8-bit pixels, the tile front + the fused first-layer
-    gradient launch at its default split count (48: split-K reduction, optimizer steps and
-    the [G1 | G2] share in one launch).  Two steps; the oracle runs in FP64 on the GPU on the
+    gradient launch at its default split count (24, on 80 x 128 tiles: split-K reduction,
+    optimizer steps and the [G1 | G2] share in one launch).  Two steps; the oracle runs in FP64 on the GPU on the
     same inputs (pixel / 255 rounded to BF16, as the front sees them) and the same initial
     weights.  Same bounds as test_train_step_matches_oracle.  Reference step math:
     snn.c:798-1074, batched."""
