@@ -18,7 +18,7 @@
  *                                  random()*n/RAND_MAX == n overflow is
  *                                  rejected instead of indexing past the end)
  *   nn_run_kernel                 :1306-1536
- * Extensions: [mode] online|batched, [dtype], [device], [batch], [epochs],
+ * Extensions: [mode] online|batched, [dtype], [device], [batch], [epochs], [shuffle],
  * [lr], [momentum] conf keys; batched training on CPU (FP64) or GPU.
  */
 #include <libhpnn/ann.h>
@@ -114,6 +114,9 @@ extern "C" void _NN(set, mode)(nn_def *c, nn_mode m) { c->mode = m; }
 extern "C" nn_mode _NN(return, mode)(nn_def *c) { return c->mode; }
 extern "C" void _NN(set, dtype)(nn_def *c, nn_dtype d) { c->dtype = d; }
 extern "C" nn_dtype _NN(return, dtype)(nn_def *c) { return c->dtype; }
+extern "C" void _NN(set, shuffle)(nn_def *c, nn_shuffle v) { c->shuffle = v == NN_SHUFFLE_EPOCH ? NN_SHUFFLE_EPOCH : NN_SHUFFLE_ONCE; }
+extern "C" void _NN(get, shuffle)(nn_def *c, nn_shuffle *v) { *v = c->shuffle; }
+extern "C" nn_shuffle _NN(return, shuffle)(nn_def *c) { return c->shuffle; }
 extern "C" void _NN(set, device)(nn_def *c, nn_device d) { c->device = d; }
 extern "C" nn_device _NN(return, device)(nn_def *c) { return c->device; }
 extern "C" void _NN(set, batch)(nn_def *c, UINT b) { c->batch = b ? b : 1; }
@@ -232,6 +235,12 @@ extern "C" nn_def *_NN(load, conf)(const CHAR *filename) {
             else if (u == "f32" || u == "fp32" || u == "float") conf->dtype = NN_DTYPE_F32;
             else if (u == "f64" || u == "fp64" || u == "double") conf->dtype = NN_DTYPE_F64;
             else CONF_FAIL("[dtype] unknown: %s (f64 | f32 | bf16)\n", v.c_str()); /* docs/PARITY.md */
+        } else if (is("shuffle")) {
+            std::string u = v;
+            for (auto &ch : u) ch = (char)tolower(ch);
+            if (u == "epoch") conf->shuffle = NN_SHUFFLE_EPOCH;
+            else if (u == "once") conf->shuffle = NN_SHUFFLE_ONCE;
+            else CONF_FAIL("[shuffle] unknown: %s (once | epoch)\n", v.c_str());
         } else if (is("device")) {
             std::string u = v;
             for (auto &ch : u) ch = (char)tolower(ch);
@@ -308,6 +317,7 @@ extern "C" void _NN(dump, conf)(nn_def *conf, FILE *fp) {
              dn[conf->dtype]);
         if (conf->parallel == NN_PARALLEL_TP) _OUT(fp, "[parallel] tp\n");
     }
+    if (conf->shuffle == NN_SHUFFLE_EPOCH) _OUT(fp, "[shuffle] epoch\n");
     if (conf->lr > 0) _OUT(fp, "[lr] %.17g\n", conf->lr);
     if (conf->momentum >= 0) _OUT(fp, "[momentum] %.17g\n", conf->momentum);
 }
@@ -522,6 +532,7 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
         o.seed = conf->seed;
         o.resume = conf->resume && k->dw != NULL;
         o.epoch0 = conf->epochs_done;
+        o.shuffle = conf->shuffle == NN_SHUFFLE_EPOCH ? 1 : 0;
         UINT ng = 1;
         _NN(get, n_gpu)(&ng);
         o.n_gpu = ng ? ng : 1;
@@ -557,6 +568,11 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
     }
 
     /* online (reference) mode */
+    if (conf->shuffle == NN_SHUFFLE_EPOCH) {
+        static bool warned = false; /* no epochs here: every sample is trained to convergence once */
+        if (!warned) NN_WARN(stderr, "[shuffle] epoch has no effect in online mode (ignored)\n");
+        warned = true;
+    }
     std::vector<UINT> order = seeded_order((UINT)src.size(), conf->seed);
     UINT n_ok = 0, n_done = 0;
     for (UINT idx : order) {

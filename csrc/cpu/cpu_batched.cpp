@@ -15,6 +15,7 @@
  */
 #include <libhpnn/ann.h>
 #include <libhpnn/observe.h>
+#include <libhpnn/shuffle.h>
 #include <math.h>
 #include <string.h>
 #include <chrono>
@@ -147,15 +148,35 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
         if (!keep) ann_raz_momentum(k);
     }
     const UINT B = o->batch ? o->batch : 1;
+    /* [shuffle] epoch: epoch e trains on a permuted copy, position i = sample src(i) of
+     * <libhpnn/shuffle.h> for (n, seed, epochs completed); one batch per epoch: nothing to do */
+    const bool shuffle = o->shuffle && B < n;
+    if (o->shuffle && !shuffle) NN_OUT(stdout, "batched CPU training: one batch per epoch, no reshuffle\n");
+    std::vector<DOUBLE> Xs, Ts;
+    std::vector<unsigned int> perm;
+    if (shuffle) {
+        NN_OUT(stdout, "batched CPU training: samples reshuffled every epoch\n");
+        Xs.resize((size_t)n * k->n_inputs);
+        Ts.resize((size_t)n * k->n_outputs);
+        perm.resize(n);
+    }
+    const DOUBLE *Xe = shuffle ? Xs.data() : X, *Te = shuffle ? Ts.data() : T;
     auto t0 = std::chrono::steady_clock::now();
     UINT64 samples = 0;
     DOUBLE last = 0.0;
     for (UINT e = 0; e < o->epochs; e++) {
         DOUBLE acc = 0.0;
         UINT nb = 0, hits = 0;
+        if (shuffle) {
+            hpnn_shuffle_perm(n, o->seed, o->epoch0 + e, perm.data());
+            for (UINT i = 0; i < n; i++) {
+                memcpy(&Xs[(size_t)i * k->n_inputs], X + (size_t)perm[i] * k->n_inputs, sizeof(DOUBLE) * k->n_inputs);
+                memcpy(&Ts[(size_t)i * k->n_outputs], T + (size_t)perm[i] * k->n_outputs, sizeof(DOUBLE) * k->n_outputs);
+            }
+        }
         for (UINT s = 0; s < n; s += B) {
             UINT b = (n - s < B) ? n - s : B;
-            last = hpnn_cpu_batched_step(k, o->type, X + (size_t)s * k->n_inputs, T + (size_t)s * k->n_outputs, b,
+            last = hpnn_cpu_batched_step(k, o->type, Xe + (size_t)s * k->n_inputs, Te + (size_t)s * k->n_outputs, b,
                                          o->lr, mom, o->alpha, &hits);
             acc += last;
             nb++;
@@ -188,4 +209,8 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
     }
     /* the momentum stays in k->dw: nn_dump_state saves it for an exact resume */
     return TRUE;
+}
+
+extern "C" void hpnn_epoch_perm(UINT n, UINT seed, UINT epoch, UINT *out) {
+    if (out) hpnn_shuffle_perm(n, seed, epoch, out);
 }

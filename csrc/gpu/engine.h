@@ -51,6 +51,8 @@ typedef struct {
     BOOL resume;      /* BPM: start from the momentum in k->dw (exact resume)  */
     UINT epoch0;      /* epochs completed before this call (metrics numbering) */
     UINT tp;          /* 1: row-sharded tensor parallelism ([parallel] tp; f64 / f32 / bf16) */
+    UINT shuffle;     /* 1: a new sample order every epoch (<libhpnn/shuffle.h>, epoch = epoch0 + e;
+                       * single-device engines only); 0: the order drawn once */
 } hpnn_batched_opts;
 
 typedef struct {

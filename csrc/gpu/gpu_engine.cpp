@@ -734,6 +734,30 @@ struct Batched {
         xs->u8 = 0;
         return TRUE;
     }
+    /* [shuffle] epoch: the row-major canonical copies (cn) the gathers read; xs, from upload_x,
+     * is the staging set in the plan's layout that the steps read */
+    static constexpr bool dense_always = false; /* with labels the dense targets are not read */
+    BOOL upload_canon(const DOUBLE *src, int rows, int cols, const XSet &xs, XSet *cn) {
+        const int lay = fm_ok ? p.input_layout() : 0, Kp0 = p.Kp[0];
+        if (xs.u8) {
+            std::vector<uint8_t> h((size_t)rows * Kp0, 0);
+            for (int r = 0; r < rows; r++)
+                for (int c = 0; c < cols; c++) h[(size_t)r * Kp0 + c] = (uint8_t)src[(size_t)r * cols + c];
+            void **dst = lay == 1 ? &cn->x : &cn->xg;
+            HIPCHK(hpnn_dev_malloc(dst, h.size()));
+            HIPCHK(hipMemcpyAsync(*dst, h.data(), h.size(), hipMemcpyHostToDevice, s));
+            HIPCHK(hipStreamSynchronize(s));
+            if (lay == 1) return TRUE;
+        }
+        return upload_bf16(src, rows, cols, rows, Kp0, &cn->x, s);
+    }
+    BOOL gather(const XSet &cn, const XSet &xs, const int *perm, int n, int rows_p) {
+        const int lay = fm_ok ? p.input_layout() : 0, Kp0 = p.Kp[0];
+        rows_p = pad_rows(rows_p, 32);
+        if (lay == 1) return hpnn_gather_fm(xs.x, cn.x, perm, n, rows_p, Kp0, xs.u8 ? 1 : 2, s) == 0;
+        if (hpnn_gather_rows(xs.x, cn.x, perm, n, rows_p, (long)Kp0 * 2, s)) return FALSE;
+        return !xs.xg || hpnn_gather_fm(xs.xg, cn.xg, perm, n, rows_p, Kp0, 1, s) == 0;
+    }
     hpnn::XIn at(const XSet &xs, long row) const {
         hpnn::XIn v;
         v.x = (const char *)xs.x + row * xs.row_bytes;
@@ -938,6 +962,13 @@ struct BatchedFP {
         HIPCHK(hipStreamSynchronize(s));
         xs->row_bytes = (size_t)cols * sizeof(T);
         return TRUE;
+    }
+    static constexpr bool dense_always = true;
+    BOOL upload_canon(const DOUBLE *src, int rows, int cols, const XSet &, XSet *cn) {
+        return upload_x(src, rows, cols, rows, cn);
+    }
+    BOOL gather(const XSet &cn, const XSet &xs, const int *perm, int n, int rows_p) {
+        return hpnn_gather_rows(xs.x, cn.x, perm, n, rows_p, (long)xs.row_bytes, s) == 0;
     }
     static const void *at(const XSet &xs, long row) { return (const char *)xs.x + row * xs.row_bytes; }
     static int reduce_sum(grad_t *buf, int G, size_t count, hipStream_t st) {
@@ -1256,7 +1287,10 @@ namespace {
 
 /* HIP graph of one epoch's steps (HPNN_GRAPH=0: eager launches): the epoch's minibatches
  * are the same every epoch (the sample order is drawn once, libhpnn.c:1218-1229), so one
- * capture is replayed per epoch and the host launches nothing per step.  Returns FALSE when
+ * capture is replayed per epoch and the host launches nothing per step.  With [shuffle] epoch
+ * the launches are still the same every epoch: the captured epoch starts with the permutation
+ * kernel (its epoch read from a device word a captured one-thread launch advances) and the
+ * gathers into the staging set the steps read.  Returns FALSE when
  * the launches cannot be captured (the caller then runs them eagerly: nothing of a failed
  * capture was executed). */
 template <class Launch>
@@ -1311,7 +1345,45 @@ BOOL train_single(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, const
         HIPCHK(hpnn_dev_malloc(&Td, tf.size() * sizeof(TT)));
         HIPCHK(hipMemcpy(Td, tf.data(), tf.size() * sizeof(TT), hipMemcpyHostToDevice));
     }
+    /* [shuffle] epoch: xs / Td are a staging set; every epoch starts with the permutation of
+     * (n, seed, epochs completed) and the gathers of the canonical row-major copies into it,
+     * all on the compute stream (so inside the captured epoch).  One batch per epoch: the
+     * order only changes the summation order, nothing is reshuffled. */
+    const bool shuffle = o->shuffle && n_batches > 1;
+    if (o->shuffle && !shuffle) NN_OUT(stdout, "batched GPU training: one batch per epoch, no reshuffle\n");
+    XSet cn;
+    TT *Tc = nullptr;
+    int *perm = nullptr;
+    unsigned int *shw = nullptr; /* [0] the epoch word, [1] the permutation kernel's error word */
+    const bool dense = Net::dense_always || !xs.lab;
+    if (shuffle) {
+        NN_OUT(stdout, "batched GPU training: samples reshuffled every epoch\n");
+        const unsigned int w0[2] = {o->epoch0, 0u};
+        if (!net.upload_canon(X, (int)n, (int)k->n_inputs, xs, &cn)) return FALSE;
+        HIPCHK(hpnn_dev_malloc(&perm, (size_t)n * sizeof(int)));
+        HIPCHK(hpnn_dev_malloc(&shw, sizeof w0));
+        HIPCHK(hipMemcpy(shw, w0, sizeof w0, hipMemcpyHostToDevice));
+        if (xs.lab) {
+            HIPCHK(hpnn_dev_malloc(&cn.lab, (size_t)n * sizeof(int)));
+            HIPCHK(hipMemcpy(cn.lab, xs.lab, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice));
+        }
+        if (dense) {
+            const size_t tb = (size_t)n * k->n_outputs * sizeof(TT);
+            HIPCHK(hpnn_dev_malloc(&Tc, tb));
+            HIPCHK(hipMemcpy(Tc, Td, tb, hipMemcpyDeviceToDevice));
+        }
+    }
+    auto reshuffle = [&]() -> bool {
+        if (hpnn_epoch_perm_dev(perm, (int)n, o->seed, shw, shw + 1, s) || hpnn_epoch_advance(shw, s)) return false;
+        if (!net.gather(cn, xs, perm, (int)n, rows_p)) return false;
+        if (xs.lab && hpnn_gather_rows(xs.lab, cn.lab, perm, (int)n, rows_p, 4, s)) return false;
+        return !dense || hpnn_gather_rows(Td, Tc, perm, (int)n, rows_p, (long)k->n_outputs * sizeof(TT), s) == 0;
+    };
     auto epoch = [&]() -> bool {
+        if (shuffle && !reshuffle()) {
+            NN_ERROR(stderr, "batched GPU training: the epoch reshuffle could not be launched\n");
+            return false;
+        }
         for (int b = 0; b < n_batches; b++) {
             const int nv = (b == n_batches - 1) ? (int)n - b * B : B;
             if (!net.step(xs, (long)b * B, Td + (size_t)b * B * k->n_outputs, (int)k->n_outputs, nv, o->lr, o->alpha,
@@ -1357,7 +1429,12 @@ BOOL train_single(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, const
         hipEventCreateWithFlags(&hev[1], hipEventDisableTiming) != hipSuccess)
         ok = FALSE;
     int pend = -1, slot = 0;
-    auto judge = [&](int sl) -> bool { return hipEventSynchronize(hev[sl]) == hipSuccess && net.health_ok(hw + 4 * sl); };
+    auto judge = [&](int sl) -> bool {
+        if (hipEventSynchronize(hev[sl]) != hipSuccess || !net.health_ok(hw + 4 * sl)) return false;
+        if (hw[4 * sl + 3] == 0) return true;
+        NN_ERROR(stderr, "batched GPU training: the epoch permutation did not terminate within its bound; stopping\n");
+        return false;
+    };
     for (int e = 0; e < E && ok;) {
         const int ne = std::min(epg, E - e);
         auto g = graphs.find(ne);
@@ -1365,8 +1442,10 @@ BOOL train_single(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, const
         e += ne;
         if (ok) {
             unsigned int *d = hw + 4 * slot;
-            d[0] = d[1] = d[2] = 0;
-            ok = net.health_enqueue(d) && hipEventRecord(hev[slot], s) == hipSuccess;
+            d[0] = d[1] = d[2] = d[3] = 0;
+            ok = net.health_enqueue(d) &&
+                 (!shuffle || hipMemcpyAsync(d + 3, shw + 1, 4, hipMemcpyDeviceToHost, s) == hipSuccess) &&
+                 hipEventRecord(hev[slot], s) == hipSuccess;
         }
         if (ok && pend >= 0) ok = judge(pend);
         pend = ok ? slot : -1;
@@ -1397,7 +1476,11 @@ BOOL train_single(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, const
         st->last_loss = st->epoch_loss;
     }
     xs.release();
+    cn.release();
     hpnn_dev_free(Td);
+    hpnn_dev_free(Tc);
+    hpnn_dev_free(perm);
+    hpnn_dev_free(shw);
     /* device FP64 copy of the online engine (if any) is now stale */
     if (k->gpu) ((GpuModel *)k->gpu)->host_newer = true;
     return ok;
@@ -1413,6 +1496,10 @@ BOOL train_dp(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, const hpn
     typedef typename Net::target_t TT;
     typedef typename Net::grad_t GT;
     if (k->n_hiddens + 1 > 16 || G < 1) return FALSE;
+    if (o->shuffle) {
+        NN_ERROR(stderr, "[shuffle] epoch is not supported by data-parallel batched training (one device only)\n");
+        return FALSE;
+    }
     if (!loopback && !hpnn_comm_available()) return FALSE;
     hpnn_gpu_sync_host(k);
     const int B = (int)(o->batch ? o->batch : 256);
@@ -1650,6 +1737,10 @@ BOOL train_dp_mp(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, const 
     typedef typename Net::target_t TT;
     const int W = hpnn_boot_world(), R = hpnn_boot_rank();
     if (k->n_hiddens + 1 > 16 || W < 1 || W > 64) return FALSE;
+    if (o->shuffle) {
+        NN_ERROR(stderr, "[shuffle] epoch is not supported by data-parallel batched training (one device only)\n");
+        return FALSE;
+    }
     hpnn_gpu_sync_host(k);
     const int dev = hpnn_rt_device(0);
     HIPCHK(hipSetDevice(dev));

@@ -199,6 +199,24 @@ int hpnn_hash_words(const void *p, long nbytes, long base, unsigned long long *o
  * first eager step does not pay for it.  Once per device; 0 on success. */
 int hpnn_preload_code_objects(void);
 
+/* ---- per-epoch reshuffle of the resident training set (kernels_shuffle.hip) ----
+ * perm[i] = src(i) of <libhpnn/shuffle.h> for (n, seed, *epoch_word); a walk that passes
+ * HPNN_SHUFFLE_MAX_WALK iterations sets *err (never with a correct build) */
+int hpnn_epoch_perm_dev(int *perm, int n, unsigned int seed, const unsigned int *epoch_word, unsigned int *err,
+                        hipStream_t stream);
+/* *epoch_word += 1 in a one-thread launch: ordered behind the launches that read the word, so
+ * a replayed graph of several epochs sees e, e + 1, .. with no host involvement */
+int hpnn_epoch_advance(unsigned int *epoch_word, hipStream_t stream);
+/* row-major: dst row i = src row perm[i] (i < n), zero rows n .. rows_p - 1; row_bytes % 4 == 0
+ * (16-byte accesses when rows and pointers allow); an index outside [0, n) gives a zero row */
+int hpnn_gather_rows(void *dst, const void *src, const int *perm, int n, long rows_p, long row_bytes,
+                     hipStream_t stream);
+/* row-major src [n][Kp] (elem_bytes 1 or 2) -> fragment-major dst [rows_p/32][Kp/16][64][8]
+ * (lane 16 g + r of fragment (t, cb) holds A[32 t + 8 g + j][16 cb + r]) of the permuted rows,
+ * zero rows from n up; rows_p % 32 == 0, Kp % 16 == 0, 16-byte aligned pointers */
+int hpnn_gather_fm(void *dst, const void *src_rowmajor, const int *perm, int n, long rows_p, int Kp, int elem_bytes,
+                   hipStream_t stream);
+
 /* output layer: logits Z [B x ldz] FP32 (n_out valid columns) ->
  *   delta  D [B x ldd] BF16  (zero in padded rows/cols)
  *   loss_acc[slot] += sum of per-sample loss over valid rows (slot array, above)

@@ -307,6 +307,20 @@ PYBIND11_MODULE(_native, m) {
                           uptr stream) {
         check(hpnn_pack_bf16(P(src), src_f64, rows, cols, lds, P(dst), prow, pcol, ldd, S(stream)), "pack_bf16");
     });
+    m.def("epoch_perm", [](uptr perm, int n, unsigned int seed, uptr epoch_word, uptr err, uptr stream) {
+        check(hpnn_epoch_perm_dev((int *)P(perm), n, seed, (const unsigned int *)P(epoch_word),
+                                  (unsigned int *)P(err), S(stream)),
+              "epoch_perm");
+    });
+    m.def("epoch_advance", [](uptr epoch_word, uptr stream) {
+        check(hpnn_epoch_advance((unsigned int *)P(epoch_word), S(stream)), "epoch_advance");
+    });
+    m.def("gather_rows", [](uptr dst, uptr src, uptr perm, int n, long rows_p, long row_bytes, uptr stream) {
+        check(hpnn_gather_rows(P(dst), P(src), (const int *)P(perm), n, rows_p, row_bytes, S(stream)), "gather_rows");
+    });
+    m.def("gather_fm", [](uptr dst, uptr src, uptr perm, int n, long rows_p, int Kp, int elem_bytes, uptr stream) {
+        check(hpnn_gather_fm(P(dst), P(src), (const int *)P(perm), n, rows_p, Kp, elem_bytes, S(stream)), "gather_fm");
+    });
     m.def("fill_f32", [](uptr p, long n, float v, uptr stream) {
         check(hpnn_fill_f32((float *)P(p), n, v, S(stream)), "fill_f32");
     });

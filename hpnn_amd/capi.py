@@ -20,6 +20,7 @@ NN_TRAIN = {"BP": 0, "BPM": 1, "CG": 2, "SPLX": 3}
 NN_MODE = {"online": 0, "batched": 1}
 NN_DTYPE = {"f64": 0, "f32": 1, "bf16": 2}
 NN_DEVICE = {"auto": 0, "cpu": 1, "gpu": 2}
+NN_SHUFFLE = {"once": 0, "epoch": 1}
 
 
 def lib():
@@ -43,6 +44,8 @@ def lib():
             "nn_get_n_inputs": (u, [vp]), "nn_get_n_hiddens": (u, [vp]), "nn_get_n_outputs": (u, [vp]),
             "nn_get_h_neurons": (u, [vp, u]),
             "nn_set_mode": (None, [vp, i]), "nn_set_dtype": (None, [vp, i]), "nn_set_device": (None, [vp, i]),
+            "nn_set_shuffle": (None, [vp, i]), "nn_return_shuffle": (i, [vp]),
+            "hpnn_epoch_perm": (None, [u, u, u, vp]),
             "nn_set_batch": (None, [vp, u]), "nn_set_epochs": (None, [vp, u]),
             "nn_set_learning_rate": (None, [vp, d]), "nn_set_momentum": (None, [vp, d]),
             "nn_set_seed": (None, [vp, u]), "nn_return_seed": (u, [vp]),
@@ -101,7 +104,8 @@ class Network:
             pass
 
     # configuration
-    def set(self, mode=None, dtype=None, device=None, batch=None, epochs=None, lr=None, momentum=None, seed=None):
+    def set(self, mode=None, dtype=None, device=None, batch=None, epochs=None, lr=None, momentum=None, seed=None,
+            shuffle=None):
         if mode is not None:
             self.L.nn_set_mode(self.ptr, NN_MODE[mode])
         if dtype is not None:
@@ -118,7 +122,13 @@ class Network:
             self.L.nn_set_momentum(self.ptr, momentum)
         if seed is not None:
             self.L.nn_set_seed(self.ptr, seed)
+        if shuffle is not None:  # "once" | "epoch" (or a bool: True = "epoch")
+            self.L.nn_set_shuffle(self.ptr, NN_SHUFFLE[shuffle] if isinstance(shuffle, str) else int(bool(shuffle)))
         return self
+
+    @property
+    def shuffle(self):
+        return {v: k for k, v in NN_SHUFFLE.items()}[self.L.nn_return_shuffle(self.ptr)]
 
     @property
     def dims(self):
@@ -159,6 +169,15 @@ class Network:
     @property
     def epochs_done(self):
         return self.L.nn_return_epochs_done(self.ptr)
+
+
+def hpnn_epoch_perm(n, seed, epoch):
+    """the [shuffle] epoch permutation (include/libhpnn/shuffle.h) as a numpy uint32 array:
+    out[i] = index, in the order drawn once from [seed], of the sample at position i of `epoch`"""
+    import numpy as np
+    out = np.empty(int(n), dtype=np.uint32)
+    lib().hpnn_epoch_perm(int(n), int(seed) & 0xffffffff, int(epoch) & 0xffffffff, out.ctypes.data)
+    return out
 
 
 def pack_samples(sample_dir, out_path):

@@ -207,6 +207,55 @@ class MLP:
         ops.pack_bf16(Xd.contiguous(), out)
         return out
 
+    def canonical_rows(self, X, pixel_scale=None):
+        """[n, n_in] -> the device-resident row-major set MLP.gather_input reads: a dict with
+        "x" = [n, Kp0] rows in the element type of the plan's input layout (uint8 for 8-bit data
+        on the tile path, else BF16; the values prepare_input gives) and, for 8-bit data in
+        mode "x", "xg" = the [n, Kp0] bytes of the first-layer gradient's copy."""
+        ps = PIXEL_SCALE if pixel_scale is None else float(pixel_scale)
+        Xd = X.to(self.device)
+        n = Xd.shape[0]
+        layout = self.cfg["input_layout"] if self._gpu else 0
+        u8 = Xd.dtype == torch.uint8
+        rows = {"n": n, "scale": ps if u8 else 1.0}
+        if u8:
+            b = torch.zeros(n, self.Kp[0], dtype=torch.uint8, device=self.device)
+            b[:, :Xd.shape[1]] = Xd
+            if layout == 1:
+                rows["x"] = b
+                return rows
+            if layout == 2:
+                rows["xg"] = b
+            rows["x"] = (b.float() * ps).bfloat16()
+            return rows
+        rows["x"] = ops.pack_bf16(Xd.contiguous(), torch.empty(n, self.Kp[0], dtype=torch.bfloat16,
+                                                               device=self.device))
+        return rows
+
+    def gather_input(self, X_rows, perm, pixel_scale=None):
+        """what prepare_input(X[perm]) returns, gathered on the device (ops.gather_rows /
+        ops.gather_fragment_major) from a resident row-major set: X_rows is canonical_rows(X),
+        or X itself (converted first); perm an int32 device tensor of row indices."""
+        if not isinstance(X_rows, dict):
+            X_rows = self.canonical_rows(X_rows, pixel_scale)
+        perm = perm.to(device=self.device, dtype=torch.int32).contiguous()
+        n = perm.numel()
+        layout = self.cfg["input_layout"] if self._gpu else 0
+        rows = max(self.Bp, ops.pad_to(n, 256 if layout == 1 else 128))
+        x = X_rows["x"]
+        if layout == 1:
+            out = torch.empty(rows // 32, self.Kp[0] // 16, 64, 8, dtype=x.dtype, device=self.device)
+            ops.gather_fragment_major(x, perm, out)
+            out.hpnn_fm_scale = X_rows["scale"]
+            return out
+        out = ops.gather_rows(x, perm, torch.empty(rows, self.Kp[0], dtype=torch.bfloat16, device=self.device))
+        if "xg" in X_rows:
+            out.hpnn_fm = ops.gather_fragment_major(
+                X_rows["xg"], perm, torch.empty(rows // 32, self.Kp[0] // 16, 4, 16, 8, dtype=torch.uint8,
+                                                device=self.device))
+            out.hpnn_fm_scale = X_rows["scale"]
+        return out
+
     @staticmethod
     def _is_fm(X):
         return X.dim() >= 4

@@ -443,6 +443,71 @@ def pack_bf16(src, dst):
     return dst
 
 
+def epoch_perm(n, seed, epoch, device, out=None, err=None, advance=False):
+    """int32 [n] permutation of epoch `epoch` ([shuffle] epoch, include/libhpnn/shuffle.h):
+    out[i] = the sample at position i.  `epoch` is an int, or a 1-element int32 device tensor
+    (the epoch word: read by the kernel, so a captured launch follows it); advance=True adds
+    one to that word in a launch of its own behind the kernel.  err (1-element int32 tensor)
+    is set when the bounded walk did not terminate; without it that raises."""
+    device = torch.device(device)
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=device)
+    if device.type == "cpu":
+        from .. import capi
+        e = int(epoch.item()) if torch.is_tensor(epoch) else int(epoch)
+        out.copy_(torch.from_numpy(capi.hpnn_epoch_perm(n, seed, e).astype("int32")))
+        if advance and torch.is_tensor(epoch):
+            epoch += 1
+        return out
+    word = epoch if torch.is_tensor(epoch) else torch.tensor([int(epoch) & 0xffffffff], dtype=torch.int64,
+                                                              device=device).to(torch.int32)
+    assert word.dtype == torch.int32 and word.numel() == 1 and out.dtype == torch.int32 and out.numel() >= n
+    own_err = err is None
+    if own_err:
+        err = torch.zeros(1, dtype=torch.int32, device=device)
+    native().epoch_perm(out.data_ptr(), n, int(seed) & 0xffffffff, word.data_ptr(), err.data_ptr(), _stream())
+    if advance:
+        native().epoch_advance(word.data_ptr(), _stream())
+    if own_err and not torch.cuda.is_current_stream_capturing() and int(err.item()):
+        raise RuntimeError("epoch_perm: the permutation walk did not terminate within its bound")
+    return out
+
+
+def gather_rows(src, perm, out, n=None):
+    """row-major gather: out[i] = src[perm[i]] for i < n (default len(perm)), zero rows from n
+    up.  Rows of any dtype whose byte size is a multiple of 4; src, out contiguous."""
+    n = perm.numel() if n is None else int(n)
+    rb = src[0].numel() * src.element_size()
+    assert src.is_contiguous() and out.is_contiguous() and perm.dtype == torch.int32 and perm.is_contiguous()
+    assert out.dtype == src.dtype and out[0].numel() == src[0].numel() and rb % 4 == 0
+    assert n <= perm.numel() and n <= out.shape[0] and n <= src.shape[0]
+    if _cpu(src):
+        out.zero_()
+        out[:n] = src[perm[:n].long()]
+        return out
+    native().gather_rows(out.data_ptr(), src.data_ptr(), perm.data_ptr(), n, out.shape[0], rb, _stream())
+    return out
+
+
+def gather_fragment_major(src, perm, out, n=None):
+    """out = to_fragment_major(zero-padded src[perm[:n]]): src row-major [rows, Kp] uint8 or
+    bfloat16 (Kp % 16 == 0), out fragment-major [rows_p/32, Kp/16, 64, 8] of the same dtype."""
+    n = perm.numel() if n is None else int(n)
+    Kp = src.shape[1]
+    rows_p = out.numel() // Kp
+    assert src.is_contiguous() and out.is_contiguous() and perm.dtype == torch.int32 and perm.is_contiguous()
+    assert src.dtype in (torch.uint8, torch.bfloat16) and out.dtype == src.dtype
+    assert Kp % 16 == 0 and rows_p % 32 == 0 and out.numel() == rows_p * Kp
+    assert n <= perm.numel() and n <= rows_p and n <= src.shape[0]
+    if _cpu(src):
+        pad = torch.zeros(rows_p, Kp, dtype=src.dtype)
+        pad[:n] = src[perm[:n].long()]
+        out.view(-1).copy_(to_fragment_major(pad).reshape(-1))
+        return out
+    native().gather_fm(out.data_ptr(), src.data_ptr(), perm.data_ptr(), n, rows_p, Kp, src.element_size(), _stream())
+    return out
+
+
 # --------------------------------------------------------------------------- references
 def bipolar(x):
     return 2.0 / (1.0 + torch.exp(-x)) - 1.0

@@ -93,6 +93,11 @@ typedef enum {
     NN_PARALLEL_TP = 1,
 } nn_parallel;
 
+typedef enum {
+    NN_SHUFFLE_ONCE = 0,  /* the sample order drawn once from [seed], replayed every epoch */
+    NN_SHUFFLE_EPOCH = 1, /* a new order every epoch of batched training (libhpnn/shuffle.h) */
+} nn_shuffle;
+
 typedef struct {
     nn_runtime *rr;  /* link to the runtime parameters */
     CHAR *name;
@@ -119,6 +124,8 @@ typedef struct {
     /* -- batched multi-GPU layout: [parallel] dp (replicas) | tp (rows of every hidden
      *    layer sharded over the GPUs / ranks; [dtype] f64 or f32) -- */
     nn_parallel parallel;
+    /* -- batched sample order: [shuffle] once (default) | epoch -- */
+    nn_shuffle shuffle;
 } nn_def;
 
 #define _NN(a, b) nn_##a##_##b
@@ -253,6 +260,13 @@ void _NN(set, learning_rate)(nn_def *conf, DOUBLE lr);
 DOUBLE _NN(return, learning_rate)(nn_def *conf);
 void _NN(set, momentum)(nn_def *conf, DOUBLE alpha);
 DOUBLE _NN(return, momentum)(nn_def *conf);
+/* batched sample order: once (default) or a new permutation every epoch */
+void _NN(set, shuffle)(nn_def *conf, nn_shuffle shuffle);
+void _NN(get, shuffle)(nn_def *conf, nn_shuffle *shuffle);
+nn_shuffle _NN(return, shuffle)(nn_def *conf);
+/* the [shuffle] epoch permutation (libhpnn/shuffle.h): out[i] = index, in the order drawn once
+ * from [seed], of the sample at position i of epoch `epoch` (epochs completed before it) */
+void hpnn_epoch_perm(UINT n, UINT seed, UINT epoch, UINT *out);
 /* write the kernel with %.17g (bit-exact round trip) instead of %17.15f */
 void _NN(dump, kernel_exact)(nn_def *conf, FILE *output);
 /* number of accurate predictions of the last nn_run_kernel call */

@@ -8,6 +8,8 @@
  * Extensions: -G N GPUs, -b N minibatch (implies batched mode), -e N epochs,
  *   -m online|batched, -d f64|f32|bf16, -c force the CPU engine,
  *   -l LR learning rate, -a ALPHA momentum,
+ *   -R (train_nn only) reshuffle the samples every epoch of batched training (same as
+ *   [shuffle] epoch),
  *   -r FILE exact-resume state (loaded when present, written after training),
  *   -M FILE JSON-lines metrics (same as HPNN_METRICS=FILE),
  *   -T trace ranges + timing table (same as HPNN_TRACE=1).
@@ -27,6 +29,7 @@ typedef struct {
     int mode;  /* -1 = from conf */
     int dtype; /* -1 = from conf */
     int force_cpu;
+    int reshuffle; /* -R */
     double lr, alpha;
     const char *state;   /* -r */
     const char *metrics; /* -M */
@@ -65,6 +68,11 @@ static int cli_parse(int argc, char **argv, cli_opts *o, int allow_x) {
             }
             if (c == 'c') {
                 o->force_cpu = 1;
+                j++;
+                continue;
+            }
+            if (c == 'R' && allow_x) {
+                o->reshuffle = 1;
                 j++;
                 continue;
             }
@@ -130,6 +138,7 @@ static void cli_apply_conf(const cli_opts *o, nn_def *conf) {
     if (o->batch) _NN(set, batch)(conf, o->batch);
     if (o->epochs) _NN(set, epochs)(conf, o->epochs);
     if (o->force_cpu) _NN(set, device)(conf, NN_DEVICE_CPU);
+    if (o->reshuffle) _NN(set, shuffle)(conf, NN_SHUFFLE_EPOCH);
     if (o->lr > 0) _NN(set, learning_rate)(conf, o->lr);
     if (o->alpha >= 0) _NN(set, momentum)(conf, o->alpha);
 }

@@ -31,6 +31,7 @@ static void dump_help(void) {
     _OUT(stdout, "-d D\tdtype: f64 | f32 | bf16.\n");
     _OUT(stdout, "-l X\tlearning rate.  -a X momentum.\n");
     _OUT(stdout, "-c \tforce the CPU engine.\n");
+    _OUT(stdout, "-R \treshuffle the samples every epoch (batched mode; [shuffle] epoch).\n");
     _OUT(stdout, "-r F\texact-resume state file (read if present, written after training).\n");
     _OUT(stdout, "-M F\tJSON-lines metrics file.  -T trace ranges + timing table.\n");
     _OUT(stdout, "***********************************\n");
