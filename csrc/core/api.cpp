@@ -18,7 +18,7 @@
  *                                  random()*n/RAND_MAX == n overflow is
  *                                  rejected instead of indexing past the end)
  *   nn_run_kernel                 :1306-1536
- * Extensions: [mode] online|batched, [dtype], [device], [batch], [epochs], [shuffle],
+ * Extensions: [mode] online|batched, [dtype], [device], [batch], [epochs], [shuffle], [validate],
  * [lr], [momentum] conf keys; batched training on CPU (FP64) or GPU.
  */
 #include <libhpnn/ann.h>
@@ -75,6 +75,9 @@ extern "C" void _NN(deinit, conf)(nn_def *conf) {
     free(conf->f_kernel);
     free(conf->samples);
     free(conf->tests);
+    free(conf->validation);
+    conf->validation = NULL;
+    conf->n_validation = 0;
     conf->name = conf->f_kernel = conf->samples = conf->tests = NULL;
 }
 
@@ -117,6 +120,20 @@ extern "C" nn_dtype _NN(return, dtype)(nn_def *c) { return c->dtype; }
 extern "C" void _NN(set, shuffle)(nn_def *c, nn_shuffle v) { c->shuffle = v == NN_SHUFFLE_EPOCH ? NN_SHUFFLE_EPOCH : NN_SHUFFLE_ONCE; }
 extern "C" void _NN(get, shuffle)(nn_def *c, nn_shuffle *v) { *v = c->shuffle; }
 extern "C" nn_shuffle _NN(return, shuffle)(nn_def *c) { return c->shuffle; }
+extern "C" void _NN(set, validate)(nn_def *c, UINT v) { c->validate = v; }
+extern "C" void _NN(get, validate)(nn_def *c, UINT *v) { *v = c->validate; }
+extern "C" UINT _NN(return, validate)(nn_def *c) { return c->validate; }
+extern "C" UINT _NN(get, validation)(nn_def *c, UINT max, UINT *epoch, DOUBLE *loss, UINT *correct, UINT *n) {
+    if (!c) return 0;
+    const hpnn_validation_record *r = (const hpnn_validation_record *)c->validation;
+    for (UINT i = 0; r && i < c->n_validation && i < max; i++) {
+        if (epoch) epoch[i] = r[i].epoch;
+        if (loss) loss[i] = r[i].loss;
+        if (correct) correct[i] = r[i].correct;
+        if (n) n[i] = r[i].n;
+    }
+    return r ? c->n_validation : 0;
+}
 extern "C" void _NN(set, device)(nn_def *c, nn_device d) { c->device = d; }
 extern "C" nn_device _NN(return, device)(nn_def *c) { return c->device; }
 extern "C" void _NN(set, batch)(nn_def *c, UINT b) { c->batch = b ? b : 1; }
@@ -241,6 +258,12 @@ extern "C" nn_def *_NN(load, conf)(const CHAR *filename) {
             if (u == "epoch") conf->shuffle = NN_SHUFFLE_EPOCH;
             else if (u == "once") conf->shuffle = NN_SHUFFLE_ONCE;
             else CONF_FAIL("[shuffle] unknown: %s (once | epoch)\n", v.c_str());
+        } else if (is("validate")) {
+            char *end = NULL;
+            const unsigned long every = strtoul(v.c_str(), &end, 10);
+            if (v.empty() || !isdigit((unsigned char)v[0]) || every == 0 || every > 0xffffffffUL)
+                CONF_FAIL("[validate] value: %s (epochs between validation passes, >= 1)\n", v.c_str());
+            conf->validate = (UINT)every;
         } else if (is("device")) {
             std::string u = v;
             for (auto &ch : u) ch = (char)tolower(ch);
@@ -318,6 +341,7 @@ extern "C" void _NN(dump, conf)(nn_def *conf, FILE *fp) {
         if (conf->parallel == NN_PARALLEL_TP) _OUT(fp, "[parallel] tp\n");
     }
     if (conf->shuffle == NN_SHUFFLE_EPOCH) _OUT(fp, "[shuffle] epoch\n");
+    if (conf->validate) _OUT(fp, "[validate] %u\n", conf->validate);
     if (conf->lr > 0) _OUT(fp, "[lr] %.17g\n", conf->lr);
     if (conf->momentum >= 0) _OUT(fp, "[momentum] %.17g\n", conf->momentum);
 }
@@ -520,6 +544,28 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
             n = (UINT)src.load(order, k->n_inputs, k->n_outputs, _NN(return, omp_threads)(), X, T);
         }
         if (n == 0) return FALSE;
+        /* [validate] N: the held-out set of [test_dir] (directory or pack file), in name order */
+        std::vector<DOUBLE> Xv, Tv;
+        UINT nv = 0;
+        free(conf->validation);
+        conf->validation = NULL;
+        conf->n_validation = 0;
+        if (conf->validate) {
+            HpnnSamples vsrc;
+            if (!conf->tests || !vsrc.open(conf->tests)) {
+                NN_ERROR(stderr, "[validate] needs a [test_dir] that can be opened: %s\n",
+                         conf->tests ? conf->tests : "(not set)");
+                return FALSE;
+            }
+            std::vector<UINT> vorder(vsrc.size());
+            for (UINT i = 0; i < (UINT)vorder.size(); i++) vorder[i] = i;
+            HpnnTraceRange tl("load_validation_samples");
+            nv = (UINT)vsrc.load(vorder, k->n_inputs, k->n_outputs, _NN(return, omp_threads)(), Xv, Tv);
+            if (nv == 0) {
+                NN_ERROR(stderr, "[validate]: no usable sample in [test_dir] %s\n", conf->tests);
+                return FALSE;
+            }
+        }
         hpnn_batched_opts o;
         memset(&o, 0, sizeof(o));
         o.type = conf->type;
@@ -533,6 +579,10 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
         o.resume = conf->resume && k->dw != NULL;
         o.epoch0 = conf->epochs_done;
         o.shuffle = conf->shuffle == NN_SHUFFLE_EPOCH ? 1 : 0;
+        o.validate = conf->validate;
+        o.Xv = nv ? Xv.data() : NULL;
+        o.Tv = nv ? Tv.data() : NULL;
+        o.nv = nv;
         UINT ng = 1;
         _NN(get, n_gpu)(&ng);
         o.n_gpu = ng ? ng : 1;
@@ -555,6 +605,15 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
         NN_OUT(stdout, "BATCHED TRAINING: %llu samples in %.6f s (%.1f samples/s) loss=%.10f acc=%u/%u\n",
                (unsigned long long)st.samples, st.seconds, st.seconds > 0 ? st.samples / st.seconds : 0.0,
                st.epoch_loss, st.correct, n);
+        for (UINT i = 0; ok && i < st.n_val; i++)
+            NN_OUT(stdout, "VALIDATION: epoch %u loss=%.10f acc=%u/%u\n", st.val[i].epoch, st.val[i].loss,
+                   st.val[i].correct, st.val[i].n);
+        if (ok) {
+            conf->validation = st.val;
+            conf->n_validation = st.n_val;
+        } else {
+            free(st.val);
+        }
         if (hpnn_metrics_active()) {
             char buf[384];
             snprintf(buf, sizeof buf,
@@ -568,6 +627,11 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
     }
 
     /* online (reference) mode */
+    if (conf->validate) {
+        static bool warned_v = false; /* no epochs here to validate between */
+        if (!warned_v) NN_WARN(stderr, "[validate] has no effect in online mode (ignored)\n");
+        warned_v = true;
+    }
     if (conf->shuffle == NN_SHUFFLE_EPOCH) {
         static bool warned = false; /* no epochs here: every sample is trained to convergence once */
         if (!warned) NN_WARN(stderr, "[shuffle] epoch has no effect in online mode (ignored)\n");

@@ -181,6 +181,14 @@ extern "C" void hpnn_metrics_epoch(const char *engine, UINT epoch, double loss, 
     hpnn_metrics_emit("epoch", buf);
 }
 
+extern "C" void hpnn_metrics_validation(const char *engine, UINT epoch, double loss, UINT correct, UINT n) {
+    if (!hpnn_metrics_active()) return;
+    char buf[256];
+    snprintf(buf, sizeof buf, "\"engine\": \"%s\", \"epoch\": %u, \"loss\": %.10g, \"correct\": %u, \"n\": %u, "
+             "\"accuracy\": %.6f", engine, epoch, loss, correct, n, n ? (double)correct / n : 0.0);
+    hpnn_metrics_emit("validation", buf);
+}
+
 /* ---------------------------------------------------------------- debug */
 extern "C" int hpnn_debug_enabled(void) {
     if (g_debug < 0) {

@@ -17,6 +17,7 @@
 #include <libhpnn/observe.h>
 #include <libhpnn/shuffle.h>
 #include <math.h>
+#include <stdlib.h>
 #include <string.h>
 #include <chrono>
 #include <vector>
@@ -138,6 +139,41 @@ extern "C" DOUBLE hpnn_cpu_batched_step(kernel_ann *k, nn_type type, const DOUBL
     return s * inv_b;
 }
 
+extern "C" UINT hpnn_validation_schedule(UINT epoch0, UINT epochs, UINT validate, UINT *out) {
+    UINT c = 0;
+    if (!validate) return 0;
+    for (UINT e = 0; e < epochs; e++) {
+        const UINT a = epoch0 + e + 1;
+        if (a % validate && e + 1 != epochs) continue;
+        if (out) out[c] = a;
+        c++;
+    }
+    return c;
+}
+
+/* [validate]: forward only over the held-out set with the current weights (FP64; the oracle of
+ * the GPU engines' validation pass): mean loss per sample and argmax hits (first maximum) */
+static void cpu_validate(kernel_ann *k, nn_type type, const DOUBLE *X, const DOUBLE *T, UINT n,
+                         hpnn_validation_record *r) {
+    DOUBLE sum = 0.0;
+    UINT hits = 0;
+    for (UINT s = 0; s < n; s++) {
+        memcpy(k->in, X + (size_t)s * k->n_inputs, sizeof(DOUBLE) * k->n_inputs);
+        hpnn_cpu_forward(k, type);
+        const DOUBLE *t = T + (size_t)s * k->n_outputs;
+        sum += hpnn_cpu_error(k, type, t);
+        UINT g = 0, tr = 0;
+        for (UINT i = 1; i < k->n_outputs; i++) {
+            if (k->output.vec[i] > k->output.vec[g]) g = i;
+            if (t[i] > t[tr]) tr = i;
+        }
+        hits += (g == tr);
+    }
+    r->loss = sum / (DOUBLE)n;
+    r->correct = hits;
+    r->n = n;
+}
+
 extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n,
                                        const hpnn_batched_opts *o, hpnn_batched_stats *st) {
     if (!k || n == 0) return FALSE;
@@ -161,6 +197,8 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
         perm.resize(n);
     }
     const DOUBLE *Xe = shuffle ? Xs.data() : X, *Te = shuffle ? Ts.data() : T;
+    const bool validate = o->validate && o->Xv && o->Tv && o->nv;
+    std::vector<hpnn_validation_record> val;
     auto t0 = std::chrono::steady_clock::now();
     UINT64 samples = 0;
     DOUBLE last = 0.0;
@@ -186,6 +224,13 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
         if (hpnn_metrics_active())
             hpnn_metrics_epoch("cpu", o->epoch0 + e + 1, acc / (nb ? nb : 1), hits, n,
                                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), samples);
+        if (validate && ((o->epoch0 + e + 1) % o->validate == 0 || e + 1 == o->epochs)) {
+            hpnn_validation_record r;
+            r.epoch = o->epoch0 + e + 1;
+            cpu_validate(k, o->type, o->Xv, o->Tv, o->nv, &r);
+            hpnn_metrics_validation("cpu", r.epoch, r.loss, r.correct, r.n);
+            val.push_back(r);
+        }
     }
     auto t1 = std::chrono::steady_clock::now();
     if (st) {
@@ -206,6 +251,13 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
             correct += (g == tr);
         }
         st->correct = correct;
+        st->val = NULL;
+        st->n_val = (UINT)val.size();
+        if (!val.empty()) {
+            st->val = (hpnn_validation_record *)malloc(val.size() * sizeof(val[0]));
+            if (!st->val) return FALSE;
+            memcpy(st->val, val.data(), val.size() * sizeof(val[0]));
+        }
     }
     /* the momentum stays in k->dw: nn_dump_state saves it for an exact resume */
     return TRUE;

@@ -173,6 +173,7 @@ int BPlan::configure(const int *sizes, int n_layers, int net_type, int batch_siz
     add("Z", -1, BD_F32, {Bp, Np[L - 1]}, false);
     add("stats", -1, BD_F32, {HPNN_STAT_SLOTS, HPNN_STAT_STRIDE}, true);
     add("lab0", -1, BD_I32, {Bp}, true);
+    add("vstats", -1, BD_F32, {HPNN_STAT_SLOTS, HPNN_STAT_STRIDE}, true); /* evaluate(): validation statistics */
     if (mode == 't' || mode == 'x' || mode == 'm') {
         add("midslab", -1, BD_F32, {mid_grid, slab_f}, false);
         add("midtmp", -1, BD_F32, {16, slab_f}, false);
@@ -211,6 +212,7 @@ void BPlan::name_pointers() {
     gflat = (float *)buf("gflat");
     Z = (float *)buf("Z");
     stats = (float *)buf("stats");
+    vstats = (float *)buf("vstats");
     lab0 = (int *)buf("lab0");
     midslab = (float *)buf("midslab");
     midtmp = (float *)buf("midtmp");
@@ -277,9 +279,10 @@ int BPlan::forward(const void *X, hipStream_t s) {
 }
 
 int BPlan::output(const int *labels, const float *T, int ldt, int n_valid, float *O, int ldo, bool with_stats,
-                  hipStream_t s) {
+                  hipStream_t s, float *slots) {
+    float *st = slots ? slots : stats;
     return hpnn_output_delta(Z, Np[L - 1], T, ldt, labels, 1.f, type == 2 ? 0.f : -1.f, D[L - 1], Np[L - 1], O, ldo,
-                             with_stats ? stats : nullptr, with_stats ? (unsigned int *)(stats + 1) : nullptr, Bp,
+                             with_stats ? st : nullptr, with_stats ? (unsigned int *)(st + 1) : nullptr, Bp,
                              n_valid, n_out, type, s);
 }
 
@@ -657,6 +660,24 @@ int BPlan::update_flat(const float *G, float lr, float alpha, float scale, hipSt
     for (int l = 0; l < L; l++)
         u[l] = {W32[l], V32[l], G + goff[l], 0, Wb[l], Wt[l], l == 0 ? W0f : nullptr, 1, Np[l], Kp[l]};
     return hpnn_sgd_update_multi(u, L, lr, alpha, scale, momentum ? 1 : 0, s);
+}
+
+int BPlan::evaluate(const XIn &x, const int *labels, const float *T, int ldt, int n_valid, float *slots, int *guess,
+                    hipStream_t s) {
+    if (!slots || n_valid < 1 || (!labels && !T)) return -1;
+    if (mode == 't' && eval_fused && !x.rowmajor) {
+        const int rows = pad_to(n_valid, TILE_T);
+        const int r = hpnn_mlp3_eval(x.x, x.u8, x.u8 ? x.scale : 1.f, Kp[0], W0f, Wb[1], Wb[2], labels, T, ldt, 1.f,
+                                     type == 2 ? 0.f : -1.f, slots, (unsigned int *)(slots + 1), guess, rows, n_valid,
+                                     n_out, type, 0, s);
+        return r > 0 ? 0 : (r ? r : -1);
+    }
+    /* per-layer: row-major BF16 rows (mode 't' plans train on fragment-major input only) */
+    if ((mode == 't' && !x.rowmajor) || n_valid > Bp) return -2;
+    int r = forward(x.x, s);
+    if (!r) r = output(labels, T, ldt, n_valid, nullptr, 0, true, s, slots);
+    if (!r && guess) r = hpnn_argmax_rows(Z, Np[L - 1], n_out, Bp, n_valid, guess, s);
+    return r;
 }
 
 int BPlan::predict(const void *X, int n_valid, float *O, int ldo, hipStream_t s) {

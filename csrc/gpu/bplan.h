@@ -60,6 +60,9 @@ struct XIn {
     const void *xg = nullptr;
     int u8 = 0;
     float scale = 1.f;
+    /* evaluate() only: x is row-major BF16 [rows][Kp0] whatever the plan's layout (the
+     * per-layer path of a mode 't' plan) */
+    int rowmajor = 0;
 };
 
 /* gradient ready for exchange: layers lo..hi (contiguous in gflat) are final */
@@ -119,7 +122,7 @@ class BPlan {
     /* per-layer building blocks */
     int forward(const void *X, hipStream_t s); /* row-major BF16 input -> H[], Z */
     int output(const int *labels, const float *T, int ldt, int n_valid, float *O, int ldo, bool stats,
-               hipStream_t s);
+               hipStream_t s, float *slots = nullptr); /* slots: the statistics go there, not to stats */
     int backward_layer(int l, hipStream_t s);                                 /* D[l-1] from D[l] */
     int grad_layer(int l, const XIn &x, bool reduce, hipStream_t s);         /* slab[l] / G[l] */
     int update_layer(int l, float lr, float alpha, float scale, bool from_g, hipStream_t s);
@@ -156,6 +159,19 @@ class BPlan {
     int update_flat(const float *G, float lr, float alpha, float scale, hipStream_t s);
     /* layer l's weight gradient and step run as ONE 8-phase TN launch */
     bool tn_update_ok(int l) const;
+    /* forward only (validation): loss and argmax hits of the first n_valid rows of x added
+     * into the caller's 64 stat slots (vstats, or any buffer of that layout); guess (may be
+     * null): int32 per row, the lowest index of the largest output, -1 from n_valid up.
+     * Mode 't' with a fragment-major x: one hpnn_mlp3_eval launch over n_valid rows padded to
+     * 256 (any number of tiles; guess holds that many); every other input: forward() + the
+     * output kernel on one chunk, n_valid <= Bp (guess holds Bp).  Changes nothing a training
+     * step reads later: H, Z and D[L-1] are scratch the next step rewrites.  eval_fused
+     * (HPNN_EVAL_FUSED=0: off) selects the per-layer path in mode 't' too; x must then be
+     * row-major (x.rowmajor).  -2 when the input's layout does not fit the path. */
+    int evaluate(const XIn &x, const int *labels, const float *T, int ldt, int n_valid, float *slots, int *guess,
+                 hipStream_t s);
+    bool eval_fused = [] { const char *e = getenv("HPNN_EVAL_FUSED"); return !(e && e[0] == '0'); }();
+    bool eval_is_fused() const { return mode == 't' && eval_fused; }
     /* network outputs O [Bp][ldo] FP32 of a row-major BF16 batch */
     int predict(const void *X, int n_valid, float *O, int ldo, hipStream_t s);
     /* 0, or -9 when an in-kernel hand-over (wide front partials, fused G0 splits) timed out
@@ -174,7 +190,7 @@ class BPlan {
     /* named pointers (valid after allocate / bind) */
     float *W32[16] = {0}, *V32[16] = {0}, *slab[16] = {0};
     void *Wb[16] = {0}, *Wt[16] = {0}, *H[16] = {0}, *D[16] = {0};
-    float *Z = nullptr, *stats = nullptr, *gflat = nullptr, *midslab = nullptr, *midtmp = nullptr;
+    float *Z = nullptr, *stats = nullptr, *vstats = nullptr, *gflat = nullptr, *midslab = nullptr, *midtmp = nullptr;
     void *W0f = nullptr;
     float *wpbuf = nullptr;
     unsigned int *wwords = nullptr, *g0cnt = nullptr, *tncnt = nullptr;

@@ -53,7 +53,23 @@ typedef struct {
     UINT tp;          /* 1: row-sharded tensor parallelism ([parallel] tp; f64 / f32 / bf16) */
     UINT shuffle;     /* 1: a new sample order every epoch (<libhpnn/shuffle.h>, epoch = epoch0 + e;
                        * single-device engines only); 0: the order drawn once */
+    /* [validate] N: the held-out set (host, row-major FP64, nv x n_in / nv x n_out), evaluated
+     * forward-only after every epoch whose absolute number epoch0 + e + 1 is a multiple of
+     * validate and after the last epoch of the call; validate = 0: off (single-device engines) */
+    const DOUBLE *Xv;
+    const DOUBLE *Tv;
+    UINT nv;
+    UINT validate;
 } hpnn_batched_opts;
+
+/* one validation pass: the absolute epoch it followed, the mean loss per sample and the argmax
+ * hits over the n held-out samples */
+typedef struct {
+    UINT epoch;
+    DOUBLE loss;
+    UINT correct;
+    UINT n;
+} hpnn_validation_record;
 
 typedef struct {
     DOUBLE last_loss;   /* mean loss of the last minibatch            */
@@ -61,7 +77,14 @@ typedef struct {
     UINT64 samples;     /* samples processed                          */
     DOUBLE seconds;     /* wall time spent in the training loop       */
     UINT correct;       /* argmax hits in the last epoch              */
+    /* [validate]: n_val records in epoch order, malloc'ed by the engine (the caller frees val) */
+    hpnn_validation_record *val;
+    UINT n_val;
 } hpnn_batched_stats;
+
+/* the epochs (absolute numbers, ascending) a call of `epochs` epochs after `epoch0` completed
+ * ones validates at; out may be NULL; returns the count */
+UINT hpnn_validation_schedule(UINT epoch0, UINT epochs, UINT validate, UINT *out);
 
 /* X: n x n_in, T: n x n_out (host, row-major FP64). Weights are read from
  * and written back to the host kernel; with BPM the final momentum is written to

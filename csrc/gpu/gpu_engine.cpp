@@ -758,6 +758,36 @@ struct Batched {
         if (hpnn_gather_rows(xs.x, cn.x, perm, n, rows_p, (long)Kp0 * 2, s)) return FALSE;
         return !xs.xg || hpnn_gather_fm(xs.xg, cn.xg, perm, n, rows_p, Kp0, 1, s) == 0;
     }
+    /* [validate]: the held-out set as BPlan::evaluate reads it -- the plan's fragment-major
+     * layout padded to whole 256-row tiles on the tile path (one launch over the set), else
+     * row-major BF16 padded to whole Bp-row chunks (forward + output kernel per chunk) */
+    BOOL upload_val(const DOUBLE *src, int rows, int cols, XSet *vs, int *rows_p) {
+        if (p.eval_is_fused()) {
+            *rows_p = pad_rows(rows, 256);
+            return upload_x(src, rows, cols, *rows_p, vs);
+        }
+        *rows_p = pad_rows(rows, p.Bp);
+        vs->row_bytes = (size_t)p.Kp[0] * 2;
+        return upload_bf16(src, rows, cols, *rows_p, p.Kp[0], &vs->x, s);
+    }
+    float *vacc() { return p.vstats; }
+    BOOL evaluate(const XSet &vs, const float *T, int ldt, int nv) {
+        int r = 0;
+        if (p.eval_is_fused()) {
+            r = p.evaluate(at(vs, 0), vs.lab, vs.lab ? nullptr : T, ldt, nv, p.vstats, nullptr, s);
+        } else {
+            for (long row = 0; row < nv && !r; row += p.Bp) {
+                hpnn::XIn v;
+                v.x = (const char *)vs.x + row * vs.row_bytes;
+                v.rowmajor = 1;
+                const int *lb = vs.lab ? vs.lab + row : nullptr;
+                r = p.evaluate(v, lb, lb ? nullptr : T + (size_t)row * ldt, ldt, std::min((long)p.Bp, nv - row),
+                               p.vstats, nullptr, s);
+            }
+        }
+        if (r) NN_ERROR(stderr, "batched validation pass failed: %d\n", r);
+        return r == 0;
+    }
     hpnn::XIn at(const XSet &xs, long row) const {
         hpnn::XIn v;
         v.x = (const char *)xs.x + row * xs.row_bytes;
@@ -974,6 +1004,28 @@ struct BatchedFP {
     static int reduce_sum(grad_t *buf, int G, size_t count, hipStream_t st) {
         return hpnn_reduce_fp(F64, buf, buf, G, (long)count, (long)count, st);
     }
+    /* [validate]: the held-out rows as they are (the kernels take any shape) and stat slots of
+     * the pass's own; forward + the output kernel without a delta, in chunks of Bp rows */
+    float *vslots = nullptr;
+    BOOL upload_val(const DOUBLE *src, int rows, int cols, XSet *vs, int *rows_p) {
+        *rows_p = rows;
+        if (!vslots) {
+            HIPCHK(hpnn_dev_malloc(&vslots, ACC_BYTES));
+            HIPCHK(hipMemsetAsync(vslots, 0, ACC_BYTES, s));
+        }
+        return upload_x(src, rows, cols, rows, vs);
+    }
+    float *vacc() { return vslots; }
+    BOOL evaluate(const XSet &vs, const T *Tt, int ldt, int nv) {
+        for (long row = 0; row < nv; row += Bp) {
+            const int rows = (int)std::min((long)Bp, nv - row);
+            if (!forward(at(vs, row), rows)) return FALSE;
+            if (hpnn_output_fp_eval(F64, Z, N[L - 1], Tt + (size_t)row * ldt, ldt, nullptr, vslots, rows, rows, n_out,
+                                    type, s))
+                return FALSE;
+        }
+        return TRUE;
+    }
 
     ~BatchedFP() {
         if (s) hipStreamSynchronize(s);
@@ -987,6 +1039,7 @@ struct BatchedFP {
         }
         hpnn_dev_free(Z);
         hpnn_dev_free(acc);
+        hpnn_dev_free(vslots);
         if (own_flat) hpnn_dev_free(gflat);
     }
 
@@ -1379,6 +1432,39 @@ BOOL train_single(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, const
         if (xs.lab && hpnn_gather_rows(xs.lab, cn.lab, perm, (int)n, rows_p, 4, s)) return false;
         return !dense || hpnn_gather_rows(Td, Tc, perm, (int)n, rows_p, (long)k->n_outputs * sizeof(TT), s) == 0;
     };
+    /* [validate] N: the held-out set, uploaded once; a pass = the evaluation launches into the
+     * validation stat slots plus the one-workgroup commit that files them as the next record
+     * of a device history -- all on the compute stream, so inside the captured replay; the host
+     * reads the history once after the last replay (per record with per-epoch metrics) */
+    const bool validate = o->validate && o->Xv && o->Tv && o->nv;
+    const int nval = validate ? (int)o->nv : 0;
+    XSet vs;
+    TT *Tvd = nullptr;
+    hpnn_val_record *vhist = nullptr;
+    unsigned int *vcur = nullptr;
+    std::vector<UINT> vsched;
+    if (validate) {
+        vsched.resize(hpnn_validation_schedule(o->epoch0, o->epochs, o->validate, nullptr));
+        hpnn_validation_schedule(o->epoch0, o->epochs, o->validate, vsched.data());
+        int vrows = 0;
+        if (!net.upload_val(o->Xv, nval, (int)k->n_inputs, &vs, &vrows)) return FALSE;
+        if (!attach_labels(&vs, o->Tv, o->nv, (int)k->n_outputs, vrows, o->type, s)) return FALSE;
+        std::vector<TT> tf((size_t)vrows * k->n_outputs, (TT)0);
+        for (size_t i = 0; i < (size_t)nval * k->n_outputs; i++) tf[i] = (TT)o->Tv[i];
+        HIPCHK(hpnn_dev_malloc(&Tvd, tf.size() * sizeof(TT)));
+        HIPCHK(hipMemcpy(Tvd, tf.data(), tf.size() * sizeof(TT), hipMemcpyHostToDevice));
+        HIPCHK(hpnn_dev_malloc(&vhist, (vsched.size() + 1) * sizeof(hpnn_val_record)));
+        HIPCHK(hpnn_dev_malloc(&vcur, sizeof(unsigned int)));
+        HIPCHK(hipMemset(vcur, 0, sizeof(unsigned int)));
+        NN_OUT(stdout, "batched GPU training: %d held-out samples validated every %u epochs\n", nval, o->validate);
+    }
+    auto validation = [&]() -> bool {
+        if (net.evaluate(vs, Tvd, (int)k->n_outputs, nval) &&
+            hpnn_validate_commit(net.vacc(), vhist, vcur, (unsigned int)vsched.size(), s) == 0)
+            return true;
+        NN_ERROR(stderr, "batched GPU training: the validation pass could not be launched\n");
+        return false;
+    };
     auto epoch = [&]() -> bool {
         if (shuffle && !reshuffle()) {
             NN_ERROR(stderr, "batched GPU training: the epoch reshuffle could not be launched\n");
@@ -1392,26 +1478,45 @@ BOOL train_single(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, const
         }
         return true;
     };
-    /* ne epochs back to back; the statistics are zeroed before the last (the only one read) */
-    auto epochs = [&](int ne) -> bool {
-        for (int i = 0; i < ne; i++)
+    const bool metrics = hpnn_metrics_active() != 0;
+    const int E = (int)o->epochs;
+    /* epoch e of this call (0-based) is followed by a validation pass; with per-epoch metrics
+     * the pass runs eagerly behind the epoch's replay (that loop synchronises every epoch anyway) */
+    auto val_due = [&](int e) { return validate && ((o->epoch0 + e + 1) % o->validate == 0 || e + 1 == E); };
+    /* ne epochs from epoch e0 of the call, back to back; the statistics are zeroed before the
+     * last (the only one read) */
+    auto epochs = [&](int ne, int e0) -> bool {
+        for (int i = 0; i < ne; i++) {
             if ((i + 1 == ne && hipMemsetAsync(net.acc, 0, Net::ACC_BYTES, s) != hipSuccess) || !epoch()) return false;
+            if (!metrics && val_due(e0 + i) && !validation()) return false;
+        }
         return true;
     };
     /* one graph replays epg epochs (about 32 steps: the host launches once per replay); with
-     * per-epoch metrics every epoch is its own replay followed by a statistics read */
-    const bool metrics = hpnn_metrics_active() != 0;
-    const int E = (int)o->epochs;
-    const int epg = metrics ? 1 : std::max(1, std::min(E, 32 / std::max(1, n_batches)));
+     * per-epoch metrics every epoch is its own replay followed by a statistics read.  With
+     * [validate] N the replay is a whole number of validation periods where that fits a graph,
+     * so every replay has the same pattern of passes; a graph is keyed by its epochs and the
+     * offsets of its passes (the last replay, shorter or with the closing pass, is another key) */
+    int epg = metrics ? 1 : std::max(1, std::min(E, 32 / std::max(1, n_batches)));
+    if (validate && !metrics && (long)o->validate * n_batches <= 4096)
+        epg = std::min(E, (int)((epg + o->validate - 1) / o->validate * o->validate));
+    auto gkey = [&](int ne, int e0) {
+        std::vector<int> key{ne};
+        for (int i = 0; i < ne && !metrics; i++)
+            if (val_due(e0 + i)) key.push_back(i);
+        return key;
+    };
     hpnn_preload_code_objects();
-    std::map<int, hipGraphExec_t> graphs;
+    std::map<std::vector<int>, hipGraphExec_t> graphs;
     if (graphs_enabled() && n_batches <= 4096)
-        for (int ne : {epg, E % epg}) {
-            if (ne <= 0 || graphs.count(ne)) continue;
+        for (int e0 = 0; e0 < E; e0 += epg) {
+            const int ne = std::min(epg, E - e0);
+            const std::vector<int> key = gkey(ne, e0);
+            if (graphs.count(key)) continue;
             hipGraphExec_t x = nullptr;
-            if (!capture_epoch(s, [&]() { return epochs(ne); }, &x))
+            if (!capture_epoch(s, [&]() { return epochs(ne, e0); }, &x))
                 NN_DBG(stdout, "batched GPU training: epochs not capturable, eager launches\n");
-            graphs[ne] = x;
+            graphs[key] = x;
         }
     /* setup (data upload and layout conversions) is finished before the clock starts */
     HIPCHK(hipDeviceSynchronize());
@@ -1435,10 +1540,12 @@ BOOL train_single(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, const
         NN_ERROR(stderr, "batched GPU training: the epoch permutation did not terminate within its bound; stopping\n");
         return false;
     };
+    std::vector<hpnn_val_record> vrec(vsched.size());
+    size_t vdone = 0;
     for (int e = 0; e < E && ok;) {
         const int ne = std::min(epg, E - e);
-        auto g = graphs.find(ne);
-        ok = (g != graphs.end() && g->second) ? hipGraphLaunch(g->second, s) == hipSuccess : epochs(ne);
+        auto g = graphs.find(gkey(ne, e));
+        ok = (g != graphs.end() && g->second) ? hipGraphLaunch(g->second, s) == hipSuccess : epochs(ne, e);
         e += ne;
         if (ok) {
             unsigned int *d = hw + 4 * slot;
@@ -1459,9 +1566,29 @@ BOOL train_single(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, const
             hpnn_metrics_epoch("gpu", o->epoch0 + e, ep_loss / (double)n, ep_hits, n,
                                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(),
                                (UINT64)n * e);
+        if (ok && metrics && val_due(e - 1) && vdone < vrec.size()) {
+            ok = validation() && hipMemcpyAsync(&vrec[vdone], vhist + vdone, sizeof(hpnn_val_record),
+                                                hipMemcpyDeviceToHost, s) == hipSuccess &&
+                 hipStreamSynchronize(s) == hipSuccess;
+            if (ok)
+                hpnn_metrics_validation("gpu", o->epoch0 + e, vrec[vdone].loss_sum / (double)nval, vrec[vdone].hits,
+                                        (UINT)nval);
+            vdone++;
+        }
     }
     if (ok && pend >= 0) ok = judge(pend);
     auto t1 = std::chrono::steady_clock::now();
+    if (ok && validate && !metrics) {
+        /* the whole history, once; the cursor tells how many passes were filed */
+        unsigned int filed = 0;
+        ok = hipMemcpy(&filed, vcur, sizeof filed, hipMemcpyDeviceToHost) == hipSuccess &&
+             hipMemcpy(vrec.data(), vhist, vrec.size() * sizeof(hpnn_val_record), hipMemcpyDeviceToHost) == hipSuccess;
+        if (ok && filed != vrec.size()) {
+            NN_ERROR(stderr, "batched GPU training: %u validation records filed, %zu scheduled\n", filed, vrec.size());
+            ok = FALSE;
+        }
+        vdone = vrec.size();
+    }
     for (hipEvent_t ev : hev)
         if (ev) hipEventDestroy(ev);
     if (hw) hipHostFree(hw);
@@ -1474,7 +1601,23 @@ BOOL train_single(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, const
         st->epoch_loss = ep_loss / (double)n;
         st->correct = ep_hits;
         st->last_loss = st->epoch_loss;
+        st->val = NULL;
+        st->n_val = (UINT)vrec.size();
+        if (!vrec.empty()) {
+            st->val = (hpnn_validation_record *)malloc(vrec.size() * sizeof(hpnn_validation_record));
+            if (!st->val) ok = FALSE;
+            for (size_t i = 0; ok && i < vrec.size(); i++) {
+                st->val[i].epoch = vsched[i];
+                st->val[i].loss = vrec[i].loss_sum / (double)nval;
+                st->val[i].correct = vrec[i].hits;
+                st->val[i].n = (UINT)nval;
+            }
+        }
     }
+    vs.release();
+    hpnn_dev_free(Tvd);
+    hpnn_dev_free(vhist);
+    hpnn_dev_free(vcur);
     xs.release();
     cn.release();
     hpnn_dev_free(Td);
@@ -1498,6 +1641,10 @@ BOOL train_dp(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, const hpn
     if (k->n_hiddens + 1 > 16 || G < 1) return FALSE;
     if (o->shuffle) {
         NN_ERROR(stderr, "[shuffle] epoch is not supported by data-parallel batched training (one device only)\n");
+        return FALSE;
+    }
+    if (o->validate) {
+        NN_ERROR(stderr, "[validate] is not supported by data-parallel batched training (one device only)\n");
         return FALSE;
     }
     if (!loopback && !hpnn_comm_available()) return FALSE;
@@ -1739,6 +1886,10 @@ BOOL train_dp_mp(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, const 
     if (k->n_hiddens + 1 > 16 || W < 1 || W > 64) return FALSE;
     if (o->shuffle) {
         NN_ERROR(stderr, "[shuffle] epoch is not supported by data-parallel batched training (one device only)\n");
+        return FALSE;
+    }
+    if (o->validate) {
+        NN_ERROR(stderr, "[validate] is not supported by data-parallel batched training (one device only)\n");
         return FALSE;
     }
     hpnn_gpu_sync_host(k);

@@ -318,6 +318,28 @@ int hpnn_mlp3_tile(const void *Xg, int xu8, float xscale, int K0, const void *W0
                    float *gslab, float *loss_acc, unsigned int *correct, int Bp, int n_valid, int n_out, int type,
                    int grid, hipStream_t stream);
 int hpnn_mlp3_tile_grid(int Bp, int grid);
+/* forward-only form of hpnn_mlp3_tile (validation): the same input, W0f / W1 / W2, rounding
+ * points and summation order, so a batch's loss and hits are the numbers the training front
+ * reports for it; added into the caller's stat slots (HPNN_STAT_SLOTS layout).  guess (may be
+ * NULL) [Bp] int32: the lowest index of the largest logit, -1 for rows >= n_valid.  No delta,
+ * no slab, no W2t.  Same shapes, alignment checks and return values as hpnn_mlp3_tile. */
+int hpnn_mlp3_eval(const void *Xg, int xu8, float xscale, int K0, const void *W0f, const void *W1, const void *W2,
+                   const int *labels, const float *T, int ldt, float t_hi, float t_lo, float *loss_acc,
+                   unsigned int *correct, int *guess, int Bp, int n_valid, int n_out, int type, int grid,
+                   hipStream_t stream);
+/* commit one validation pass (kernels_validate.hip), one workgroup, capturable: the 64 stat
+ * slots summed in slot order (float loss at [0] plus the double at floats 2..3 the FP engines'
+ * hpnn_output_fp_eval adds into) -> hist[*cursor] = {double loss_sum, uint hits}, the slots zeroed,
+ * *cursor += 1; a full history (cursor == cap) drops the record and only zeroes the slots */
+typedef struct {
+    double loss_sum;
+    unsigned int hits, pad;
+} hpnn_val_record;
+/* guess[r] = lowest index of the largest of Z[r][0 .. n_out) for r < n_valid, -1 for the rows up
+ * to `rows` (the per-layer evaluation path's guess) */
+int hpnn_argmax_rows(const float *Z, int ldz, int n_out, int rows, int n_valid, int *guess, hipStream_t stream);
+int hpnn_validate_commit(float *slots, hpnn_val_record *hist, unsigned int *cursor, unsigned int cap,
+                         hipStream_t stream);
 /* profiling (HPNN_TILE_TRACE=1): per-workgroup s_memtime stamps [1024][12] */
 int hpnn_mlp3_tile_trace(unsigned long long *out);
 /* HPNN_G0_TRACE=1 phase stamps of the fused G0 launch: out[512][8] */
@@ -363,6 +385,10 @@ int hpnn_gemm_fp_splits(int K, int splits);
 int hpnn_output_fp(int f64, const void *Z, int ldz, const void *T, int ldt, void *D, int ldd, void *O, int ldo,
                    int *guess, float *loss_acc, unsigned int *correct, int B, int n_valid, int n_out, int type,
                    hipStream_t stream);
+/* the same output layer forward only (validation): no delta, no O; hits into slots[.][1], the
+ * loss as a DOUBLE into floats 2..3 of each slot (hpnn_validate_commit adds both forms) */
+int hpnn_output_fp_eval(int f64, const void *Z, int ldz, const void *T, int ldt, int *guess, float *slots, int B,
+                        int n_valid, int n_out, int type, hipStream_t stream);
 /* W += step(scale * sum_s G[s]) (BP / BPM), n elements */
 int hpnn_update_fp(int f64, void *W, void *V, const void *G, int S, long gstride, long n, double lr, double alpha,
                    double scale, int momentum, hipStream_t stream);

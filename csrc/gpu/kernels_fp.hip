@@ -317,7 +317,9 @@ __device__ __forceinline__ T wave_sum_fp(T v) {
 
 /* one wave per sample row; O (optional) receives the network output, guess (optional)
  * the argmax index of the output (the reference's evaluation rule: first maximum) */
-template <typename T>
+/* ACC64 (validation of the FP64 / FP32 engines): the loss is added as a double into the slot's
+ * second 8 bytes (floats 2..3), so an FP64 validation loss keeps the engine's precision */
+template <typename T, bool ACC64 = false>
 __global__ __launch_bounds__(256) void output_fp_kernel(const T *__restrict__ Z, int ldz, const T *__restrict__ Tg,
                                                         int ldt, T *__restrict__ D, int ldd, T *__restrict__ O, int ldo,
                                                         int *__restrict__ guess, float *__restrict__ loss_acc,
@@ -373,7 +375,13 @@ __global__ __launch_bounds__(256) void output_fp_kernel(const T *__restrict__ Z,
         if (guess) guess[row] = io;
         if (valid && Tg) {
             const float l = (float)(type == 2 ? -loss / (T)n_out : (T)0.5 * loss);
-            if (loss_acc) atomicAdd(loss_acc + HPNN_STAT_SLOT(blockIdx.x), l);
+            if constexpr (ACC64) {
+                if (loss_acc)
+                    atomicAdd((double *)(loss_acc + HPNN_STAT_SLOT(blockIdx.x) + 2),
+                              (double)(type == 2 ? -loss / (T)n_out : (T)0.5 * loss));
+            } else {
+                if (loss_acc) atomicAdd(loss_acc + HPNN_STAT_SLOT(blockIdx.x), l);
+            }
             if (correct && io == it) atomicAdd(correct + HPNN_STAT_SLOT(blockIdx.x), 1u);
         }
     }
@@ -490,6 +498,22 @@ extern "C" int hpnn_output_fp(int f64, const void *Z, int ldz, const void *T, in
     else
         hipLaunchKernelGGL(output_fp_kernel<float>, grid, dim3(256), 0, stream, (const float *)Z, ldz,
                            (const float *)T, ldt, (float *)D, ldd, (float *)O, ldo, guess, loss_acc, correct, B,
+                           n_valid, n_out, type);
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+extern "C" int hpnn_output_fp_eval(int f64, const void *Z, int ldz, const void *T, int ldt, int *guess, float *slots,
+                                   int B, int n_valid, int n_out, int type, hipStream_t stream) {
+    if (B <= 0 || n_out < 1 || !slots || !T) return -2;
+    const dim3 grid((B + 3) / 4);
+    unsigned int *hits = (unsigned int *)(slots + 1);
+    if (f64)
+        hipLaunchKernelGGL((output_fp_kernel<double, true>), grid, dim3(256), 0, stream, (const double *)Z, ldz,
+                           (const double *)T, ldt, (double *)nullptr, 0, (double *)nullptr, 0, guess, slots, hits, B,
+                           n_valid, n_out, type);
+    else
+        hipLaunchKernelGGL((output_fp_kernel<float, true>), grid, dim3(256), 0, stream, (const float *)Z, ldz,
+                           (const float *)T, ldt, (float *)nullptr, 0, (float *)nullptr, 0, guess, slots, hits, B,
                            n_valid, n_out, type);
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }

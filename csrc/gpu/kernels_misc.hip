@@ -931,6 +931,7 @@ const void *hpnn_co_probe_ws(void);
 const void *hpnn_co_probe_online(void);
 const void *hpnn_co_probe_xar(void);
 const void *hpnn_co_probe_shuffle(void);
+const void *hpnn_co_probe_validate(void);
 }
 
 extern "C" int hpnn_preload_code_objects(void) {
@@ -944,7 +945,7 @@ extern "C" int hpnn_preload_code_objects(void) {
     const void *probes[] = {hpnn_co_probe_8ph(),  hpnn_co_probe_fp(),   hpnn_co_probe_g0(),    hpnn_co_probe_mfma(),
                             hpnn_co_probe_misc(), hpnn_co_probe_mlp3(), hpnn_co_probe_mlp3t(), hpnn_co_probe_mlp3x(),
                             hpnn_co_probe_wide(), hpnn_co_probe_ws(),   hpnn_co_probe_online(), hpnn_co_probe_xar(),
-                            hpnn_co_probe_shuffle()};
+                            hpnn_co_probe_shuffle(), hpnn_co_probe_validate()};
     /* an empty one-thread launch per unit: the launch is what loads its code object */
     hipStream_t s = nullptr;
     int rc = hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess ? 0 : -1;

@@ -101,7 +101,7 @@ constexpr int TR_BLOCKS = 1024, TR_MARKS = 12;
 __device__ unsigned long long g_tile_trace[TR_BLOCKS][TR_MARKS];
 
 template <int TYPE, bool LABELS, int KS, bool XU8, int D, bool TRACE = false, int ABL = 0, bool EARLY = true,
-          bool TRADE = false, bool XORD = false, int IL = 1, bool CB = false>
+          bool TRADE = false, bool XORD = false, int IL = 1, bool CB = false, bool EVAL = false>
 __global__ __launch_bounds__(512) void mlp3_tile_kernel(const void *__restrict__ Xg, float xscale,
                                                             const __bf16 *__restrict__ W0f,
                                                             const __bf16 *__restrict__ W1,
@@ -112,7 +112,11 @@ __global__ __launch_bounds__(512) void mlp3_tile_kernel(const void *__restrict__
                                                             float t_lo, __bf16 *__restrict__ D1,
                                                             float *__restrict__ gslab, float *__restrict__ loss_acc,
                                                             unsigned int *__restrict__ correct, int n_tiles,
-                                                            int n_valid, int n_out) {
+                                                            int n_valid, int n_out, int *__restrict__ guess) {
+    /* EVAL (hpnn_mlp3_eval): the forward-only form -- phase A, P1 and P2 exactly as in training
+     * (same operands, rounding points and summation order, so the loss and the hits of a batch
+     * are the training front's), then the argmax; no P3 / P4 / phase C, D1, gslab and W2t are
+     * not touched and no delta image is written */
     /* 8 waves (a 16-wave workgroup, 128 VGPRs a wave, measured slower: 65.2 vs 60.2-60.7 us
      * per step, its chain no faster -- the chain is bound by LDS / MFMA throughput, not by
      * per-wave latency).  Phase A on 32 x 128 wave tiles: 64 x 64 (half the B reads, twice
@@ -336,8 +340,10 @@ __global__ __launch_bounds__(512) void mlp3_tile_kernel(const void *__restrict__
 #pragma unroll
             for (int kk = 0; kk < 2; kk++)
                 w2f[ot][kk] = *(const bf16x8 *)(W2 + (size_t)(16 * ot + r16) * H2 + 32 * kk + 8 * q);
+        if constexpr (!EVAL) {
 #pragma unroll
-        for (int ht = 0; ht < 4; ht++) w2tf[ht] = *(const bf16x8 *)(W2t + (size_t)(16 * ht + r16) * NO + 8 * q);
+            for (int ht = 0; ht < 4; ht++) w2tf[ht] = *(const bf16x8 *)(W2t + (size_t)(16 * ht + r16) * NO + 8 * q);
+        }
         int lab[STC];
 #pragma unroll
         for (int st = 0; st < STC; st++) {
@@ -393,14 +399,46 @@ __global__ __launch_bounds__(512) void mlp3_tile_kernel(const void *__restrict__
             if (n_ot > 1) {
                 z[1] = mfma(w2f[1][0], b0, z[1]);
                 z[1] = mfma(w2f[1][1], b1, z[1]);
-                output_layer<TYPE, LABELS, TS, 2>(z, lab[st], T, ldt, t_hi, t_lo, s, s < n_valid, n_out, imgD3, lo,
+                output_layer<TYPE, LABELS, TS, 2, !EVAL>(z, lab[st], T, ldt, t_hi, t_lo, s, s < n_valid, n_out, imgD3, lo,
                                                   r0, lane, inv_nout, my_loss, my_hit);
             } else {
-                output_layer<TYPE, LABELS, TS, 1>(z, lab[st], T, ldt, t_hi, t_lo, s, s < n_valid, n_out, imgD3, lo,
+                output_layer<TYPE, LABELS, TS, 1, !EVAL>(z, lab[st], T, ldt, t_hi, t_lo, s, s < n_valid, n_out, imgD3, lo,
                                                   r0, lane, inv_nout, my_loss, my_hit);
+            }
+            if constexpr (EVAL) {
+                /* the guess: the lowest output index that attains the row maximum.  This lane
+                 * holds outputs 16 ot + 4 q + r of sample r16 in ascending order; then across q */
+                if (guess) {
+                    float bz = -INFINITY;
+                    int bi = 1 << 30;
+#pragma unroll
+                    for (int ot = 0; ot < 2; ot++)
+#pragma unroll
+                        for (int r = 0; r < 4; r++) {
+                            const int c = ot * 16 + 4 * q + r;
+                            if (c < n_out && z[ot][r] > bz) {
+                                bz = z[ot][r];
+                                bi = c;
+                            }
+                        }
+                    {
+                        const float oz = shfl_xor16(bz, lane);
+                        const int oi = shfl_xor16(bi, lane);
+                        if (oz > bz || (oz == bz && oi < bi)) bz = oz, bi = oi;
+                    }
+                    {
+                        const float oz = shfl_xor32(bz, lane);
+                        const int oi = shfl_xor32(bi, lane);
+                        if (oz > bz || (oz == bz && oi < bi)) bz = oz, bi = oi;
+                    }
+                    if (q == 0) guess[s] = s < n_valid ? bi : -1;
+                }
             }
         }
         mark(6);
+        /* forward only: the tile ends here (the next tile's first barrier orders its X^T stage
+         * writes behind this tile's H1 / H2 reads) */
+        if constexpr (EVAL) continue;
         wave_lds_fence();
         /* P3: delta2^T [h2][sample] = (W2^T delta3^T) * f'(H2) */
 #pragma unroll
@@ -545,11 +583,11 @@ int g_tile_cus = 0;
 const int g_tile_abl = [] { const char *e = getenv("HPNN_TILE_ABL"); return e ? atoi(e) : 0; }();
 #endif
 
-template <int TYPE, bool LABELS, int KS, bool XU8>
+template <int TYPE, bool LABELS, int KS, bool XU8, bool EVAL = false>
 int launch_tile(const void *Xg, float xscale, const void *W0f, const void *W1, const void *W2, const void *W2t,
                 const int *labels, const float *T, int ldt, float t_hi, float t_lo, void *D1, float *gslab,
                 float *loss_acc, unsigned int *correct, int n_tiles, int n_valid, int n_out, int grid,
-                hipStream_t stream) {
+                hipStream_t stream, int *guess = nullptr) {
     static const bool trace = [] { const char *e = getenv("HPNN_TILE_TRACE"); return e && e[0] == '1'; }();
     auto go = [&](auto kern, int threads) {
         static bool attr = false;
@@ -559,9 +597,12 @@ int launch_tile(const void *Xg, float xscale, const void *W0f, const void *W1, c
         }
         hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), LDS_TOTAL, stream, Xg, xscale, (const __bf16 *)W0f,
                            (const __bf16 *)W1, (const __bf16 *)W2, (const __bf16 *)W2t, labels, T, ldt, t_hi, t_lo,
-                           (__bf16 *)D1, gslab, loss_acc, correct, n_tiles, n_valid, n_out);
+                           (__bf16 *)D1, gslab, loss_acc, correct, n_tiles, n_valid, n_out, guess);
         return hipGetLastError() == hipSuccess ? grid : -5;
     };
+    /* the forward-only form (hpnn_mlp3_eval): the production schedule, backward phases off */
+    if constexpr (EVAL)
+        return go(mlp3_tile_kernel<TYPE, LABELS, KS, XU8, 3, false, 0, true, false, false, 1, false, true>, 512);
     /* D = 3 k-steps of loads in flight: 58.7-59.4 us per MNIST step vs 59.6-60.4 at D = 4 and
      * 59.8-60.3 at D = 2 (B reads one k-step ahead; a deeper ring costs the registers the B
      * prefetch needs), profiles/r3/SUMMARY.md; re-measured on the round-4 front (253 VGPRs):
@@ -604,14 +645,14 @@ int launch_tile(const void *Xg, float xscale, const void *W0f, const void *W1, c
     return go(mlp3_tile_kernel<TYPE, LABELS, KS, XU8, 3>, 512);
 }
 
-template <int KS>
+template <int KS, bool EVAL = false>
 int launch_tile_k(const void *Xg, int xu8, float xscale, const void *W0f, const void *W1, const void *W2,
                   const void *W2t, const int *labels, const float *T, int ldt, float t_hi, float t_lo, void *D1,
                   float *gslab, float *loss_acc, unsigned int *correct, int n_tiles, int n_valid, int n_out, int type,
-                  int grid, hipStream_t stream) {
+                  int grid, hipStream_t stream, int *guess = nullptr) {
 #define HPNN_TL(TY, LB, U8)                                                                                     \
-    return launch_tile<TY, LB, KS, U8>(Xg, xscale, W0f, W1, W2, W2t, labels, T, ldt, t_hi, t_lo, D1, gslab,     \
-                                       loss_acc, correct, n_tiles, n_valid, n_out, grid, stream)
+    return launch_tile<TY, LB, KS, U8, EVAL>(Xg, xscale, W0f, W1, W2, W2t, labels, T, ldt, t_hi, t_lo, D1,      \
+                                             gslab, loss_acc, correct, n_tiles, n_valid, n_out, grid, stream, guess)
 #define HPNN_TL2(TY, LB)       \
     if (xu8) HPNN_TL(TY, LB, true); \
     HPNN_TL(TY, LB, false)
@@ -659,6 +700,31 @@ extern "C" int hpnn_mlp3_tile(const void *Xg, int xu8, float xscale, int K0, con
     if (K0 == K_)                                                                                                \
     return launch_tile_k<K_ / 32>(Xg, xu8, xscale, W0f, W1, W2, W2t, labels, T, ldt, t_hi, t_lo, D1, gslab,     \
                                   loss_acc, correct, n_tiles, n_valid, n_out, type, grid, stream)
+    HPNN_TK(800);
+    HPNN_TK(256);
+#undef HPNN_TK
+    return -3;
+}
+
+/* Forward-only evaluation of Bp rows (kernel comment, EVAL): loss and argmax hits of the rows
+ * below n_valid added into the caller's stat slots, guess[Bp] (may be NULL) = the lowest index
+ * of the largest logit, -1 from n_valid up.  Reads what hpnn_mlp3_tile reads except W2t; writes
+ * nothing but the slots and guess.  No workgroup waits for another. */
+extern "C" int hpnn_mlp3_eval(const void *Xg, int xu8, float xscale, int K0, const void *W0f, const void *W1,
+                              const void *W2, const int *labels, const float *T, int ldt, float t_hi, float t_lo,
+                              float *loss_acc, unsigned int *correct, int *guess, int Bp, int n_valid, int n_out,
+                              int type, int grid, hipStream_t stream) {
+    if (Bp <= 0 || Bp % TS || n_out > NO || n_out < 1 || n_valid < 0 || n_valid > Bp) return -2;
+    if (!labels && !T) return -1;
+    if (((uintptr_t)Xg | (uintptr_t)W0f | (uintptr_t)W1 | (uintptr_t)W2) & 15) return -4;
+    grid = hpnn_mlp3_tile_grid(Bp, grid);
+    if (grid <= 0) return -2;
+    const int n_tiles = Bp / TS;
+#define HPNN_TK(K_)                                                                                              \
+    if (K0 == K_)                                                                                                \
+    return launch_tile_k<K_ / 32, true>(Xg, xu8, xscale, W0f, W1, W2, nullptr, labels, T, ldt, t_hi, t_lo,      \
+                                        nullptr, nullptr, loss_acc, correct, n_tiles, n_valid, n_out, type,     \
+                                        grid, stream, guess)
     HPNN_TK(800);
     HPNN_TK(256);
 #undef HPNN_TK

@@ -105,7 +105,7 @@ __device__ __forceinline__ bf16x4 ld_d4(const char *img, const LaneOff &lo, int 
  * SNN: reference e^{z-1}/(TINY + sum e^{z-1}) evaluated in the max-shifted form. */
 /* Hot path of output_layer: SNN, one-hot labels with t_lo == 0: no per-output
  * logarithms or branches -- one log per lane (the label's output), loss -log(o_lab+TINY)/N */
-template <int R, int NOT>
+template <int R, int NOT, bool STORE = true>
 __device__ __forceinline__ void output_snn_onehot(const f32x4 (&z)[2], int lab, float t_hi, bool valid, int n_out,
                                                   char *imgD3, const LaneOff &lo, int r0, int lane, float inv_nout,
                                                   float &my_loss, unsigned int &my_hit) {
@@ -142,7 +142,7 @@ __device__ __forceinline__ void output_snn_onehot(const f32x4 (&z)[2], int lab, 
                 dv[r] = (__bf16)(((is_lab ? t_hi : 0.f) - o) * vm);
             }
         }
-        *(bf16x4 *)wr_ptr<R>(imgD3, lo, r0, ot * 16) = dv;
+        if constexpr (STORE) *(bf16x4 *)wr_ptr<R>(imgD3, lo, r0, ot * 16) = dv;
     }
     /* lanes that do not hold the label contribute 0 */
     float l = (z_lab > -INFINITY && valid) ? t_hi * __logf(o_lab + TINY) : 0.f;
@@ -154,14 +154,15 @@ __device__ __forceinline__ void output_snn_onehot(const f32x4 (&z)[2], int lab, 
     }
 }
 
-template <int TYPE, bool LABELS, int R, int NOT>
+/* STORE = false (forward-only evaluation): loss and hits only, no delta3 image */
+template <int TYPE, bool LABELS, int R, int NOT, bool STORE = true>
 __device__ __forceinline__ void output_layer(const f32x4 (&z)[2], int lab, const float *__restrict__ T, int ldt,
                                              float t_hi, float t_lo, int s, bool valid, int n_out, char *imgD3,
                                              const LaneOff &lo, int r0, int lane, float inv_nout,
                                              float &my_loss, unsigned int &my_hit) {
     if constexpr (TYPE == 2 && LABELS) {
         if (t_lo == 0.f) {
-            output_snn_onehot<R, NOT>(z, lab, t_hi, valid, n_out, imgD3, lo, r0, lane, inv_nout, my_loss, my_hit);
+            output_snn_onehot<R, NOT, STORE>(z, lab, t_hi, valid, n_out, imgD3, lo, r0, lane, inv_nout, my_loss, my_hit);
             return;
         }
     }
@@ -253,7 +254,7 @@ __device__ __forceinline__ void output_layer(const f32x4 (&z)[2], int lab, const
                 dv[r] = (__bf16)d;
             }
         }
-        *(bf16x4 *)wr_ptr<R>(imgD3, lo, r0, ot * 16) = dv;
+        if constexpr (STORE) *(bf16x4 *)wr_ptr<R>(imgD3, lo, r0, ot * 16) = dv;
     }
     if constexpr (!LABELS) {
         /* hit iff the logit of the (first) max-target column is the max logit */

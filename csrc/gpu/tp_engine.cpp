@@ -952,6 +952,10 @@ extern "C" BOOL hpnn_gpu_train_tp(kernel_ann *k, const DOUBLE *X, const DOUBLE *
         NN_ERROR(stderr, "[shuffle] epoch is not supported by tensor-parallel batched training (one device only)\n");
         return FALSE;
     }
+    if (o->validate) {
+        NN_ERROR(stderr, "[validate] is not supported by tensor-parallel batched training (one device only)\n");
+        return FALSE;
+    }
     if (o->dtype == NN_DTYPE_F64) return train_tp<TpNet<double>>(k, X, T, n, o, st);
     if (o->dtype == NN_DTYPE_F32) return train_tp<TpNet<float>>(k, X, T, n, o, st);
     return train_tp<TpNetBf16>(k, X, T, n, o, st);

@@ -173,6 +173,17 @@ void bind_plan(py::module_ &m) {
              [](BPlan &p, uptr G, float lr, float alpha, float scale, uptr s) {
                  check(p.update_flat((const float *)P(G), lr, alpha, scale, S(s)), "BPlan.update_flat");
              })
+        .def("evaluate",
+             [](BPlan &p, uptr x, int u8, float sc, bool rowmajor, uptr labels, uptr T, int ldt, int n_valid,
+                uptr slots, uptr guess, uptr s) {
+                 XIn v = xin(x, 0, u8, sc);
+                 v.rowmajor = rowmajor ? 1 : 0;
+                 check(p.evaluate(v, (const int *)P(labels), (const float *)P(T), ldt, n_valid, (float *)P(slots),
+                                  (int *)P(guess), S(s)),
+                       "BPlan.evaluate");
+             })
+        .def_readwrite("eval_fused", &BPlan::eval_fused)
+        .def("eval_is_fused", &BPlan::eval_is_fused)
         .def("health", [](BPlan &p, uptr s) { return p.health(S(s)); })
         .def("weights_digest",
              [](BPlan &p, int which, uptr s) {
@@ -400,6 +411,21 @@ PYBIND11_MODULE(_native, m) {
         std::vector<unsigned long long> v(512 * 12);
         check(hpnn_wide2_trace(v.data()), "wide2_trace");
         return v;
+    });
+    m.def("mlp3_eval", [](uptr Xg, int xu8, float xscale, int K0, uptr W0f, uptr W1, uptr W2, uptr labels, uptr T,
+                          int ldt, float t_hi, float t_lo, uptr loss_acc, uptr correct, uptr guess, int Bp,
+                          int n_valid, int n_out, int type, int grid, uptr stream) {
+        const int rc = hpnn_mlp3_eval(P(Xg), xu8, xscale, K0, P(W0f), P(W1), P(W2), (const int *)P(labels),
+                                      (const float *)P(T), ldt, t_hi, t_lo, (float *)P(loss_acc),
+                                      (unsigned int *)P(correct), (int *)P(guess), Bp, n_valid, n_out, type, grid,
+                                      S(stream));
+        if (rc <= 0) check(rc ? rc : -1, "mlp3_eval");
+        return rc;
+    });
+    m.def("validate_commit", [](uptr slots, uptr hist, uptr cursor, unsigned int cap, uptr stream) {
+        check(hpnn_validate_commit((float *)P(slots), (hpnn_val_record *)P(hist), (unsigned int *)P(cursor), cap,
+                                   S(stream)),
+              "validate_commit");
     });
     m.def("mlp3_tile_grid", [](int Bp, int grid) { return hpnn_mlp3_tile_grid(Bp, grid); });
     m.def("mlp3_tile_trace", []() {

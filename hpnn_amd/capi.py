@@ -46,6 +46,8 @@ def lib():
             "nn_set_mode": (None, [vp, i]), "nn_set_dtype": (None, [vp, i]), "nn_set_device": (None, [vp, i]),
             "nn_set_shuffle": (None, [vp, i]), "nn_return_shuffle": (i, [vp]),
             "hpnn_epoch_perm": (None, [u, u, u, vp]),
+            "nn_set_validate": (None, [vp, u]), "nn_return_validate": (u, [vp]),
+            "nn_get_validation": (u, [vp, u, vp, vp, vp, vp]),
             "nn_set_batch": (None, [vp, u]), "nn_set_epochs": (None, [vp, u]),
             "nn_set_learning_rate": (None, [vp, d]), "nn_set_momentum": (None, [vp, d]),
             "nn_set_seed": (None, [vp, u]), "nn_return_seed": (u, [vp]),
@@ -105,7 +107,7 @@ class Network:
 
     # configuration
     def set(self, mode=None, dtype=None, device=None, batch=None, epochs=None, lr=None, momentum=None, seed=None,
-            shuffle=None):
+            shuffle=None, validate=None):
         if mode is not None:
             self.L.nn_set_mode(self.ptr, NN_MODE[mode])
         if dtype is not None:
@@ -124,7 +126,25 @@ class Network:
             self.L.nn_set_seed(self.ptr, seed)
         if shuffle is not None:  # "once" | "epoch" (or a bool: True = "epoch")
             self.L.nn_set_shuffle(self.ptr, NN_SHUFFLE[shuffle] if isinstance(shuffle, str) else int(bool(shuffle)))
+        if validate is not None:  # N: batched training validates on [test_dir] every N epochs (0 = off)
+            self.L.nn_set_validate(self.ptr, int(validate))
         return self
+
+    @property
+    def validate(self):
+        return self.L.nn_return_validate(self.ptr)
+
+    def validation(self):
+        """the validation records of the last train() call: a list of dicts with epoch, loss
+        (mean per sample), correct, n and accuracy, in epoch order"""
+        import numpy as np
+        m = self.L.nn_get_validation(self.ptr, 0, None, None, None, None)
+        ep, co, nn = (np.zeros(m, dtype=np.uint32) for _ in range(3))
+        lo = np.zeros(m, dtype=np.float64)
+        if m:
+            self.L.nn_get_validation(self.ptr, m, ep.ctypes.data, lo.ctypes.data, co.ctypes.data, nn.ctypes.data)
+        return [{"epoch": int(ep[i]), "loss": float(lo[i]), "correct": int(co[i]), "n": int(nn[i]),
+                 "accuracy": float(co[i]) / float(nn[i]) if nn[i] else 0.0} for i in range(m)]
 
     @property
     def shuffle(self):

@@ -431,6 +431,69 @@ class MLP:
         ops.output_delta(self.Z, self.n_out, self.type, self.D[-1], T=Tz, n_valid=n_valid, O=O)
         return O[:n_valid, :self.n_out]
 
+    def evaluate(self, X, labels=None, T=None, n_valid=None, guess=False):
+        """Forward only (validation) on the current stream, no host sync: the loss and the
+        argmax hits of the first n_valid rows of a prepared input X (any number of rows >=
+        n_valid) are added into the validation stat slots (read_eval_stats), apart from the
+        training statistics.  guess=True returns the int32 guesses (lowest index of the largest
+        output, -1 from n_valid up).  The tile path makes one launch over the whole set
+        (hpnn_mlp3_eval: the training front's numbers for the same batch and weights); every
+        other plan -- and the tile path under HPNN_EVAL_FUSED=0 -- runs forward + the output
+        kernel in chunks of Bp rows.  Weights, momenta, gradients and the training statistics
+        are not touched; H, Z and the last D are scratch.  On CPU tensors: the emulation."""
+        rows = X.shape[0] * 32 if self._is_fm(X) else X.shape[0]
+        n_valid = rows if n_valid is None else int(n_valid)
+        if n_valid < 1 or n_valid > rows:
+            raise ValueError(f"n_valid {n_valid} outside the prepared input's {rows} rows")
+        if labels is None and T is None:
+            raise ValueError("evaluate needs labels or dense targets T")
+        vst = self.buf[("vstats", -1)]
+        ldt = T.stride(0) if T is not None else 0
+        if not self._gpu:
+            A = self._rowmajor(X)[:n_valid]
+            for l in range(self.L - 1):
+                A = ops.gemm_nt(A, self.Wb[l], ops.EPI_ACT) if A.shape[0] % 128 == 0 else \
+                    ops.ref_gemm_nt(A, self.Wb[l], ops.EPI_ACT).bfloat16()
+            Z = A.float() @ self.Wb[-1].float().t()
+            t_hi, t_lo = self._t_hilo()
+            D = torch.empty(n_valid, self.Np[-1], dtype=torch.bfloat16)
+            ops.output_delta(Z, self.n_out, self.type, D, labels=None if labels is None else labels[:n_valid],
+                             T=None if T is None else T[:n_valid], t_hi=t_hi, t_lo=t_lo, n_valid=n_valid,
+                             loss_acc=vst[0, 0:1], correct=vst[0, 1:2])
+            if not guess:
+                return None
+            g = torch.full((rows,), -1, dtype=torch.int32)
+            g[:n_valid] = Z[:, :self.n_out].argmax(1).to(torch.int32)
+            return g
+        if self.plan.eval_is_fused() and self._is_fm(X):
+            if X.shape[1] * 16 != self.Kp[0]:
+                raise ValueError(f"fragment-major input {tuple(X.shape)} does not fit Kp0 {self.Kp[0]}")
+            if ops.pad_to(n_valid, 256) > rows:
+                raise ValueError("the tile path evaluates whole 256-row tiles: pad the prepared input")
+            g = torch.empty(ops.pad_to(n_valid, 256), dtype=torch.int32, device=self.device) if guess else None
+            self.plan.evaluate(X.data_ptr(), int(X.dtype == torch.uint8), float(getattr(X, "hpnn_fm_scale", 1.0)),
+                               False, _p(labels), _p(T), ldt, n_valid, vst.data_ptr(), _p(g), _stream())
+            return g
+        Xr = self._rowmajor(X)
+        chunks = (n_valid + self.Bp - 1) // self.Bp
+        if Xr.shape[0] < chunks * self.Bp:  # the per-layer kernels read whole Bp-row chunks
+            Xr = torch.cat([Xr, Xr.new_zeros(chunks * self.Bp - Xr.shape[0], Xr.shape[1])])
+        g = torch.full((chunks * self.Bp,), -1, dtype=torch.int32, device=self.device) if guess else None
+        for c in range(chunks):
+            r0 = c * self.Bp
+            self.plan.evaluate(Xr[r0:].data_ptr(), 0, 1.0, True, _p(None if labels is None else labels[r0:]),
+                               _p(None if T is None else T[r0:]), ldt, min(self.Bp, n_valid - r0), vst.data_ptr(),
+                               _p(None if g is None else g[r0:]), _stream())
+        return g
+
+    def reset_eval_stats(self):
+        self.buf[("vstats", -1)].zero_()
+
+    def read_eval_stats(self):
+        """(loss sum, hits) of the evaluate() calls since the last reset (synchronises)"""
+        s = self.buf[("vstats", -1)].cpu()
+        return float(s[:, 0].double().sum()), int(s[:, 1].contiguous().view(torch.int32).long().sum())
+
     def healthy(self):
         """False when an in-kernel hand-off (the fused G0's split-K tickets, a fused TN
         gradient's tickets, the wide front's tile pair) timed out since the model was made:

@@ -287,6 +287,52 @@ def mlp3_tile(Xg, K0, W0, W0f, W1, W2, W2t, D1g, gslab, n_out, net_type, labels=
     return D1g
 
 
+def mlp3_eval(Xg, K0, W0, W0f, W1, W2, n_out, net_type, labels=None, T=None, t_hi=1.0, t_lo=0.0, n_valid=None,
+              loss_acc=None, correct=None, guess=None, xscale=1.0, grid=0):
+    """Forward-only form of mlp3_tile (validation; csrc/gpu/kernels_mlp3t.hip, EVAL): the same
+    fragment-major input and weights, the same rounding points, so the loss and the argmax hits
+    of the first n_valid rows (added into loss_acc / correct, stat-slot layout) are the numbers
+    the training front reports for the batch.  guess (optional int32 [Bp]): the lowest index of
+    the largest logit, -1 from n_valid up.  No deltas, no slabs.  grid: workgroups (0 = one per
+    CU, capped at the tiles).  W0 (row-major) is used by the CPU emulation only."""
+    Bp = Xg.shape[0] * 32
+    n_valid = Bp if n_valid is None else int(n_valid)
+    u8 = Xg.dtype == torch.uint8
+    if _cpu(Xg):
+        X = from_fragment_major(Xg, Bp, K0)
+        H1 = bipolar((X.float() @ W0.float().t()) * xscale).bfloat16()
+        H2 = bipolar(H1.float() @ W1.float().t()).bfloat16()
+        Z = H2.float() @ W2.float().t()
+        D3 = torch.empty(Bp, W2.shape[0], dtype=torch.bfloat16)
+        _cpu_output_delta(Z, n_out, net_type, D3, labels, T, t_hi, t_lo, n_valid, None, loss_acc, correct)
+        if guess is not None:
+            guess.fill_(-1)
+            guess[:n_valid] = Z[:n_valid, :n_out].argmax(1).to(torch.int32)
+        return guess
+    native().mlp3_eval(Xg.data_ptr(), int(u8), float(xscale), K0, W0f.data_ptr(), W1.data_ptr(), W2.data_ptr(),
+                       _ptr(labels), _ptr(T), T.stride(0) if T is not None else 0, float(t_hi), float(t_lo),
+                       _ptr(loss_acc), _ptr(correct), _ptr(guess), Bp, n_valid, n_out, net_type, int(grid), _stream())
+    return guess
+
+
+def validate_commit(slots, hist, cursor):
+    """file one validation pass: the 64 stat slots summed in slot order (the float loss at [0]
+    plus the double the FP64 / FP32 engines keep in floats 2..3) -> hist[cursor] = (float64 loss
+    sum, uint32 hits, pad), the slots zeroed, cursor += 1 (a full history drops the record).  hist: [cap, 2] float64 (row = 16 bytes), cursor: [1] int32; one capturable launch."""
+    cap = hist.shape[0]
+    if _cpu(slots):
+        c = int(cursor[0])
+        if c < cap:
+            hist[c, 0] = slots[:, 0].double().sum() + slots[:, 2:4].contiguous().view(torch.float64).sum()
+            hist[c, 1:2].view(torch.int32)[0] = int(slots[:, 1].contiguous().view(torch.int32).long().sum())
+            hist[c, 1:2].view(torch.int32)[1] = 0
+            cursor[0] = c + 1
+        slots[:, :4] = 0
+        return hist
+    native().validate_commit(slots.data_ptr(), hist.data_ptr(), cursor.data_ptr(), cap, _stream())
+    return hist
+
+
 WIDE2_K0 = (4096,)  # first-layer input widths of hpnn_wide2_front
 WIDE2_TILE = 128  # samples per tile (the batch must be a multiple)
 

@@ -126,6 +126,11 @@ typedef struct {
     nn_parallel parallel;
     /* -- batched sample order: [shuffle] once (default) | epoch -- */
     nn_shuffle shuffle;
+    /* -- [validate] N: batched training evaluates [test_dir] every N epochs (0: off); the
+     *    records of the last nn_train_kernel call (nn_get_validation) -- */
+    UINT validate;
+    UINT n_validation;
+    void *validation;
 } nn_def;
 
 #define _NN(a, b) nn_##a##_##b
@@ -264,6 +269,16 @@ DOUBLE _NN(return, momentum)(nn_def *conf);
 void _NN(set, shuffle)(nn_def *conf, nn_shuffle shuffle);
 void _NN(get, shuffle)(nn_def *conf, nn_shuffle *shuffle);
 nn_shuffle _NN(return, shuffle)(nn_def *conf);
+/* [validate] N: batched training evaluates the held-out set ([test_dir], a directory or a pack
+ * file, in name order) forward-only after every epoch whose absolute number is a multiple of
+ * N and after the last epoch of the call; 0 = off.  nn_train_kernel prints one
+ * "VALIDATION: epoch E loss=L acc=C/N" line per pass and keeps the records for
+ * nn_get_validation: up to max records of the last call into the arrays (any may be NULL),
+ * returns the number of records the call made */
+void _NN(set, validate)(nn_def *conf, UINT every);
+void _NN(get, validate)(nn_def *conf, UINT *every);
+UINT _NN(return, validate)(nn_def *conf);
+UINT _NN(get, validation)(nn_def *conf, UINT max, UINT *epoch, DOUBLE *loss, UINT *correct, UINT *n);
 /* the [shuffle] epoch permutation (libhpnn/shuffle.h): out[i] = index, in the order drawn once
  * from [seed], of the sample at position i of epoch `epoch` (epochs completed before it) */
 void hpnn_epoch_perm(UINT n, UINT seed, UINT epoch, UINT *out);

@@ -49,6 +49,8 @@ void hpnn_metrics_emit(const char *event, const char *fields);
 /* epoch record of the batched drivers */
 void hpnn_metrics_epoch(const char *engine, UINT epoch, double loss, UINT correct, UINT n, double seconds,
                         UINT64 samples);
+/* "validation" record ([validate] N): the held-out set after `epoch` completed epochs */
+void hpnn_metrics_validation(const char *engine, UINT epoch, double loss, UINT correct, UINT n);
 
 /* debug mode */
 int hpnn_debug_enabled(void);

@@ -10,6 +10,8 @@
  *   -l LR learning rate, -a ALPHA momentum,
  *   -R (train_nn only) reshuffle the samples every epoch of batched training (same as
  *   [shuffle] epoch),
+ *   -V N (train_nn only) validate on [test_dir] every N epochs of batched training and after
+ *   the last one (same as [validate] N),
  *   -r FILE exact-resume state (loaded when present, written after training),
  *   -M FILE JSON-lines metrics (same as HPNN_METRICS=FILE),
  *   -T trace ranges + timing table (same as HPNN_TRACE=1).
@@ -30,6 +32,7 @@ typedef struct {
     int dtype; /* -1 = from conf */
     int force_cpu;
     int reshuffle; /* -R */
+    unsigned validate; /* -V N */
     double lr, alpha;
     const char *state;   /* -r */
     const char *metrics; /* -M */
@@ -81,13 +84,13 @@ static int cli_parse(int argc, char **argv, cli_opts *o, int allow_x) {
                 j++;
                 continue;
             }
-            if (strchr("OBSGbemdlarM", c)) {
+            if (strchr("OBSGbemdlarM", c) || (c == 'V' && allow_x)) {
                 const char *val = a[j + 1] ? &a[j + 1] : (i + 1 < argc ? argv[++i] : NULL);
                 if (!val) {
                     _OUT(stderr, "syntax error: missing -%c parameter!\n", c);
                     return -1;
                 }
-                if (strchr("OBSGbe", c)) {
+                if (strchr("OBSGbeV", c)) {
                     if (!isdigit((unsigned char)*val) || atoi(val) <= 0) {
                         _OUT(stderr, "syntax error: bad -%c parameter!\n", c);
                         return -1;
@@ -100,6 +103,7 @@ static int cli_parse(int argc, char **argv, cli_opts *o, int allow_x) {
                         case 'G': o->gpus = v; break;
                         case 'b': o->batch = v; o->mode = NN_MODE_BATCHED; break;
                         case 'e': o->epochs = v; break;
+                        case 'V': o->validate = v; break;
                     }
                 } else if (c == 'm') {
                     o->mode = (val[0] == 'b' || val[0] == 'B') ? NN_MODE_BATCHED : NN_MODE_ONLINE;
@@ -139,6 +143,7 @@ static void cli_apply_conf(const cli_opts *o, nn_def *conf) {
     if (o->epochs) _NN(set, epochs)(conf, o->epochs);
     if (o->force_cpu) _NN(set, device)(conf, NN_DEVICE_CPU);
     if (o->reshuffle) _NN(set, shuffle)(conf, NN_SHUFFLE_EPOCH);
+    if (o->validate) _NN(set, validate)(conf, o->validate);
     if (o->lr > 0) _NN(set, learning_rate)(conf, o->lr);
     if (o->alpha >= 0) _NN(set, momentum)(conf, o->alpha);
 }

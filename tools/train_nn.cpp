@@ -32,6 +32,7 @@ static void dump_help(void) {
     _OUT(stdout, "-l X\tlearning rate.  -a X momentum.\n");
     _OUT(stdout, "-c \tforce the CPU engine.\n");
     _OUT(stdout, "-R \treshuffle the samples every epoch (batched mode; [shuffle] epoch).\n");
+    _OUT(stdout, "-V N\tvalidate on [test_dir] every N epochs and after the last (batched mode; [validate] N).\n");
     _OUT(stdout, "-r F\texact-resume state file (read if present, written after training).\n");
     _OUT(stdout, "-M F\tJSON-lines metrics file.  -T trace ranges + timing table.\n");
     _OUT(stdout, "***********************************\n");
