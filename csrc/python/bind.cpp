@@ -384,6 +384,18 @@ PYBIND11_MODULE(_native, m) {
         check(hpnn_update_fp(f64, P(W), P(V), P(G), Sn, gstride, n, lr, alpha, scale, momentum, S(stream)),
               "update_fp");
     });
+    m.def("output_fp_eval", [](int f64, uptr Z, int ldz, uptr T, int ldt, uptr guess, uptr slots, int B, int n_valid,
+                               int n_out, int type, uptr stream) {
+        check(hpnn_output_fp_eval(f64, P(Z), ldz, P(T), ldt, (int *)P(guess), (float *)P(slots), B, n_valid, n_out,
+                                  type, S(stream)),
+              "output_fp_eval");
+    });
+    m.def("reduce_fp", [](int f64, uptr out, uptr G, int Sn, long gstride, long n, uptr stream) {
+        check(hpnn_reduce_fp(f64, P(out), P(G), Sn, gstride, n, S(stream)), "reduce_fp");
+    });
+    m.def("dact_fp", [](int f64, uptr out, uptr in, uptr aux, long n, uptr stream) {
+        check(hpnn_dact_fp(f64, P(out), P(in), P(aux), n, S(stream)), "dact_fp");
+    });
     m.def("wide2_front", [](uptr X, int ldx, int K0, uptr W0, uptr W1, uptr W1t, uptr labels, uptr T, int ldt,
                             float t_hi, float t_lo, uptr H0, uptr D2, uptr D1, uptr pbuf, uptr cnt, uptr flag, uptr err,
                             uptr loss, uptr correct, int Bp, int n_valid, int n_out, int type, int ksplit,
