@@ -1,0 +1,670 @@
+/*
+ * libhpnn batched GPU engine -- the two net adapters the drivers are templated over:
+ * Batched (BF16 MFMA, FP32 masters: the library's BPlan) and BatchedFP<T> (FP64 / FP32).
+ * Per minibatch
+ *     forward   gemm_nt(act) per layer          (MFMA bf16)
+ *     output    output_delta (act/softmax+loss+delta+accuracy)
+ *     backward  gemm_nt(W^T, * f'(h)) per layer (MFMA bf16)
+ *     gradient  gemm_tn split-K FP32 slabs      (MFMA bf16, tr-LDS reads)
+ *     update    sgd_update (slab reduce + BP/BPM + BF16 W / W^T refresh)
+ * Weights: host FP64 kernel_ann is the I/O master; the device keeps FP32 masters.
+ */
+#ifndef HPNN_GPU_BATCHED_NET_H
+#define HPNN_GPU_BATCHED_NET_H
+#include <libhpnn/xar.h>
+#include <algorithm>
+#include <memory>
+#include <string>
+
+#include "batched_common.h"
+#include "bplan.h"
+#include "../dist/dp_exchange.h"
+
+namespace hpnn {
+namespace eng {
+
+/* upload n host rows (FP64) as a padded BF16 matrix [rows_p x cols_p] */
+inline BOOL upload_bf16(const DOUBLE *src, int rows, int cols, int rows_p, int cols_p, void **dst, hipStream_t s) {
+    DevBuf<char> tmp;
+    HIPCHK(hpnn_dev_malloc(dst, (size_t)rows_p * cols_p * 2));
+    HIPCHK(tmp.alloc((size_t)rows * cols * 8));
+    HIPCHK(hipMemcpyAsync(tmp.get(), src, (size_t)rows * cols * 8, hipMemcpyHostToDevice, s));
+    if (hpnn_pack_bf16(tmp.get(), 1, rows, cols, cols, *dst, rows_p, cols_p, cols_p, s)) return FALSE;
+    HIPCHK(hipStreamSynchronize(s));
+    return TRUE;
+}
+
+/* a new device buffer *dst holding the bytes host bytes at h */
+inline BOOL upload_bytes(const void *h, size_t bytes, void **dst, hipStream_t s) {
+    HIPCHK(hpnn_dev_malloc(dst, bytes));
+    HIPCHK(hipMemcpyAsync(*dst, h, bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return TRUE;
+}
+
+/* round-to-nearest-even FP32 -> BF16 bits (the kernels' rounding) */
+inline uint16_t bf16_bits(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    return (uint16_t)((u + 0x7FFF + ((u >> 16) & 1)) >> 16);
+}
+
+/* host [rows][cols] -> fragment-major [rows_p/32][cols_p/16][64][8] (hpnn_amd.ops.to_fragment_major:
+ * lane 16 g + r of fragment (t, cb) holds A[32 t + 8 g + j][16 cb + r], j < 8), zero padded */
+template <typename E, typename Cvt>
+std::vector<E> to_fragment_major(const DOUBLE *src, int rows, int cols, int rows_p, int cols_p, Cvt cvt) {
+    std::vector<E> out((size_t)rows_p * cols_p, (E)0);
+    const int nbc = cols_p / 16;
+    for (int r = 0; r < rows; r++) {
+        const int t = r / 32, g = (r % 32) / 8, j = r % 8;
+        for (int c = 0; c < cols; c++) {
+            const size_t idx = ((((size_t)t * nbc + c / 16) * 64) + 16 * g + c % 16) * 8 + j;
+            out[idx] = cvt(src[(size_t)r * cols + c]);
+        }
+    }
+    return out;
+}
+
+/* BF16 batched engine: an adapter of the library's batched plan (bplan.h, the same object
+ * hpnn_amd.models.MLP binds) to the precision-generic drivers below */
+struct Batched {
+    typedef float target_t; /* dense targets, uploaded once */
+    typedef float grad_t;   /* flat gradient buffer (the all-reduce payload) */
+    static constexpr hpnn_comm_dtype comm_dt = HPNN_DT_F32;
+    static const char *name() { return "bf16"; }
+    static constexpr size_t ACC_BYTES = HPNN_STAT_SLOTS * HPNN_STAT_STRIDE * 4;
+    static int reduce_sum(grad_t *buf, int G, size_t count, hipStream_t st) {
+        return hpnn_reduce_slabs(buf, G, (long)count, (long)count, buf, st);
+    }
+    hpnn::BPlan p;
+    int L = 0, Bp = 0;
+    float *acc = nullptr, *gflat = nullptr;
+    size_t goff[17] = {0};
+    bool fm_ok = true; /* minibatch starts are multiples of 32 rows: fragment-major inputs */
+    bool own_flat = false; /* the plan owns its flat buffer (loopback re-points it) */
+    hipStream_t s = nullptr;
+
+    ~Batched() {
+        if (s) hipStreamSynchronize(s);
+    }
+
+    BOOL read_stats(double *loss, unsigned int *hits) { return p.read_stats(loss, hits, s) == 0; }
+
+    /* layer l: host FP64 [N][M] -> the zero-padded FP32 [Np][Kp] device buffer, and back */
+    BOOL pad_f32(float *dev, const DOUBLE *host, const layer_ann *ly, int l) {
+        const int M = (int)ly->n_inputs, N = (int)ly->n_neurons, Kp = p.Kp[l];
+        std::vector<float> tmp((size_t)p.Np[l] * Kp, 0.f);
+        for (int n = 0; n < N; n++)
+            for (int m = 0; m < M; m++) tmp[(size_t)n * Kp + m] = (float)host[(size_t)n * M + m];
+        HIPCHK(hipMemcpyAsync(dev, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return TRUE;
+    }
+    BOOL unpad(DOUBLE *host, const float *dev, const layer_ann *ly, int l) {
+        const int M = (int)ly->n_inputs, N = (int)ly->n_neurons, Kp = p.Kp[l];
+        std::vector<float> tmp((size_t)p.Np[l] * Kp);
+        HIPCHK(hipMemcpy(tmp.data(), dev, tmp.size() * 4, hipMemcpyDeviceToHost));
+        for (int n = 0; n < N; n++)
+            for (int m = 0; m < M; m++) host[(size_t)n * M + m] = tmp[(size_t)n * Kp + m];
+        return TRUE;
+    }
+
+    /* allow_fm: every minibatch (shard) this net trains starts at a row multiple of 32;
+     * fused: the plan's structure request (-1 auto, 0 per-layer only) */
+    BOOL init(kernel_ann *k, int B, nn_type t, bool momentum, hipStream_t st, bool allow_fm = true, int fused = -1) {
+        s = st;
+        L = (int)k->n_hiddens + 1;
+        std::vector<int> sizes(L + 1);
+        sizes[0] = (int)k->n_inputs;
+        for (int l = 0; l < L; l++) sizes[l + 1] = (int)layer_of(k, l)->n_neurons;
+        const int type = plan_type(t);
+        std::string err;
+        int rc = p.configure(sizes.data(), L, type, B, momentum, fused, nullptr, 512, true, &err);
+        if (!rc && !allow_fm && p.mode == 't') /* the tile front reads fragment-major rows only */
+            rc = p.configure(sizes.data(), L, type, B, momentum, 'x', nullptr, 512, true, &err);
+        if (rc) {
+            NN_ERROR(stderr, "batched plan: %s (%d)\n", err.c_str(), rc);
+            return FALSE;
+        }
+        fm_ok = allow_fm;
+        if (p.allocate(s)) return FALSE;
+        Bp = p.Bp;
+        for (int l = 0; l < L; l++) {
+            const layer_ann *ly = layer_of(k, l);
+            if (!pad_f32(p.W32[l], ly->weights, ly, l)) return FALSE;
+        }
+        if (p.cast_weights(s)) return FALSE;
+        acc = p.stats;
+        gflat = p.gflat;
+        memcpy(goff, p.goff, sizeof goff);
+        NN_DBG(stdout, "batched plan: mode %c, Bp %d, G0 splits %d\n", p.mode ? p.mode : '-', p.Bp, p.S[0]);
+        return TRUE;
+    }
+
+    /* the training set in the plan's input layout: fragment-major for the tile front, plus a
+     * fragment-major byte copy for mode 'x'; data that are all integers 0..255 (the reference's
+     * pmnist pixels) go as bytes -- the same values, half the bytes of BF16 */
+    BOOL upload_x(const DOUBLE *src, int rows, int cols, int rows_p, XSet *xs) {
+        const int lay = fm_ok ? p.input_layout() : 0, Kp0 = p.Kp[0];
+        rows_p = pad_rows(rows_p, 32);
+        bool u8 = lay != 0;
+        for (size_t i = 0; u8 && i < (size_t)rows * cols; i++) {
+            const DOUBLE v = src[i];
+            u8 = v >= 0.0 && v <= 255.0 && v == (DOUBLE)(int)v;
+        }
+        xs->u8 = u8 ? 1 : 0;
+        xs->scale = 1.f;
+        auto put = [&](const void *h, size_t bytes, void **dst) { return upload_bytes(h, bytes, dst, s); };
+        if (lay == 1) {
+            if (u8) {
+                auto h = to_fragment_major<uint8_t>(src, rows, cols, rows_p, Kp0, [](DOUBLE v) { return (uint8_t)v; });
+                xs->row_bytes = Kp0;
+                return put(h.data(), h.size(), &xs->x);
+            }
+            auto h = to_fragment_major<uint16_t>(src, rows, cols, rows_p, Kp0,
+                                                 [](DOUBLE v) { return bf16_bits((float)v); });
+            xs->row_bytes = (size_t)Kp0 * 2;
+            return put(h.data(), h.size() * 2, &xs->x);
+        }
+        if (!upload_bf16(src, rows, cols, rows_p, Kp0, &xs->x, s)) return FALSE;
+        xs->row_bytes = (size_t)Kp0 * 2;
+        if (lay == 2 && u8) {
+            auto h = to_fragment_major<uint8_t>(src, rows, cols, rows_p, Kp0, [](DOUBLE v) { return (uint8_t)v; });
+            xs->row_bytes_g = Kp0;
+            return put(h.data(), h.size(), &xs->xg);
+        }
+        xs->u8 = 0;
+        return TRUE;
+    }
+    /* [shuffle] epoch: the row-major canonical copies (cn) the gathers read; xs, from upload_x,
+     * is the staging set in the plan's layout that the steps read */
+    static constexpr bool dense_always = false; /* with labels the dense targets are not read */
+    BOOL upload_canon(const DOUBLE *src, int rows, int cols, const XSet &xs, XSet *cn) {
+        const int lay = fm_ok ? p.input_layout() : 0, Kp0 = p.Kp[0];
+        if (xs.u8) {
+            std::vector<uint8_t> h((size_t)rows * Kp0, 0);
+            for (int r = 0; r < rows; r++)
+                for (int c = 0; c < cols; c++) h[(size_t)r * Kp0 + c] = (uint8_t)src[(size_t)r * cols + c];
+            if (!upload_bytes(h.data(), h.size(), lay == 1 ? &cn->x : &cn->xg, s)) return FALSE;
+            if (lay == 1) return TRUE;
+        }
+        return upload_bf16(src, rows, cols, rows, Kp0, &cn->x, s);
+    }
+    BOOL gather(const XSet &cn, const XSet &xs, const int *perm, int n, int rows_p) {
+        const int lay = fm_ok ? p.input_layout() : 0, Kp0 = p.Kp[0];
+        rows_p = pad_rows(rows_p, 32);
+        if (lay == 1) return hpnn_gather_fm(xs.x, cn.x, perm, n, rows_p, Kp0, xs.u8 ? 1 : 2, s) == 0;
+        if (hpnn_gather_rows(xs.x, cn.x, perm, n, rows_p, (long)Kp0 * 2, s)) return FALSE;
+        return !xs.xg || hpnn_gather_fm(xs.xg, cn.xg, perm, n, rows_p, Kp0, 1, s) == 0;
+    }
+    /* [validate]: the held-out set as BPlan::evaluate reads it -- the plan's fragment-major
+     * layout padded to whole 256-row tiles on the tile path (one launch over the set), else
+     * row-major BF16 padded to whole Bp-row chunks (forward + output kernel per chunk) */
+    BOOL upload_val(const DOUBLE *src, int rows, int cols, XSet *vs, int *rows_p) {
+        if (p.eval_is_fused()) {
+            *rows_p = pad_rows(rows, 256);
+            return upload_x(src, rows, cols, *rows_p, vs);
+        }
+        *rows_p = pad_rows(rows, p.Bp);
+        vs->row_bytes = (size_t)p.Kp[0] * 2;
+        return upload_bf16(src, rows, cols, *rows_p, p.Kp[0], &vs->x, s);
+    }
+    float *vacc() { return p.vstats; }
+    BOOL evaluate(const XSet &vs, const float *T, int ldt, int nv) {
+        int r = 0;
+        if (p.eval_is_fused()) {
+            r = p.evaluate(at(vs, 0), vs.lab, vs.lab ? nullptr : T, ldt, nv, p.vstats, nullptr, s);
+        } else {
+            for (long row = 0; row < nv && !r; row += p.Bp) {
+                hpnn::XIn v;
+                v.x = (const char *)vs.x + row * vs.row_bytes;
+                v.rowmajor = 1;
+                const int *lb = vs.lab ? vs.lab + row : nullptr;
+                r = p.evaluate(v, lb, lb ? nullptr : T + (size_t)row * ldt, ldt, std::min((long)p.Bp, nv - row),
+                               p.vstats, nullptr, s);
+            }
+        }
+        if (r) NN_ERROR(stderr, "batched validation pass failed: %d\n", r);
+        return r == 0;
+    }
+    hpnn::XIn at(const XSet &xs, long row) const {
+        hpnn::XIn v;
+        v.x = (const char *)xs.x + row * xs.row_bytes;
+        v.xg = xs.xg ? (const char *)xs.xg + row * xs.row_bytes_g : nullptr;
+        v.u8 = xs.u8;
+        v.scale = xs.scale;
+        return v;
+    }
+
+    BOOL step(const XSet &xs, long row, const float *T, int ldt, int n_valid, float lr, float alpha, bool) {
+        const int *L = xs.lab ? xs.lab + row : nullptr;
+        const int r = p.step(at(xs, row), L, L ? nullptr : T, ldt, n_valid, lr, alpha, s);
+        if (r) NN_ERROR(stderr, "batched step failed: %d\n", r);
+        return r == 0 && hpnn_debug_check("batched training step") == 0;
+    }
+
+    /* data parallel: gradients into the flat FP32 buffer (the all-reduce payload) */
+    BOOL alloc_flat(float *external = nullptr) {
+        if (external) p.gflat = external; /* loopback: replicas' buffers in one allocation */
+        gflat = p.gflat;
+        return TRUE;
+    }
+    size_t flat_count() const { return p.goff[L]; }
+    template <class Ready>
+    BOOL grads(const XSet &xs, long row, const float *T, int ldt, int n_valid, Ready &&ready) {
+        const int *L = xs.lab ? xs.lab + row : nullptr;
+        const int r = p.grads(at(xs, row), L, L ? nullptr : T, ldt, n_valid, hpnn::ReadyFn(ready), s);
+        if (r) NN_ERROR(stderr, "batched gradients failed: %d\n", r);
+        return r == 0;
+    }
+    BOOL grads(const XSet &xs, long row, const float *T, int ldt, int n_valid) {
+        /* no exchange to overlap (the xGMI all-reduce of the whole buffer follows): the fused
+         * modes reduce G0 and [G1|G2] inside the G0 launch */
+        const int *L = xs.lab ? xs.lab + row : nullptr;
+        const int r = p.grads_local(at(xs, row), L, L ? nullptr : T, ldt, n_valid, s);
+        if (r != -1) {
+            if (r) NN_ERROR(stderr, "batched gradients failed: %d\n", r);
+            return r == 0;
+        }
+        return grads(xs, row, T, ldt, n_valid, [](int, int) { return true; });
+    }
+    std::vector<std::pair<int, int>> buckets() const { return p.buckets(); }
+    BOOL update_flat(const float *G, float lr, float alpha, float scale, bool) {
+        return p.update_flat(G, lr, alpha, scale, s) == 0;
+    }
+
+    /* one process per GPU: the library's data-parallel step (dp_exchange.h) */
+    std::unique_ptr<hpnn::DpExchange> dpx;
+    bool attach_dpx(hpnn_comm *c, int mode) {
+        dpx.reset(new hpnn::DpExchange());
+        if (dpx->init(&p, c, mode)) dpx.reset();
+        return (bool)dpx;
+    }
+    BOOL dp_step(const XSet &xs, long row, const float *T, int ldt, int nv, int total, float lr, float alpha) {
+        const int *L = xs.lab ? xs.lab + row : nullptr;
+        return dpx && dpx->step(at(xs, row), L, L ? nullptr : T, ldt, nv, total, lr, alpha, s) == 0;
+    }
+    BOOL gather_masters() { return !dpx || dpx->gather_masters(s) == 0; }
+    /* fused modes: front + G0 with the exchange over xk and every layer's step in the same
+     * launch (BPlan::xchg_step, the Python DataParallel's path); -1 = not covered */
+    int xchg_step(const XSet &xs, long row, const float *T, int ldt, int nv, float lr, float alpha, float scale,
+                  hpnn_xar *xk) {
+        hpnn_xar_view v;
+        if (hpnn_xar_view_get(xk, &v)) return -2;
+        const int *L = xs.lab ? xs.lab + row : nullptr;
+        return p.xchg_step(at(xs, row), L, L ? nullptr : T, ldt, nv, lr, alpha, scale, v, s);
+    }
+    bool has_dpx() const { return (bool)dpx; }
+    void detach_dpx() { dpx.reset(); }
+
+    /* FALSE when an in-kernel hand-off (fused G0 split-K tickets, fused TN tickets, the wide
+     * front's tile pair) timed out since the plan was made: that launch stepped with partial
+     * sums, so training must not go on from those weights (reference: CHK_ERR after every
+     * launch, common.h:324-335) */
+    static BOOL handoff_timed_out() {
+        NN_ERROR(stderr, "batched GPU training: an in-kernel split-K / tile hand-off timed out "
+                         "(the step used partial sums); stopping\n");
+        return FALSE;
+    }
+    BOOL healthy() { return p.health(s) == 0 ? TRUE : handoff_timed_out(); }
+    /* healthy() in two halves: enqueue the readback into d[0..2] (pinned, zeroed), judge it
+     * once an event after it has completed */
+    bool health_enqueue(unsigned int *d) { return p.health_enqueue(s, d) == 0; }
+    BOOL health_ok(const unsigned int *d) { return (d[0] || d[1] || d[2]) ? handoff_timed_out() : TRUE; }
+    /* digest of the weights every data-parallel replica must hold bit for bit: the BF16 copies,
+     * plus the FP32 masters unless the BF16 reduce-scatter step keeps them sharded */
+    BOOL digest(unsigned long long *d) {
+        bool sh = false;
+        for (int l = 0; dpx && l < L; l++) sh = sh || dpx->sharded(l);
+        return p.weights_digest(sh ? 1 : 3, d, s) == 0;
+    }
+
+    /* FP32 master weights (and BPM momentum, into k->dw) -> host FP64 */
+    BOOL download(kernel_ann *k) {
+        HIPCHK(hipStreamSynchronize(s));
+        if (p.V32[0]) ann_momentum_init(k);
+        for (int l = 0; l < L; l++) {
+            layer_ann *ly = layer_of(k, l);
+            if (!unpad(ly->weights, p.W32[l], ly, l)) return FALSE;
+            if (p.V32[l] && !unpad(k->dw[l], p.V32[l], ly, l)) return FALSE;
+        }
+        return TRUE;
+    }
+
+    /* the replica state (FP32 masters + momentum, padded) as bytes, and back (then the BF16
+     * copies are re-derived): rank 0's state re-broadcast after an exchange fallback */
+    BOOL get_state(std::vector<char> &out) {
+        out.clear();
+        HIPCHK(hipStreamSynchronize(s));
+        for (int l = 0; l < L; l++)
+            for (float *b : {p.W32[l], p.V32[l]}) {
+                if (!b) continue;
+                const size_t n = (size_t)p.Np[l] * p.Kp[l] * 4, o = out.size();
+                out.resize(o + n);
+                HIPCHK(hipMemcpy(out.data() + o, b, n, hipMemcpyDeviceToHost));
+            }
+        return TRUE;
+    }
+    BOOL set_state(const char *in) {
+        size_t o = 0;
+        for (int l = 0; l < L; l++)
+            for (float *b : {p.W32[l], p.V32[l]}) {
+                if (!b) continue;
+                const size_t n = (size_t)p.Np[l] * p.Kp[l] * 4;
+                HIPCHK(hipMemcpy(b, in + o, n, hipMemcpyHostToDevice));
+                o += n;
+            }
+        return p.cast_weights(s) == 0 && hipStreamSynchronize(s) == hipSuccess;
+    }
+
+    /* exact resume: BPM momentum k->dw (host FP64) -> padded FP32 V32 */
+    BOOL upload_momentum(const kernel_ann *k) {
+        if (!k->dw) return TRUE;
+        for (int l = 0; l < L; l++)
+            if (p.V32[l] && !pad_f32(p.V32[l], k->dw[l], layer_of((kernel_ann *)k, l), l)) return FALSE;
+        return TRUE;
+    }
+};
+
+/* FP64 / FP32 batched engine ([dtype] f64 | f32): the reference's precision (the
+ * reference computes in double throughout, cuda_ann.cu:41-148, 546-548, 2139-2142) on the
+ * FP64 / FP32 MFMA kernels of kernels_fp.hip.  Same minibatch semantics as the FP64 CPU
+ * oracle (cpu_batched.cpp) and as Batched: forward, output delta, deltas with the
+ * pre-update weights, G = sum over the batch, W updated with scale = 1 / n_valid.  No
+ * padding: the kernels take any shape; the backward delta reads W itself (transposed
+ * operand), so no W^T copy is kept. */
+template <typename T>
+struct BatchedFP {
+    typedef T target_t;
+    typedef T grad_t;
+    static constexpr int F64 = sizeof(T) == 8 ? 1 : 0;
+    static constexpr hpnn_comm_dtype comm_dt = sizeof(T) == 8 ? HPNN_DT_F64 : HPNN_DT_F32;
+    static const char *name() { return sizeof(T) == 8 ? "f64" : "f32"; }
+    static constexpr size_t ACC_BYTES = Batched::ACC_BYTES;
+    int L = 0, Bp = 0, n_out = 0, type = 2;
+    int M[16], N[16], S[16];
+    int Kp[16]; /* Kp[0] = n_in: the row pitch of the uploaded input (drivers index rows by it) */
+    T *W[16] = {0}, *V[16] = {0}, *slab[16] = {0}, *H[16] = {0}, *D[16] = {0};
+    T *Z = nullptr, *gflat = nullptr;
+    float *acc = nullptr;
+    bool own_flat = false;
+    size_t goff[17] = {0};
+    hipStream_t s = nullptr;
+
+    BOOL upload_x(const DOUBLE *src, int rows, int cols, int rows_p, XSet *xs) {
+        std::vector<T> h((size_t)rows_p * cols, (T)0);
+        for (size_t i = 0; i < (size_t)rows * cols; i++) h[i] = (T)src[i];
+        xs->row_bytes = (size_t)cols * sizeof(T);
+        return upload_bytes(h.data(), h.size() * sizeof(T), &xs->x, s);
+    }
+    static constexpr bool dense_always = true;
+    BOOL upload_canon(const DOUBLE *src, int rows, int cols, const XSet &, XSet *cn) {
+        return upload_x(src, rows, cols, rows, cn);
+    }
+    BOOL gather(const XSet &cn, const XSet &xs, const int *perm, int n, int rows_p) {
+        return hpnn_gather_rows(xs.x, cn.x, perm, n, rows_p, (long)xs.row_bytes, s) == 0;
+    }
+    static const void *at(const XSet &xs, long row) { return (const char *)xs.x + row * xs.row_bytes; }
+    static int reduce_sum(grad_t *buf, int G, size_t count, hipStream_t st) {
+        return hpnn_reduce_fp(F64, buf, buf, G, (long)count, (long)count, st);
+    }
+    /* [validate]: the held-out rows as they are (the kernels take any shape) and stat slots of
+     * the pass's own; forward + the output kernel without a delta, in chunks of Bp rows */
+    float *vslots = nullptr;
+    BOOL upload_val(const DOUBLE *src, int rows, int cols, XSet *vs, int *rows_p) {
+        *rows_p = rows;
+        if (!vslots) {
+            HIPCHK(hpnn_dev_malloc(&vslots, ACC_BYTES));
+            HIPCHK(hipMemsetAsync(vslots, 0, ACC_BYTES, s));
+        }
+        return upload_x(src, rows, cols, rows, vs);
+    }
+    float *vacc() { return vslots; }
+    BOOL evaluate(const XSet &vs, const T *Tt, int ldt, int nv) {
+        for (long row = 0; row < nv; row += Bp) {
+            const int rows = (int)std::min((long)Bp, nv - row);
+            if (!forward(at(vs, row), rows)) return FALSE;
+            if (hpnn_output_fp_eval(F64, Z, N[L - 1], Tt + (size_t)row * ldt, ldt, nullptr, vslots, rows, rows, n_out,
+                                    type, s))
+                return FALSE;
+        }
+        return TRUE;
+    }
+
+    ~BatchedFP() {
+        if (s) hipStreamSynchronize(s);
+        if (dig) hpnn_dev_free(dig);
+        for (int l = 0; l < 16; l++) {
+            hpnn_dev_free(W[l]);
+            hpnn_dev_free(V[l]);
+            hpnn_dev_free(slab[l]);
+            hpnn_dev_free(H[l]);
+            hpnn_dev_free(D[l]);
+        }
+        hpnn_dev_free(Z);
+        hpnn_dev_free(acc);
+        hpnn_dev_free(vslots);
+        if (own_flat) hpnn_dev_free(gflat);
+    }
+
+    BOOL read_stats(double *loss, unsigned int *hits) { return read_stat_slots(acc, s, loss, hits); }
+
+    BOOL init(kernel_ann *k, int B, nn_type t, bool momentum, hipStream_t st, bool = true, int = -1) {
+        s = st;
+        L = (int)k->n_hiddens + 1;
+        Bp = B;
+        n_out = (int)k->n_outputs;
+        type = plan_type(t);
+        for (int l = 0; l < L; l++) {
+            layer_ann *ly = layer_of(k, l);
+            M[l] = (int)ly->n_inputs;
+            N[l] = (int)ly->n_neurons;
+            Kp[l] = M[l];
+            S[l] = fp_splits(N[l], M[l], Bp);
+            const size_t nw = (size_t)N[l] * M[l];
+            HIPCHK(hpnn_dev_malloc(&W[l], nw * sizeof(T)));
+            HIPCHK(hpnn_dev_malloc(&slab[l], nw * sizeof(T) * S[l]));
+            if (momentum) {
+                HIPCHK(hpnn_dev_malloc(&V[l], nw * sizeof(T)));
+                HIPCHK(hipMemsetAsync(V[l], 0, nw * sizeof(T), s));
+            }
+            HIPCHK(hpnn_dev_malloc(&D[l], (size_t)Bp * N[l] * sizeof(T)));
+            if (l < L - 1) HIPCHK(hpnn_dev_malloc(&H[l], (size_t)Bp * N[l] * sizeof(T)));
+            std::vector<T> tmp(nw);
+            for (size_t i = 0; i < nw; i++) tmp[i] = (T)ly->weights[i];
+            HIPCHK(hipMemcpyAsync(W[l], tmp.data(), nw * sizeof(T), hipMemcpyHostToDevice, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        HIPCHK(hpnn_dev_malloc(&Z, (size_t)Bp * N[L - 1] * sizeof(T)));
+        HIPCHK(hpnn_dev_malloc(&acc, ACC_BYTES));
+        HIPCHK(hipMemsetAsync(acc, 0, ACC_BYTES, s));
+        return TRUE;
+    }
+
+    BOOL forward(const void *X, int rows) {
+        for (int l = 0; l < L; l++) {
+            const T *A = l ? H[l - 1] : (const T *)X;
+            const bool last = l == L - 1;
+            int r = hpnn_gemm_fp(F64, A, M[l], 0, W[l], M[l], 0, last ? (void *)Z : H[l], N[l], nullptr, 0, rows, N[l],
+                                 M[l], last ? HPNN_EPI_NONE : HPNN_EPI_ACT, 1, 0, s);
+            if (r) {
+                NN_ERROR(stderr, "gemm_fp (fwd layer %d) failed: %d\n", l, r);
+                return FALSE;
+            }
+        }
+        return TRUE;
+    }
+
+    /* forward + output delta + hidden deltas + weight gradients (slab[l], S[l] slabs) */
+    BOOL backprop(const void *X, const T *Tt, int ldt, int n_valid) {
+        if (!forward(X, Bp)) return FALSE;
+        if (hpnn_output_fp(F64, Z, N[L - 1], Tt, ldt, D[L - 1], N[L - 1], nullptr, 0, nullptr, acc,
+                           (unsigned int *)(acc + 1), Bp, n_valid, n_out, type, s))
+            return FALSE;
+        for (int l = L - 1; l >= 1; l--) {
+            /* D[l-1] = (D[l] W_l) * f'(H[l-1]): B(n = input m, k = neuron j) = W_l[j][m] */
+            if (hpnn_gemm_fp(F64, D[l], N[l], 0, W[l], M[l], 1, D[l - 1], N[l - 1], H[l - 1], N[l - 1], Bp, M[l], N[l],
+                             HPNN_EPI_DACT, 1, 0, s))
+                return FALSE;
+        }
+        for (int l = 0; l < L; l++) {
+            /* G[n][m] = sum_b D[b][n] H[b][m]: both operands transposed (k = the batch row) */
+            const T *Hin = l ? H[l - 1] : (const T *)X;
+            if (hpnn_gemm_fp(F64, D[l], N[l], 1, Hin, M[l], 1, slab[l], M[l], nullptr, 0, N[l], M[l], Bp,
+                             HPNN_EPI_NONE, S[l], (long)N[l] * M[l], s))
+                return FALSE;
+        }
+        return TRUE;
+    }
+
+    BOOL step(const XSet &xs, long row, const T *Tt, int ldt, int n_valid, double lr, double alpha, bool mom) {
+        if (!backprop(at(xs, row), Tt, ldt, n_valid)) return FALSE;
+        const double scale = 1.0 / (double)n_valid;
+        for (int l = 0; l < L; l++)
+            if (hpnn_update_fp(F64, W[l], V[l], slab[l], S[l], (long)N[l] * M[l], (long)N[l] * M[l], lr, alpha, scale,
+                               mom ? 1 : 0, s))
+                return FALSE;
+        return hpnn_debug_check("batched training step (fp)") == 0;
+    }
+
+    BOOL alloc_flat(T *external = nullptr) {
+        goff[0] = 0;
+        for (int l = 0; l < L; l++) goff[l + 1] = goff[l] + (size_t)N[l] * M[l];
+        if (external) {
+            gflat = external;
+            own_flat = false;
+            return TRUE;
+        }
+        HIPCHK(hpnn_dev_malloc(&gflat, goff[L] * sizeof(T)));
+        own_flat = true;
+        return TRUE;
+    }
+    size_t flat_count() const { return goff[L]; }
+
+    template <class Ready>
+    BOOL grads(const XSet &xs, long row, const T *Tt, int ldt, int n_valid, Ready &&ready) {
+        const void *X = at(xs, row);
+        if (!forward(X, Bp)) return FALSE;
+        if (hpnn_output_fp(F64, Z, N[L - 1], Tt, ldt, D[L - 1], N[L - 1], nullptr, 0, nullptr, acc,
+                           (unsigned int *)(acc + 1), Bp, n_valid, n_out, type, s))
+            return FALSE;
+        for (int l = L - 1; l >= 0; l--) {
+            if (l >= 1 && hpnn_gemm_fp(F64, D[l], N[l], 0, W[l], M[l], 1, D[l - 1], N[l - 1], H[l - 1], N[l - 1], Bp,
+                                       M[l], N[l], HPNN_EPI_DACT, 1, 0, s))
+                return FALSE;
+            const T *Hin = l ? H[l - 1] : (const T *)X;
+            if (hpnn_gemm_fp(F64, D[l], N[l], 1, Hin, M[l], 1, slab[l], M[l], nullptr, 0, N[l], M[l], Bp,
+                             HPNN_EPI_NONE, S[l], (long)N[l] * M[l], s) ||
+                hpnn_reduce_fp(F64, gflat + goff[l], slab[l], S[l], (long)N[l] * M[l], (long)N[l] * M[l], s))
+                return FALSE;
+            if (!ready(l, l)) return FALSE;
+        }
+        return TRUE;
+    }
+    BOOL grads(const XSet &xs, long row, const T *Tt, int ldt, int n_valid) {
+        return grads(xs, row, Tt, ldt, n_valid, [](int, int) { return true; });
+    }
+    std::vector<std::pair<int, int>> buckets() const {
+        std::vector<std::pair<int, int>> v;
+        for (int l = L - 1; l >= 0; l--) v.push_back({l, l});
+        return v;
+    }
+
+    BOOL update_flat(const T *G, double lr, double alpha, double scale, bool mom) {
+        for (int l = 0; l < L; l++)
+            if (hpnn_update_fp(F64, W[l], V[l], G + goff[l], 1, 0, (long)N[l] * M[l], lr, alpha, scale, mom ? 1 : 0, s))
+                return FALSE;
+        return TRUE;
+    }
+
+    bool attach_dpx(hpnn_comm *, int) { return false; } /* FP32 / FP64: the generic bucket loop */
+    BOOL dp_step(const XSet &, long, const T *, int, int, int, double, double) { return FALSE; }
+    int xchg_step(const XSet &, long, const T *, int, int, double, double, double, hpnn_xar *) { return -1; }
+    BOOL gather_masters() { return TRUE; }
+    BOOL healthy() { return TRUE; } /* no in-kernel hand-offs in the FP64 / FP32 kernels */
+    bool health_enqueue(unsigned int *) { return true; }
+    BOOL health_ok(const unsigned int *) { return TRUE; }
+    unsigned long long *dig = nullptr; /* device word of digest() */
+    BOOL digest(unsigned long long *d) {
+        if (!dig && hpnn_dev_malloc((void **)&dig, 8) != hipSuccess) return FALSE;
+        if (hipMemsetAsync(dig, 0, 8, s) != hipSuccess) return FALSE;
+        long base = 0;
+        for (int l = 0; l < L; l++) {
+            const long nb = (long)N[l] * M[l] * (long)sizeof(T);
+            if (hpnn_hash_words(W[l], nb, base, dig, s) != 0) return FALSE;
+            base += nb / 4;
+        }
+        return hipMemcpyAsync(d, dig, 8, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+    }
+    bool has_dpx() const { return false; }
+    void detach_dpx() {}
+
+    BOOL download(kernel_ann *k) {
+        HIPCHK(hipStreamSynchronize(s));
+        if (V[0]) ann_momentum_init(k);
+        for (int l = 0; l < L; l++) {
+            layer_ann *ly = layer_of(k, l);
+            const size_t nw = (size_t)N[l] * M[l];
+            std::vector<T> tmp(nw);
+            HIPCHK(hipMemcpy(tmp.data(), W[l], nw * sizeof(T), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < nw; i++) ly->weights[i] = (DOUBLE)tmp[i];
+            if (!V[l]) continue;
+            HIPCHK(hipMemcpy(tmp.data(), V[l], nw * sizeof(T), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < nw; i++) k->dw[l][i] = (DOUBLE)tmp[i];
+        }
+        return TRUE;
+    }
+
+    BOOL get_state(std::vector<char> &out) {
+        out.clear();
+        HIPCHK(hipStreamSynchronize(s));
+        for (int l = 0; l < L; l++)
+            for (T *b : {W[l], V[l]}) {
+                if (!b) continue;
+                const size_t n = (size_t)N[l] * M[l] * sizeof(T), o = out.size();
+                out.resize(o + n);
+                HIPCHK(hipMemcpy(out.data() + o, b, n, hipMemcpyDeviceToHost));
+            }
+        return TRUE;
+    }
+    BOOL set_state(const char *in) {
+        size_t o = 0;
+        for (int l = 0; l < L; l++)
+            for (T *b : {W[l], V[l]}) {
+                if (!b) continue;
+                const size_t n = (size_t)N[l] * M[l] * sizeof(T);
+                HIPCHK(hipMemcpy(b, in + o, n, hipMemcpyHostToDevice));
+                o += n;
+            }
+        return TRUE;
+    }
+
+    BOOL upload_momentum(const kernel_ann *k) {
+        if (!k->dw) return TRUE;
+        for (int l = 0; l < L; l++) {
+            if (!V[l]) continue;
+            const size_t nw = (size_t)N[l] * M[l];
+            std::vector<T> tmp(nw);
+            for (size_t i = 0; i < nw; i++) tmp[i] = (T)k->dw[l][i];
+            HIPCHK(hipMemcpyAsync(V[l], tmp.data(), nw * sizeof(T), hipMemcpyHostToDevice, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        return TRUE;
+    }
+};
+
+/* the one dtype switch: calls f(NetTag<Net>()) with the adapter of `dt` */
+template <class N>
+struct NetTag {
+    typedef N type;
+};
+template <class F>
+BOOL with_net(nn_dtype dt, F &&f) {
+    if (dt == NN_DTYPE_BF16) return f(NetTag<Batched>());
+    if (dt == NN_DTYPE_F32) return f(NetTag<BatchedFP<float>>());
+    return f(NetTag<BatchedFP<double>>());
+}
+
+}  // namespace eng
+}  // namespace hpnn
+#endif

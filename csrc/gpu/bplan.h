@@ -1,7 +1,7 @@
 /*
  * The batched BF16 training plan: ONE orchestrator of the gfx950 kernels, used by the C
- * library's batched engine (train_nn -m batched: gpu_engine.cpp train_single / train_dp /
- * train_dp_mp, batched run_nn) and, through the pybind11 module, by hpnn_amd.models.MLP
+ * library's batched engine (train_nn -m batched: train_single.cpp / train_dp.cpp /
+ * train_dp_mp.cpp, infer_batched.cpp) and, through the pybind11 module, by hpnn_amd.models.MLP
  * (bench.py, the data-parallel driver, the tests).  Reference being replaced: the per-layer
  * GEMV / GER sequence of nn_train_kernel -> {ann,snn}_train_BP[M] (libhpnn.c:1149-1302,
  * cuda_snn.cu:2726-3717), here over a minibatch.

@@ -86,6 +86,10 @@ typedef struct {
  * ones validates at; out may be NULL; returns the count */
 UINT hpnn_validation_schedule(UINT epoch0, UINT epochs, UINT validate, UINT *out);
 
+/* data-parallel shard (pure): rank's rows [*start, *start + *nv) of global minibatch b (B samples
+ * of n, Bg = ceil(B / world) per rank) and *total, the samples of the whole minibatch */
+void hpnn_dp_shard(int b, int B, int n, int rank, int Bg, int *start, int *nv, int *total);
+
 /* X: n x n_in, T: n x n_out (host, row-major FP64). Weights are read from
  * and written back to the host kernel; with BPM the final momentum is written to
  * k->dw (allocated if needed) so that nn_dump_state can save it. */

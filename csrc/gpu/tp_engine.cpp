@@ -46,23 +46,13 @@
 #include <thread>
 #include <vector>
 
-#include "../core/runtime_internal.h"
+#include "batched_common.h"
 #include "bplan.h"
-#include "engine.h"
-#include "kernels.h"
 
-#define TPCHK(x)                                                                                  \
-    do {                                                                                          \
-        hipError_t e_ = (x);                                                                      \
-        if (e_ != hipSuccess) {                                                                   \
-            NN_ERROR(stderr, "HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); \
-            return FALSE;                                                                         \
-        }                                                                                         \
-    } while (0)
+using namespace hpnn::eng;
 
 namespace {
 
-layer_ann *layer_at(kernel_ann *k, int l) { return l < (int)k->n_hiddens ? &k->hiddens[l] : &k->output; }
 constexpr size_t ACC_BYTES = (size_t)HPNN_STAT_SLOTS * HPNN_STAT_STRIDE * 4;
 
 /* ---------------------------------------------------------------- collectives */
@@ -194,73 +184,63 @@ struct TpNet {
         hpnn_dev_free(acc);
     }
 
-    static int pick(int Nn, int Mm, int B) {
-        const int tiles = ((Nn + 63) / 64) * ((Mm + 63) / 64);
-        int sp = (256 + tiles - 1) / tiles;
-        const int maxs = B / 256 > 0 ? B / 256 : 1;
-        sp = sp < maxs ? sp : maxs;
-        return hpnn_gemm_fp_splits(B, sp < 1 ? 1 : sp);
-    }
 
     /* rows of layer l this rank holds in the host weights: global row of local row j */
     int grow(int l, int j) const { return l < L - 1 ? r * n[l] + j : j; }
+
+    /* this rank's rows of layer l: host FP64 [Ntrue][Mtrue] -> the zero-padded device [n][Mp] */
+    BOOL put_rows(T *dst, const DOUBLE *src, int l) {
+        std::vector<T> tmp((size_t)n[l] * Mp[l], (T)0);
+        for (int j = 0; j < n[l]; j++) {
+            const int g = grow(l, j);
+            if (g >= Ntrue[l]) continue;
+            for (int m = 0; m < Mtrue[l]; m++) tmp[(size_t)j * Mp[l] + m] = (T)src[(size_t)g * Mtrue[l] + m];
+        }
+        HIPCHK(hipMemcpyAsync(dst, tmp.data(), tmp.size() * sizeof(T), hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return TRUE;
+    }
 
     BOOL init(kernel_ann *k, int P_, int r_, int B, nn_type t, bool momentum, hipStream_t st, TpColl<T> *c) {
         P = P_, r = r_, s = st, coll = c, Bp = B;
         L = (int)k->n_hiddens + 1;
         n_out = (int)k->n_outputs;
-        type = t == NN_TYPE_ANN ? 0 : (t == NN_TYPE_LNN ? 1 : 2);
+        type = plan_type(t);
         size_t part_elems = 0;
         for (int l = 0; l < L; l++) {
-            layer_ann *ly = layer_at(k, l);
+            layer_ann *ly = layer_of(k, l);
             Ntrue[l] = (int)ly->n_neurons;
             Mtrue[l] = (int)ly->n_inputs;
             n[l] = l < L - 1 ? (Ntrue[l] + P - 1) / P : Ntrue[l];
             Mp[l] = l == 0 ? Mtrue[0] : (l - 1 < L - 1 ? P * n[l - 1] : Mtrue[l]);
-            S[l] = pick(n[l], Mp[l], Bp);
+            S[l] = fp_splits(n[l], Mp[l], Bp);
             const size_t nw = (size_t)n[l] * Mp[l];
-            TPCHK(hpnn_dev_malloc(&W[l], nw * sizeof(T)));
-            TPCHK(hpnn_dev_malloc(&slab[l], nw * sizeof(T) * S[l]));
+            HIPCHK(hpnn_dev_malloc(&W[l], nw * sizeof(T)));
+            HIPCHK(hpnn_dev_malloc(&slab[l], nw * sizeof(T) * S[l]));
             if (momentum) {
-                TPCHK(hpnn_dev_malloc(&V[l], nw * sizeof(T)));
-                TPCHK(hipMemsetAsync(V[l], 0, nw * sizeof(T), s));
+                HIPCHK(hpnn_dev_malloc(&V[l], nw * sizeof(T)));
+                HIPCHK(hipMemsetAsync(V[l], 0, nw * sizeof(T), s));
             }
             if (l < L - 1) {
-                TPCHK(hpnn_dev_malloc(&Hloc[l], (size_t)n[l] * Bp * sizeof(T)));
-                TPCHK(hpnn_dev_malloc(&Hfull[l], (size_t)P * n[l] * Bp * sizeof(T)));
-                TPCHK(hpnn_dev_malloc(&Dloc[l], (size_t)n[l] * Bp * sizeof(T)));
+                HIPCHK(hpnn_dev_malloc(&Hloc[l], (size_t)n[l] * Bp * sizeof(T)));
+                HIPCHK(hpnn_dev_malloc(&Hfull[l], (size_t)P * n[l] * Bp * sizeof(T)));
+                HIPCHK(hpnn_dev_malloc(&Dloc[l], (size_t)n[l] * Bp * sizeof(T)));
             }
             if (l >= 1 && l < L - 1) part_elems = std::max(part_elems, (size_t)Mp[l] * Bp);
-            std::vector<T> tmp(nw, (T)0);
-            for (int j = 0; j < n[l]; j++) {
-                const int g = grow(l, j);
-                if (g >= Ntrue[l]) continue;
-                for (int m = 0; m < Mtrue[l]; m++) tmp[(size_t)j * Mp[l] + m] = (T)ly->weights[(size_t)g * Mtrue[l] + m];
-            }
-            TPCHK(hipMemcpyAsync(W[l], tmp.data(), nw * sizeof(T), hipMemcpyHostToDevice, s));
-            TPCHK(hipStreamSynchronize(s));
+            if (!put_rows(W[l], ly->weights, l)) return FALSE;
         }
-        TPCHK(hpnn_dev_malloc(&Z, (size_t)Bp * n_out * sizeof(T)));
-        TPCHK(hpnn_dev_malloc(&DL, (size_t)Bp * n_out * sizeof(T)));
-        if (part_elems) TPCHK(hpnn_dev_malloc(&part, part_elems * sizeof(T)));
-        TPCHK(hpnn_dev_malloc(&acc, ACC_BYTES));
-        TPCHK(hipMemsetAsync(acc, 0, ACC_BYTES, s));
+        HIPCHK(hpnn_dev_malloc(&Z, (size_t)Bp * n_out * sizeof(T)));
+        HIPCHK(hpnn_dev_malloc(&DL, (size_t)Bp * n_out * sizeof(T)));
+        if (part_elems) HIPCHK(hpnn_dev_malloc(&part, part_elems * sizeof(T)));
+        HIPCHK(hpnn_dev_malloc(&acc, ACC_BYTES));
+        HIPCHK(hipMemsetAsync(acc, 0, ACC_BYTES, s));
         return TRUE;
     }
 
     BOOL upload_momentum(const kernel_ann *k) {
         if (!k->dw) return TRUE;
-        for (int l = 0; l < L; l++) {
-            if (!V[l]) continue;
-            std::vector<T> tmp((size_t)n[l] * Mp[l], (T)0);
-            for (int j = 0; j < n[l]; j++) {
-                const int g = grow(l, j);
-                if (g >= Ntrue[l]) continue;
-                for (int m = 0; m < Mtrue[l]; m++) tmp[(size_t)j * Mp[l] + m] = (T)k->dw[l][(size_t)g * Mtrue[l] + m];
-            }
-            TPCHK(hipMemcpyAsync(V[l], tmp.data(), tmp.size() * sizeof(T), hipMemcpyHostToDevice, s));
-            TPCHK(hipStreamSynchronize(s));
-        }
+        for (int l = 0; l < L; l++)
+            if (V[l] && !put_rows(V[l], k->dw[l], l)) return FALSE;
         return TRUE;
     }
 
@@ -342,13 +322,13 @@ struct TpNet {
         std::vector<T> h((size_t)n_in * cols, (T)0);
         for (UINT i = 0; i < ns; i++)
             for (int c = 0; c < n_in; c++) h[(size_t)c * cols + i] = (T)X[(size_t)i * n_in + c];
-        TPCHK(hpnn_dev_malloc(&Xt, h.size() * sizeof(T)));
-        TPCHK(hipMemcpyAsync(Xt, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s));
+        HIPCHK(hpnn_dev_malloc(&Xt, h.size() * sizeof(T)));
+        HIPCHK(hipMemcpyAsync(Xt, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s));
         std::vector<T> t((size_t)cols * n_out, (T)0);
         for (size_t i = 0; i < (size_t)ns * n_out; i++) t[i] = (T)Tg[i];
-        TPCHK(hpnn_dev_malloc(&Td, t.size() * sizeof(T)));
-        TPCHK(hipMemcpyAsync(Td, t.data(), t.size() * sizeof(T), hipMemcpyHostToDevice, s));
-        TPCHK(hipStreamSynchronize(s));
+        HIPCHK(hpnn_dev_malloc(&Td, t.size() * sizeof(T)));
+        HIPCHK(hipMemcpyAsync(Td, t.data(), t.size() * sizeof(T), hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
         return TRUE;
     }
     BOOL batch_step(int b, int B, int nv, double lr, double alpha, bool mom) {
@@ -366,22 +346,7 @@ struct TpNet {
     }
     BOOL host_rows(kernel_ann *k, bool mom) { return download_rows(k, r, W, mom ? V : nullptr); }
 
-    BOOL read_stats(double *loss, unsigned int *hits) {
-        std::vector<float> h(ACC_BYTES / 4);
-        TPCHK(hipMemcpyAsync(h.data(), acc, ACC_BYTES, hipMemcpyDeviceToHost, s));
-        TPCHK(hipStreamSynchronize(s));
-        double l = 0.0;
-        unsigned int c = 0;
-        for (int i = 0; i < HPNN_STAT_SLOTS; i++) {
-            l += h[(size_t)i * HPNN_STAT_STRIDE];
-            unsigned int u;
-            memcpy(&u, &h[(size_t)i * HPNN_STAT_STRIDE + 1], 4);
-            c += u;
-        }
-        *loss = l;
-        *hits = c;
-        return TRUE;
-    }
+    BOOL read_stats(double *loss, unsigned int *hits) { return read_stat_slots(acc, s, loss, hits); }
 
     /* every rank's rows of every layer -> the host kernel of this rank (all-gather) */
     BOOL gather_to_host(kernel_ann *k, TpColl<T> &cl, int W_, bool mom) {
@@ -401,7 +366,7 @@ struct TpNet {
                 hpnn_dev_free(full);
                 full = nullptr;
                 if (!ok) break;
-                layer_ann *ly = layer_at(k, l);
+                layer_ann *ly = layer_of(k, l);
                 DOUBLE *dst = pass ? k->dw[l] : ly->weights;
                 const int rows = sh * n[l];
                 for (int g = 0; g < rows && g < Ntrue[l]; g++)
@@ -414,7 +379,7 @@ struct TpNet {
     /* this rank's rows -> the host kernel (rows of other ranks untouched) */
     BOOL download_rows(kernel_ann *k, int rank_rows_of, const T *const *Wsrc, const T *const *Vsrc) {
         for (int l = 0; l < L; l++) {
-            layer_ann *ly = layer_at(k, l);
+            layer_ann *ly = layer_of(k, l);
             const int rr = rank_rows_of;
             const size_t nw = (size_t)n[l] * Mp[l];
             std::vector<T> tmp(nw);
@@ -422,8 +387,8 @@ struct TpNet {
                 const T *src = pass ? (Vsrc ? Vsrc[l] : nullptr) : Wsrc[l];
                 if (!src) continue;
                 DOUBLE *dst = pass ? k->dw[l] : ly->weights;
-                TPCHK(hipMemcpyAsync(tmp.data(), src, nw * sizeof(T), hipMemcpyDeviceToHost, s));
-                TPCHK(hipStreamSynchronize(s));
+                HIPCHK(hipMemcpyAsync(tmp.data(), src, nw * sizeof(T), hipMemcpyDeviceToHost, s));
+                HIPCHK(hipStreamSynchronize(s));
                 for (int j = 0; j < n[l]; j++) {
                     const int g = l < L - 1 ? rr * n[l] + j : j;
                     if (g >= Ntrue[l]) continue;
@@ -492,8 +457,8 @@ struct TpNetBf16 {
             if (g >= Ntrue[l]) continue;
             for (int m = 0; m < Mtrue[l]; m++) tmp[(size_t)j * Mp[l] + m] = (float)src[(size_t)g * Mtrue[l] + m];
         }
-        TPCHK(hipMemcpyAsync(dst, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice, s));
-        TPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipMemcpyAsync(dst, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
         return TRUE;
     }
 
@@ -503,30 +468,30 @@ struct TpNetBf16 {
         L = (int)k->n_hiddens + 1;
         n_out = (int)k->n_outputs;
         No = pad32(n_out);
-        type = t == NN_TYPE_ANN ? 0 : (t == NN_TYPE_LNN ? 1 : 2);
+        type = plan_type(t);
         if (L > 1 + HPNN_UPD_MAX * 2) return FALSE;
         size_t part_elems = 0, stage_b = 0, red = 0;
         for (int l = 0; l < L; l++) {
-            layer_ann *ly = layer_at(k, l);
+            layer_ann *ly = layer_of(k, l);
             Ntrue[l] = (int)ly->n_neurons;
             Mtrue[l] = (int)ly->n_inputs;
             n[l] = l < L - 1 ? pad32((Ntrue[l] + P - 1) / P) : No;
             Mp[l] = l == 0 ? pad32(Mtrue[0]) : P * n[l - 1];
             S[l] = hpnn::BPlan::pick_splits(n[l], Mp[l], Bp);
             const size_t nw = (size_t)n[l] * Mp[l];
-            TPCHK(hpnn_dev_malloc(&W32[l], nw * 4));
-            TPCHK(hpnn_dev_malloc(&Wb[l], nw * 2));
-            TPCHK(hpnn_dev_malloc(&Wt[l], nw * 2));
-            TPCHK(hpnn_dev_malloc(&slab[l], nw * 4 * S[l]));
+            HIPCHK(hpnn_dev_malloc(&W32[l], nw * 4));
+            HIPCHK(hpnn_dev_malloc(&Wb[l], nw * 2));
+            HIPCHK(hpnn_dev_malloc(&Wt[l], nw * 2));
+            HIPCHK(hpnn_dev_malloc(&slab[l], nw * 4 * S[l]));
             if (momentum) {
-                TPCHK(hpnn_dev_malloc(&V32[l], nw * 4));
-                TPCHK(hipMemsetAsync(V32[l], 0, nw * 4, s));
+                HIPCHK(hpnn_dev_malloc(&V32[l], nw * 4));
+                HIPCHK(hipMemsetAsync(V32[l], 0, nw * 4, s));
             }
             if (l < L - 1) {
-                TPCHK(hpnn_dev_malloc(&Hloc[l], (size_t)Bp * n[l] * 2));
-                TPCHK(hpnn_dev_malloc(&Dloc[l], (size_t)Bp * n[l] * 2));
+                HIPCHK(hpnn_dev_malloc(&Hloc[l], (size_t)Bp * n[l] * 2));
+                HIPCHK(hpnn_dev_malloc(&Dloc[l], (size_t)Bp * n[l] * 2));
                 if (P > 1) {
-                    TPCHK(hpnn_dev_malloc(&Hfull[l], (size_t)Bp * P * n[l] * 2));
+                    HIPCHK(hpnn_dev_malloc(&Hfull[l], (size_t)Bp * P * n[l] * 2));
                     stage_b = std::max(stage_b, (size_t)Bp * P * n[l] * 2);
                 } else {
                     Hfull[l] = nullptr; /* the local rows are the whole layer */
@@ -539,15 +504,15 @@ struct TpNetBf16 {
             if (!put_rows(W32[l], ly->weights, l)) return FALSE;
             TPK(hpnn_cast_weights(W32[l], Wb[l], Wt[l], n[l], Mp[l], s), "weight cast");
         }
-        TPCHK(hpnn_dev_malloc(&Z, (size_t)Bp * No * 4));
-        TPCHK(hpnn_dev_malloc(&DL, (size_t)Bp * No * 2));
-        TPCHK(hipMemsetAsync(DL, 0, (size_t)Bp * No * 2, s));
-        if (stage_b) TPCHK(hpnn_dev_malloc(&hstage, stage_b));
-        if (part_elems) TPCHK(hpnn_dev_malloc(&part, part_elems * 4));
-        if (red) TPCHK(hpnn_dev_malloc(&dred, red * 4));
-        TPCHK(hpnn_dev_malloc(&acc, ACC_BYTES));
-        TPCHK(hipMemsetAsync(acc, 0, ACC_BYTES, s));
-        TPCHK(hipStreamSynchronize(s));
+        HIPCHK(hpnn_dev_malloc(&Z, (size_t)Bp * No * 4));
+        HIPCHK(hpnn_dev_malloc(&DL, (size_t)Bp * No * 2));
+        HIPCHK(hipMemsetAsync(DL, 0, (size_t)Bp * No * 2, s));
+        if (stage_b) HIPCHK(hpnn_dev_malloc(&hstage, stage_b));
+        if (part_elems) HIPCHK(hpnn_dev_malloc(&part, part_elems * 4));
+        if (red) HIPCHK(hpnn_dev_malloc(&dred, red * 4));
+        HIPCHK(hpnn_dev_malloc(&acc, ACC_BYTES));
+        HIPCHK(hipMemsetAsync(acc, 0, ACC_BYTES, s));
+        HIPCHK(hipStreamSynchronize(s));
         return TRUE;
     }
 
@@ -569,11 +534,11 @@ struct TpNetBf16 {
             for (int c = 0; c < n_in; c++) h[row * K0 + c] = bf16_rne((float)X[(size_t)i * n_in + c]);
             for (int c = 0; c < n_out; c++) t[row * n_out + c] = (float)Tg[(size_t)i * n_out + c];
         }
-        TPCHK(hpnn_dev_malloc(&X16, h.size() * 2));
-        TPCHK(hipMemcpyAsync(X16, h.data(), h.size() * 2, hipMemcpyHostToDevice, s));
-        TPCHK(hpnn_dev_malloc(&T32, t.size() * 4));
-        TPCHK(hipMemcpyAsync(T32, t.data(), t.size() * 4, hipMemcpyHostToDevice, s));
-        TPCHK(hipStreamSynchronize(s));
+        HIPCHK(hpnn_dev_malloc(&X16, h.size() * 2));
+        HIPCHK(hipMemcpyAsync(X16, h.data(), h.size() * 2, hipMemcpyHostToDevice, s));
+        HIPCHK(hpnn_dev_malloc(&T32, t.size() * 4));
+        HIPCHK(hipMemcpyAsync(T32, t.data(), t.size() * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
         return TRUE;
     }
 
@@ -656,25 +621,10 @@ struct TpNetBf16 {
         for (int l = 0; l < L; l++) st = std::max(st, (size_t)P * n[l] * Mp[l]);
         return st;
     }
-    BOOL read_stats(double *loss, unsigned int *hits) {
-        std::vector<float> h(ACC_BYTES / 4);
-        TPCHK(hipMemcpyAsync(h.data(), acc, ACC_BYTES, hipMemcpyDeviceToHost, s));
-        TPCHK(hipStreamSynchronize(s));
-        double l = 0.0;
-        unsigned int c = 0;
-        for (int i = 0; i < HPNN_STAT_SLOTS; i++) {
-            l += h[(size_t)i * HPNN_STAT_STRIDE];
-            unsigned int u;
-            memcpy(&u, &h[(size_t)i * HPNN_STAT_STRIDE + 1], 4);
-            c += u;
-        }
-        *loss = l;
-        *hits = c;
-        return TRUE;
-    }
+    BOOL read_stats(double *loss, unsigned int *hits) { return read_stat_slots(acc, s, loss, hits); }
     /* rows [rank_rows_of ...] of h ([sh n_l][Mp_l] FP32) -> host weights / momentum of layer l */
     void to_host(kernel_ann *k, int l, bool momentum, const std::vector<float> &h, int rows, int row0) {
-        layer_ann *ly = layer_at(k, l);
+        layer_ann *ly = layer_of(k, l);
         DOUBLE *dst = momentum ? k->dw[l] : ly->weights;
         for (int j = 0; j < rows; j++) {
             const int g = row0 + j;
@@ -688,8 +638,8 @@ struct TpNetBf16 {
                 const float *src = pass ? V32[l] : W32[l];
                 if (!src) continue;
                 std::vector<float> h((size_t)n[l] * Mp[l]);
-                TPCHK(hipMemcpyAsync(h.data(), src, h.size() * 4, hipMemcpyDeviceToHost, s));
-                TPCHK(hipStreamSynchronize(s));
+                HIPCHK(hipMemcpyAsync(h.data(), src, h.size() * 4, hipMemcpyDeviceToHost, s));
+                HIPCHK(hipStreamSynchronize(s));
                 to_host(k, l, pass == 1, h, n[l], l < L - 1 ? r * n[l] : 0);
             }
         return TRUE;
@@ -702,7 +652,7 @@ struct TpNetBf16 {
                 const float *src = pass ? V32[l] : W32[l];
                 if (!src) continue;
                 float *full = nullptr;
-                TPCHK(hpnn_dev_malloc(&full, (size_t)cnt * sh * 4));
+                HIPCHK(hpnn_dev_malloc(&full, (size_t)cnt * sh * 4));
                 bool ok = sh > 1 ? cl.gather_rows(src, full, cnt, s)
                                  : hipMemcpyAsync(full, src, cnt * 4, hipMemcpyDeviceToDevice, s) == hipSuccess;
                 std::vector<float> h((size_t)cnt * sh);
@@ -726,46 +676,25 @@ BOOL run_rank(Net &net, UINT n, const hpnn_batched_opts *o, int B, double *ep_lo
     const int n_batches = (int)((n + B - 1) / B);
     auto epoch = [&]() -> bool {
         for (int b = 0; b < n_batches; b++) {
-            const int nv = (b == n_batches - 1) ? (int)n - b * B : B;
+            int start, nv, total;
+            hpnn_dp_shard(b, B, (int)n, 0, B, &start, &nv, &total);
             if (!net.batch_step(b, B, nv, o->lr, o->alpha, mom)) return false;
         }
         return true;
     };
-    const char *ge = getenv("HPNN_GRAPH");
-    hipGraphExec_t gx = nullptr;
-    if (net.coll->capturable() && !(ge && ge[0] == '0') && !hpnn_debug_enabled() && n_batches <= 4096) {
-        hipGraph_t g = nullptr;
-        bool ok = hipStreamBeginCapture(net.s, hipStreamCaptureModeRelaxed) == hipSuccess;
-        const bool okb = ok && epoch();
-        ok = ok && hipStreamEndCapture(net.s, &g) == hipSuccess && g && okb &&
-             hipGraphInstantiate(&gx, g, nullptr, nullptr, 0) == hipSuccess;
-        if (g) hipGraphDestroy(g);
-        if (!ok) {
-            gx = nullptr;
-            hipGetLastError();
-            NN_DBG(stdout, "tensor-parallel rank %d: epoch not capturable, eager launches\n", net.r);
-        }
-    }
+    GraphExec gx;
+    if (net.coll->capturable() && graphs_enabled() && n_batches <= 4096 && !capture_epoch(net.s, epoch, &gx))
+        NN_DBG(stdout, "tensor-parallel rank %d: epoch not capturable, eager launches\n", net.r);
     for (UINT e = 0; e < o->epochs; e++) {
-        TPCHK(hipMemsetAsync(net.acc, 0, ACC_BYTES, net.s));
-        if (gx) {
-            if (hipGraphLaunch(gx, net.s) != hipSuccess) {
-                hipGraphExecDestroy(gx);
-                return FALSE;
-            }
-        } else if (!epoch()) {
-            return FALSE;
-        }
-        if (!net.read_stats(ep_loss, ep_hits)) {
-            if (gx) hipGraphExecDestroy(gx);
-            return FALSE;
-        }
+        HIPCHK(hipMemsetAsync(net.acc, 0, ACC_BYTES, net.s));
+        if (gx ? hipGraphLaunch(gx.get(), net.s) != hipSuccess : !epoch()) return FALSE;
+        if (!net.read_stats(ep_loss, ep_hits)) return FALSE;
         if (net.r == 0 && hpnn_metrics_active())
             hpnn_metrics_epoch("gpu-tp", o->epoch0 + e + 1, *ep_loss / (double)n, *ep_hits, n, 0.0,
                                (UINT64)n * (e + 1));
     }
-    if (gx) hipGraphExecDestroy(gx);
-    TPCHK(hipStreamSynchronize(net.s));
+    gx.reset();
+    HIPCHK(hipStreamSynchronize(net.s));
     return TRUE;
 }
 
@@ -849,13 +778,7 @@ BOOL train_tp_threads(kernel_ann *k, const DOUBLE *X, const DOUBLE *Tg, UINT n, 
         hipSetDevice(dev[g]);
         ok = nets[g]->host_rows(k, mom);
     }
-    if (ok && st) {
-        st->seconds = std::chrono::duration<double>(t1 - t0).count();
-        st->samples = (UINT64)n * o->epochs;
-        st->epoch_loss = losses[0] / (double)n;
-        st->correct = hits[0];
-        st->last_loss = st->epoch_loss;
-    }
+    if (ok && st) fill_stats(st, std::chrono::duration<double>(t1 - t0).count(), n, o->epochs, losses[0], hits[0]);
     for (int g = 0; g < P; g++) {
         hipSetDevice(dev[g]);
         nets[g].reset();
@@ -874,7 +797,7 @@ BOOL train_tp_mp(kernel_ann *k, const DOUBLE *X, const DOUBLE *Tg, UINT n, const
     typedef typename Net::coll_t T;
     const int W = hpnn_boot_world(), R = hpnn_boot_rank();
     const int dev = hpnn_rt_device(0);
-    TPCHK(hipSetDevice(dev));
+    HIPCHK(hipSetDevice(dev));
     hipStream_t s = hpnn_rt_stream(0, 0);
     if (!hpnn_comm_available()) {
         NN_ERROR(stderr, "tensor parallelism across processes needs RCCL\n");
@@ -911,13 +834,7 @@ BOOL train_tp_mp(kernel_ann *k, const DOUBLE *X, const DOUBLE *Tg, UINT n, const
     if (hpnn_boot_allgather(&okv, sizeof okv, oks.data()) != 0) ok = FALSE;
     for (int v : oks) ok = ok && v;
     if (ok) ok = net.gather_to_host(k, coll, W, mom);
-    if (ok && st) {
-        st->seconds = std::chrono::duration<double>(t1 - t0).count();
-        st->samples = (UINT64)n * o->epochs;
-        st->epoch_loss = loss / (double)n;
-        st->correct = hits;
-        st->last_loss = st->epoch_loss;
-    }
+    if (ok && st) fill_stats(st, std::chrono::duration<double>(t1 - t0).count(), n, o->epochs, loss, hits);
     hipStreamSynchronize(s);
     hpnn_boot_finish();
     hpnn_comm_destroy(comm);
@@ -948,14 +865,7 @@ BOOL train_tp(kernel_ann *k, const DOUBLE *X, const DOUBLE *Tg, UINT n, const hp
 
 extern "C" BOOL hpnn_gpu_train_tp(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, const hpnn_batched_opts *o,
                                   hpnn_batched_stats *st) {
-    if (o->shuffle) {
-        NN_ERROR(stderr, "[shuffle] epoch is not supported by tensor-parallel batched training (one device only)\n");
-        return FALSE;
-    }
-    if (o->validate) {
-        NN_ERROR(stderr, "[validate] is not supported by tensor-parallel batched training (one device only)\n");
-        return FALSE;
-    }
+    if (single_device_only(o, "tensor-parallel")) return FALSE;
     if (o->dtype == NN_DTYPE_F64) return train_tp<TpNet<double>>(k, X, T, n, o, st);
     if (o->dtype == NN_DTYPE_F32) return train_tp<TpNet<float>>(k, X, T, n, o, st);
     return train_tp<TpNetBf16>(k, X, T, n, o, st);

@@ -1,0 +1,238 @@
+/*
+ * libhpnn batched GPU engine -- training on ONE device: the resident sample set, [shuffle]
+ * epoch, [validate] N, the epochs as HIP graph replays and the deferred health readback.
+ */
+#include <algorithm>
+#include <chrono>
+#include <map>
+
+#include "batched_net.h"
+
+using namespace hpnn::eng;
+
+namespace {
+
+template <class Net>
+BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, const hpnn_batched_opts *o,
+                    hpnn_batched_stats *st) {
+    typedef typename Net::target_t TT;
+    if (k->n_hiddens + 1 > 16) return FALSE;
+    hpnn_gpu_sync_host(k);
+    HIPCHK(hipSetDevice(hpnn_rt_device(0)));
+    hipStream_t s = hpnn_rt_stream(0, 0);
+    const int B = (int)(o->batch ? o->batch : 256);
+    const bool mom = o->train == NN_TRAIN_BPM;
+    const int n_in = (int)k->n_inputs, n_out = (int)k->n_outputs;
+    Net net;
+    if (!net.init(k, B, o->type, mom, s, B % 32 == 0)) return FALSE;
+    NN_OUT(stdout, "batched GPU training: %s, %d samples per step\n", Net::name(), B);
+    if (mom && o->resume && !net.upload_momentum(k)) return FALSE;
+    const int n_batches = (int)((n + B - 1) / B);
+    int rows_p = (n_batches - 1) * B + net.Bp; /* last batch reads Bp rows */
+    ResidentSet<TT> tr;
+    if (!tr.upload(net, X, T, n, n_in, n_out, &rows_p, o->type, s)) return FALSE;
+    XSet &xs = tr.xs;
+    TT *const Td = tr.T.get();
+    /* [shuffle] epoch: xs / Td are a staging set; every epoch starts with the permutation of
+     * (n, seed, epochs completed) and the gathers of the canonical row-major copies into it,
+     * all on the compute stream (so inside the captured epoch).  One batch per epoch: the
+     * order only changes the summation order, nothing is reshuffled. */
+    const bool shuffle = o->shuffle && n_batches > 1;
+    if (o->shuffle && !shuffle) NN_OUT(stdout, "batched GPU training: one batch per epoch, no reshuffle\n");
+    ResidentSet<TT> cn;
+    DevBuf<int> perm;
+    DevBuf<unsigned int> shw; /* [0] the epoch word, [1] the permutation kernel's error word */
+    const bool dense = Net::dense_always || !xs.lab;
+    if (shuffle) {
+        NN_OUT(stdout, "batched GPU training: samples reshuffled every epoch\n");
+        const unsigned int w0[2] = {o->epoch0, 0u};
+        if (!net.upload_canon(X, (int)n, n_in, xs, &cn.xs)) return FALSE;
+        HIPCHK(perm.alloc(n));
+        HIPCHK(shw.alloc(2));
+        HIPCHK(hipMemcpy(shw.get(), w0, sizeof w0, hipMemcpyHostToDevice));
+        if (xs.lab) {
+            HIPCHK(hpnn_dev_malloc(&cn.xs.lab, (size_t)n * sizeof(int)));
+            HIPCHK(hipMemcpy(cn.xs.lab, xs.lab, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice));
+        }
+        if (dense) {
+            HIPCHK(cn.T.alloc((size_t)n * n_out));
+            HIPCHK(hipMemcpy(cn.T.get(), Td, (size_t)n * n_out * sizeof(TT), hipMemcpyDeviceToDevice));
+        }
+    }
+    auto reshuffle = [&]() -> bool {
+        unsigned int *w = shw.get();
+        if (hpnn_epoch_perm_dev(perm.get(), (int)n, o->seed, w, w + 1, s) || hpnn_epoch_advance(w, s)) return false;
+        if (!net.gather(cn.xs, xs, perm.get(), (int)n, rows_p)) return false;
+        if (xs.lab && hpnn_gather_rows(xs.lab, cn.xs.lab, perm.get(), (int)n, rows_p, 4, s)) return false;
+        return !dense ||
+               hpnn_gather_rows(Td, cn.T.get(), perm.get(), (int)n, rows_p, (long)n_out * sizeof(TT), s) == 0;
+    };
+    /* [validate] N: the held-out set, uploaded once; a pass = the evaluation launches into the
+     * validation stat slots plus the one-workgroup commit that files them as the next record
+     * of a device history -- all on the compute stream, so inside the captured replay; the host
+     * reads the history once after the last replay (per record with per-epoch metrics) */
+    const bool validate = o->validate && o->Xv && o->Tv && o->nv;
+    const int nval = validate ? (int)o->nv : 0;
+    ResidentSet<TT> va;
+    DevBuf<hpnn_val_record> vhist;
+    DevBuf<unsigned int> vcur;
+    std::vector<UINT> vsched;
+    if (validate) {
+        vsched.resize(hpnn_validation_schedule(o->epoch0, o->epochs, o->validate, nullptr));
+        hpnn_validation_schedule(o->epoch0, o->epochs, o->validate, vsched.data());
+        int vrows = 0;
+        if (!va.upload(net, o->Xv, o->Tv, o->nv, n_in, n_out, &vrows, o->type, s, true)) return FALSE;
+        HIPCHK(vhist.alloc(vsched.size() + 1));
+        HIPCHK(vcur.alloc(1));
+        HIPCHK(hipMemset(vcur.get(), 0, sizeof(unsigned int)));
+        NN_OUT(stdout, "batched GPU training: %d held-out samples validated every %u epochs\n", nval, o->validate);
+    }
+    auto validation = [&]() -> bool {
+        if (net.evaluate(va.xs, va.T.get(), n_out, nval) &&
+            hpnn_validate_commit(net.vacc(), vhist.get(), vcur.get(), (unsigned int)vsched.size(), s) == 0)
+            return true;
+        NN_ERROR(stderr, "batched GPU training: the validation pass could not be launched\n");
+        return false;
+    };
+    auto epoch = [&]() -> bool {
+        if (shuffle && !reshuffle()) {
+            NN_ERROR(stderr, "batched GPU training: the epoch reshuffle could not be launched\n");
+            return false;
+        }
+        for (int b = 0; b < n_batches; b++) {
+            int start, nv, total;
+            hpnn_dp_shard(b, B, (int)n, 0, B, &start, &nv, &total);
+            if (!net.step(xs, start, Td + (size_t)start * n_out, n_out, nv, o->lr, o->alpha, mom)) return false;
+        }
+        return true;
+    };
+    const bool metrics = hpnn_metrics_active() != 0;
+    const int E = (int)o->epochs;
+    /* epoch e of this call (0-based) is followed by a validation pass; with per-epoch metrics
+     * the pass runs eagerly behind the epoch's replay (that loop synchronises every epoch anyway) */
+    auto val_due = [&](int e) { return validate && ((o->epoch0 + e + 1) % o->validate == 0 || e + 1 == E); };
+    /* ne epochs from epoch e0 of the call, back to back; the statistics are zeroed before the
+     * last (the only one read) */
+    auto epochs = [&](int ne, int e0) -> bool {
+        for (int i = 0; i < ne; i++) {
+            if ((i + 1 == ne && hipMemsetAsync(net.acc, 0, Net::ACC_BYTES, s) != hipSuccess) || !epoch()) return false;
+            if (!metrics && val_due(e0 + i) && !validation()) return false;
+        }
+        return true;
+    };
+    /* one graph replays epg epochs (about 32 steps: the host launches once per replay); with
+     * per-epoch metrics every epoch is its own replay followed by a statistics read.  With
+     * [validate] N the replay is a whole number of validation periods where that fits a graph,
+     * so every replay has the same pattern of passes; a graph is keyed by its epochs and the
+     * offsets of its passes (the last replay, shorter or with the closing pass, is another key) */
+    int epg = metrics ? 1 : std::max(1, std::min(E, 32 / std::max(1, n_batches)));
+    if (validate && !metrics && (long)o->validate * n_batches <= 4096)
+        epg = std::min(E, (int)((epg + o->validate - 1) / o->validate * o->validate));
+    auto gkey = [&](int ne, int e0) {
+        std::vector<int> key{ne};
+        for (int i = 0; i < ne && !metrics; i++)
+            if (val_due(e0 + i)) key.push_back(i);
+        return key;
+    };
+    hpnn_preload_code_objects();
+    std::map<std::vector<int>, GraphExec> graphs;
+    if (graphs_enabled() && n_batches <= 4096)
+        for (int e0 = 0; e0 < E; e0 += epg) {
+            const int ne = std::min(epg, E - e0);
+            const std::vector<int> key = gkey(ne, e0);
+            if (graphs.count(key)) continue;
+            if (!capture_epoch(s, [&]() { return epochs(ne, e0); }, &graphs[key]))
+                NN_DBG(stdout, "batched GPU training: epochs not capturable, eager launches\n");
+        }
+    /* setup (data upload and layout conversions) is finished before the clock starts */
+    HIPCHK(hipDeviceSynchronize());
+    auto t0 = std::chrono::steady_clock::now();
+    double ep_loss = 0.0;
+    unsigned int ep_hits = 0;
+    /* the health of every replay (HealthRing), plus a final check after the last replay; word
+     * [3] is the permutation kernel's error word */
+    HealthRing ring;
+    BOOL ok = ring.ok();
+    int pend = -1, slot = 0;
+    auto judge = [&](int sl) -> bool {
+        const unsigned int *d = ring.judge(sl);
+        if (!d || !net.health_ok(d)) return false;
+        if (d[3] == 0) return true;
+        NN_ERROR(stderr, "batched GPU training: the epoch permutation did not terminate within its bound; stopping\n");
+        return false;
+    };
+    std::vector<hpnn_val_record> vrec(vsched.size());
+    size_t vdone = 0;
+    for (int e = 0; e < E && ok;) {
+        const int ne = std::min(epg, E - e);
+        auto g = graphs.find(gkey(ne, e));
+        ok = (g != graphs.end() && g->second) ? hipGraphLaunch(g->second.get(), s) == hipSuccess : epochs(ne, e);
+        e += ne;
+        if (ok)
+            ok = ring.post(slot, s, net, [&](unsigned int *d) {
+                return !shuffle || hipMemcpyAsync(d + 3, shw.get() + 1, 4, hipMemcpyDeviceToHost, s) == hipSuccess;
+            });
+        if (ok && pend >= 0) ok = judge(pend);
+        pend = ok ? slot : -1;
+        slot ^= 1;
+        if (ok && (metrics || e == E)) {
+            ok = judge(pend); /* statistics read = a synchronisation anyway: judge this replay now */
+            pend = -1;
+            if (ok) ok = net.read_stats(&ep_loss, &ep_hits);
+        }
+        if (ok && metrics)
+            hpnn_metrics_epoch("gpu", o->epoch0 + e, ep_loss / (double)n, ep_hits, n,
+                               std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(),
+                               (UINT64)n * e);
+        if (ok && metrics && val_due(e - 1) && vdone < vrec.size()) {
+            ok = validation() && hipMemcpyAsync(&vrec[vdone], vhist.get() + vdone, sizeof(hpnn_val_record),
+                                                hipMemcpyDeviceToHost, s) == hipSuccess &&
+                 hipStreamSynchronize(s) == hipSuccess;
+            if (ok)
+                hpnn_metrics_validation("gpu", o->epoch0 + e, vrec[vdone].loss_sum / (double)nval, vrec[vdone].hits,
+                                        (UINT)nval);
+            vdone++;
+        }
+    }
+    if (ok && pend >= 0) ok = judge(pend);
+    auto t1 = std::chrono::steady_clock::now();
+    if (ok && validate && !metrics) {
+        /* the whole history, once; the cursor tells how many passes were filed */
+        unsigned int filed = 0;
+        ok = hipMemcpy(&filed, vcur.get(), sizeof filed, hipMemcpyDeviceToHost) == hipSuccess &&
+             hipMemcpy(vrec.data(), vhist.get(), vrec.size() * sizeof(hpnn_val_record), hipMemcpyDeviceToHost) ==
+                 hipSuccess;
+        if (ok && filed != vrec.size()) {
+            NN_ERROR(stderr, "batched GPU training: %u validation records filed, %zu scheduled\n", filed, vrec.size());
+            ok = FALSE;
+        }
+        vdone = vrec.size();
+    }
+    graphs.clear();
+    if (ok) ok = net.download(k);
+    if (ok && st) {
+        fill_stats(st, std::chrono::duration<double>(t1 - t0).count(), n, o->epochs, ep_loss, ep_hits);
+        st->val = NULL;
+        st->n_val = (UINT)vrec.size();
+        if (!vrec.empty()) {
+            st->val = (hpnn_validation_record *)malloc(vrec.size() * sizeof(hpnn_validation_record));
+            if (!st->val) ok = FALSE;
+            for (size_t i = 0; ok && i < vrec.size(); i++) {
+                st->val[i].epoch = vsched[i];
+                st->val[i].loss = vrec[i].loss_sum / (double)nval;
+                st->val[i].correct = vrec[i].hits;
+                st->val[i].n = (UINT)nval;
+            }
+        }
+    }
+    /* device FP64 copy of the online engine (if any) is now stale */
+    hpnn_gpu_mark_host_dirty(k);
+    return ok;
+}
+
+}  // namespace
+
+BOOL hpnn::eng::train_single(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, const hpnn_batched_opts *o,
+                             hpnn_batched_stats *st) {
+    return with_net(o->dtype, [&](auto t) { return train_single_t<typename decltype(t)::type>(k, X, T, n, o, st); });
+}

@@ -1,4 +1,4 @@
-"""One orchestrator: train_nn's batched BF16 engine (gpu_engine.cpp, C) and
+"""One orchestrator: train_nn's batched BF16 engine (train_single.cpp, C) and
 hpnn_amd.models.MLP (Python) drive the SAME plan (csrc/gpu/bplan.h) -- same step structure,
 split counts and kernels -- so three minibatch steps give the same weights bit for bit.
 Reference entry point being replaced: tests/train_nn.c:232 -> nn_train_kernel

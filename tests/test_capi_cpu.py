@@ -185,7 +185,7 @@ def test_capi_python_binding(tmp_path):
 
 
 def test_online_slot_plan():
-    """online slot layout (gpu_engine.cpp hpnn_online_slot_plan): slots span several GPUs only
+    """online slot layout (online_engine.cpp hpnn_online_slot_plan): slots span several GPUs only
     under the P2P memory model (the exchange buffer lives on GPU 0 and the other GPUs' kernels
     access it directly); -S and HPNN_ONLINE_SLOTS are capped at 2 slots per device, and -S is a no-op on one
     device (two slots there measured slower, profiles/r4/a_online_engine.jsonl)."""
@@ -212,3 +212,44 @@ def test_online_slot_plan():
     assert plan(1, 2, NONE) == (1, 1)
     assert plan(1, 1, NONE, env=2) == (2, 2)
     assert plan(8, 1, P2P, env=6) == (2, 2)  # virtual slots on device 0, capped
+
+
+def test_dp_shard():
+    """data-parallel shard arithmetic (batched_engine.cpp hpnn_dp_shard, the one copy every batched
+    driver uses): sample i of global minibatch b goes to rank (i - b B) // Bg, Bg = ceil(B / W).
+    Against that brute-force assignment: the ranks' ranges are disjoint, in rank order and tile
+    the minibatch exactly; total is the minibatch's sample count; one rank takes it whole."""
+    import ctypes
+    from hpnn_amd._lib import lib_path
+    lib = ctypes.CDLL(lib_path())
+    f = lib.hpnn_dp_shard
+    f.restype = None
+    start, nv, total = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+
+    def shard(b, B, n, rank, Bg):
+        f(b, B, n, rank, Bg, ctypes.byref(start), ctypes.byref(nv), ctypes.byref(total))
+        return start.value, nv.value, total.value
+
+    for n in range(1, 71):
+        for B in (1, 7, 32, 64):
+            n_batches = (n + B - 1) // B
+            for W in range(1, 6):
+                Bg = (B + W - 1) // W
+                for b in range(n_batches):
+                    end = min(b * B + B, n)
+                    owner = {i: (i - b * B) // Bg for i in range(b * B, end)}  # brute force
+                    nxt, tot = b * B, 0
+                    for r in range(W):
+                        s, v, t = shard(b, B, n, r, Bg)
+                        mine = [i for i in range(b * B, end) if owner[i] == r]
+                        assert 0 <= v <= Bg
+                        assert list(range(s, s + v)) == mine, (n, B, W, b, r)
+                        if v:  # in rank order, nothing skipped, nothing twice
+                            assert s == nxt
+                            nxt = s + v
+                        assert t == end - b * B
+                        tot += v
+                    assert nxt == end and tot == end - b * B, (n, B, W, b)
+                    if W == 1:
+                        last = b == n_batches - 1
+                        assert shard(b, B, n, 0, B)[1] == (n - b * B if last else B)

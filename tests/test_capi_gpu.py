@@ -89,7 +89,7 @@ def test_run_nn_gpu(tmp_path):
 @pytest.mark.parametrize("dp_env", [{"HPNN_LOOPBACK_RANKS": "2"}, {"HPNN_LOOPBACK_RANKS": "3"},
                                     {"HPNN_FORCE_RCCL": "1"}])
 def test_batched_data_parallel_matches_single(tmp_path, shape, dtype, dp_env):
-    """native data-parallel path (csrc/gpu/gpu_engine.cpp train_dp): replicas each take a
+    """native data-parallel path (csrc/gpu/train_dp.cpp): replicas each take a
     shard of every minibatch, gradients are summed (loopback: virtual replicas on one GPU;
     HPNN_FORCE_RCCL: a real 1-GPU RCCL communicator) -> same training as one replica."""
     if shape == "fused":

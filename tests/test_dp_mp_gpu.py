@@ -1,4 +1,4 @@
-"""Native multi-process data parallelism of train_nn (csrc/gpu/gpu_engine.cpp::train_dp_mp):
+"""Native multi-process data parallelism of train_nn (csrc/gpu/train_dp_mp.cpp):
 two train_nn processes launched like `torchrun --no-python` would (RANK / WORLD_SIZE /
 LOCAL_RANK / LOCAL_WORLD_SIZE), both on the box's single MI355X, exchanging gradients
 through the one-shot xGMI all-reduce and their bootstrap data through files -- the
