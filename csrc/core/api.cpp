@@ -19,7 +19,7 @@
  *                                  rejected instead of indexing past the end)
  *   nn_run_kernel                 :1306-1536
  * Extensions: [mode] online|batched, [dtype], [device], [batch], [epochs], [shuffle], [validate],
- * [lr], [momentum] conf keys; batched training on CPU (FP64) or GPU.
+ * [keep_best], [patience], [lr], [momentum] conf keys; batched training on CPU (FP64) or GPU.
  */
 #include <libhpnn/ann.h>
 #include <ctype.h>
@@ -133,6 +133,22 @@ extern "C" UINT _NN(get, validation)(nn_def *c, UINT max, UINT *epoch, DOUBLE *l
         if (n) n[i] = r[i].n;
     }
     return r ? c->n_validation : 0;
+}
+extern "C" void _NN(set, keep_best)(nn_def *c, nn_keep_best v) {
+    c->keep_best = (v == NN_KEEP_LOSS || v == NN_KEEP_ACC) ? v : NN_KEEP_OFF;
+}
+extern "C" void _NN(get, keep_best)(nn_def *c, nn_keep_best *v) { *v = c->keep_best; }
+extern "C" nn_keep_best _NN(return, keep_best)(nn_def *c) { return c->keep_best; }
+extern "C" void _NN(set, patience)(nn_def *c, UINT v) { c->patience = v; }
+extern "C" void _NN(get, patience)(nn_def *c, UINT *v) { *v = c->patience; }
+extern "C" UINT _NN(return, patience)(nn_def *c) { return c->patience; }
+extern "C" BOOL _NN(get, best)(nn_def *c, UINT *epoch, DOUBLE *loss, UINT *correct, UINT *n) {
+    if (!c || !c->best_epoch) return FALSE;
+    if (epoch) *epoch = c->best_epoch;
+    if (loss) *loss = c->best_loss;
+    if (correct) *correct = c->best_correct;
+    if (n) *n = c->best_n;
+    return TRUE;
 }
 extern "C" void _NN(set, device)(nn_def *c, nn_device d) { c->device = d; }
 extern "C" nn_device _NN(return, device)(nn_def *c) { return c->device; }
@@ -264,6 +280,17 @@ extern "C" nn_def *_NN(load, conf)(const CHAR *filename) {
             if (v.empty() || !isdigit((unsigned char)v[0]) || every == 0 || every > 0xffffffffUL)
                 CONF_FAIL("[validate] value: %s (epochs between validation passes, >= 1)\n", v.c_str());
             conf->validate = (UINT)every;
+        } else if (is("keep_best")) {
+            std::string u = v;
+            for (auto &ch : u) ch = (char)tolower(ch);
+            if (u == "loss") conf->keep_best = NN_KEEP_LOSS;
+            else if (u == "acc") conf->keep_best = NN_KEEP_ACC;
+            else CONF_FAIL("[keep_best] unknown: %s (loss | acc)\n", v.c_str());
+        } else if (is("patience")) {
+            const unsigned long passes = strtoul(v.c_str(), NULL, 10);
+            if (v.empty() || !isdigit((unsigned char)v[0]) || passes == 0 || passes > 0xffffffffUL)
+                CONF_FAIL("[patience] value: %s (validation passes without improvement, >= 1)\n", v.c_str());
+            conf->patience = (UINT)passes;
         } else if (is("device")) {
             std::string u = v;
             for (auto &ch : u) ch = (char)tolower(ch);
@@ -342,6 +369,8 @@ extern "C" void _NN(dump, conf)(nn_def *conf, FILE *fp) {
     }
     if (conf->shuffle == NN_SHUFFLE_EPOCH) _OUT(fp, "[shuffle] epoch\n");
     if (conf->validate) _OUT(fp, "[validate] %u\n", conf->validate);
+    if (conf->keep_best) _OUT(fp, "[keep_best] %s\n", conf->keep_best == NN_KEEP_ACC ? "acc" : "loss");
+    if (conf->patience) _OUT(fp, "[patience] %u\n", conf->patience);
     if (conf->lr > 0) _OUT(fp, "[lr] %.17g\n", conf->lr);
     if (conf->momentum >= 0) _OUT(fp, "[momentum] %.17g\n", conf->momentum);
 }
@@ -550,6 +579,15 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
         free(conf->validation);
         conf->validation = NULL;
         conf->n_validation = 0;
+        conf->best_epoch = 0;
+        if (conf->keep_best && !conf->validate) {
+            NN_ERROR(stderr, "[keep_best] needs [validate] N: there is no validation pass to keep the best of\n");
+            return FALSE;
+        }
+        if (conf->patience && !conf->keep_best) {
+            NN_ERROR(stderr, "[patience] needs [keep_best] loss | acc: the metric that has to improve\n");
+            return FALSE;
+        }
         if (conf->validate) {
             HpnnSamples vsrc;
             if (!conf->tests || !vsrc.open(conf->tests)) {
@@ -583,6 +621,8 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
         o.Xv = nv ? Xv.data() : NULL;
         o.Tv = nv ? Tv.data() : NULL;
         o.nv = nv;
+        o.keep_best = (UINT)conf->keep_best;
+        o.patience = conf->patience;
         UINT ng = 1;
         _NN(get, n_gpu)(&ng);
         o.n_gpu = ng ? ng : 1;
@@ -598,7 +638,16 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
             ok = gpu ? hpnn_gpu_train_batched(k, X.data(), T.data(), n, &o, &st)
                      : hpnn_cpu_train_batched(k, X.data(), T.data(), n, &o, &st);
         }
-        if (ok) {
+        if (ok && conf->keep_best && st.best_epoch) {
+            /* the kernel is the one of the best pass's epoch: the progress is that epoch's too */
+            conf->samples_seen += (UINT64)n * (st.best_epoch - conf->epochs_done);
+            conf->epochs_done = st.best_epoch;
+        } else if (ok && conf->keep_best) {
+            NN_WARN(stderr, "[keep_best]: no validation pass could be taken (every loss a NaN); "
+                            "the weights after the last epoch run are returned\n");
+            conf->epochs_done += st.epochs_run;
+            conf->samples_seen += (UINT64)n * st.epochs_run;
+        } else if (ok) {
             conf->epochs_done += conf->epochs;
             conf->samples_seen += st.samples;
         }
@@ -608,6 +657,32 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
         for (UINT i = 0; ok && i < st.n_val; i++)
             NN_OUT(stdout, "VALIDATION: epoch %u loss=%.10f acc=%u/%u\n", st.val[i].epoch, st.val[i].loss,
                    st.val[i].correct, st.val[i].n);
+        if (ok && conf->keep_best && st.best_epoch && st.best_index < st.n_val) {
+            const hpnn_validation_record &b = st.val[st.best_index];
+            conf->best_epoch = b.epoch;
+            conf->best_loss = b.loss;
+            conf->best_correct = b.correct;
+            conf->best_n = b.n;
+            NN_OUT(stdout, "BEST: epoch %u loss=%.10f acc=%u/%u\n", b.epoch, b.loss, b.correct, b.n);
+            if (hpnn_metrics_active()) {
+                char buf[256];
+                snprintf(buf, sizeof buf,
+                         "\"engine\": \"%s\", \"epoch\": %u, \"loss\": %.17g, \"correct\": %u, \"n\": %u, "
+                         "\"metric\": \"%s\"",
+                         gpu ? "gpu" : "cpu", b.epoch, b.loss, b.correct, b.n,
+                         conf->keep_best == NN_KEEP_ACC ? "acc" : "loss");
+                hpnn_metrics_emit("best", buf);
+            }
+        }
+        if (ok && st.stop_epoch) {
+            NN_OUT(stdout, "EARLY STOP: epoch %u (no improvement in %u passes)\n", st.stop_epoch, conf->patience);
+            if (hpnn_metrics_active()) {
+                char buf[128];
+                snprintf(buf, sizeof buf, "\"engine\": \"%s\", \"epoch\": %u, \"patience\": %u", gpu ? "gpu" : "cpu",
+                         st.stop_epoch, conf->patience);
+                hpnn_metrics_emit("early_stop", buf);
+            }
+        }
         if (ok) {
             conf->validation = st.val;
             conf->n_validation = st.n_val;
@@ -631,6 +706,16 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
         static bool warned_v = false; /* no epochs here to validate between */
         if (!warned_v) NN_WARN(stderr, "[validate] has no effect in online mode (ignored)\n");
         warned_v = true;
+    }
+    if (conf->keep_best) {
+        static bool warned_k = false; /* no validation pass here */
+        if (!warned_k) NN_WARN(stderr, "[keep_best] has no effect in online mode (ignored)\n");
+        warned_k = true;
+    }
+    if (conf->patience) {
+        static bool warned_p = false;
+        if (!warned_p) NN_WARN(stderr, "[patience] has no effect in online mode (ignored)\n");
+        warned_p = true;
     }
     if (conf->shuffle == NN_SHUFFLE_EPOCH) {
         static bool warned = false; /* no epochs here: every sample is trained to convergence once */

@@ -154,7 +154,7 @@ extern "C" UINT hpnn_validation_schedule(UINT epoch0, UINT epochs, UINT validate
 /* [validate]: forward only over the held-out set with the current weights (FP64; the oracle of
  * the GPU engines' validation pass): mean loss per sample and argmax hits (first maximum) */
 static void cpu_validate(kernel_ann *k, nn_type type, const DOUBLE *X, const DOUBLE *T, UINT n,
-                         hpnn_validation_record *r) {
+                         hpnn_validation_record *r, DOUBLE *loss_sum) {
     DOUBLE sum = 0.0;
     UINT hits = 0;
     for (UINT s = 0; s < n; s++) {
@@ -172,6 +172,7 @@ static void cpu_validate(kernel_ann *k, nn_type type, const DOUBLE *X, const DOU
     r->loss = sum / (DOUBLE)n;
     r->correct = hits;
     r->n = n;
+    if (loss_sum) *loss_sum = sum;
 }
 
 extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n,
@@ -199,10 +200,20 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
     const DOUBLE *Xe = shuffle ? Xs.data() : X, *Te = shuffle ? Ts.data() : T;
     const bool validate = o->validate && o->Xv && o->Tv && o->nv;
     std::vector<hpnn_validation_record> val;
+    /* [keep_best] / [patience] (the oracle of the GPU engines' device-side form, kernels_best.hip):
+     * the rule and the counters on the pass's loss sum and hits; the snapshot is a host copy of
+     * the weights and the momentum; training stops at the stopping pass */
+    const bool keep = validate && o->keep_best != 0;
+    const UINT L = k->n_hiddens + 1;
+    auto layer = [&](UINT l) { return l + 1 < L ? &k->hiddens[l] : &k->output; };
+    std::vector<std::vector<DOUBLE>> bestW, bestV;
+    bool have_best = false, stop = false;
+    DOUBLE best_sum = 0.0;
+    UINT best_hits = 0, best_index = 0, stale = 0, epochs_run = 0;
     auto t0 = std::chrono::steady_clock::now();
     UINT64 samples = 0;
     DOUBLE last = 0.0;
-    for (UINT e = 0; e < o->epochs; e++) {
+    for (UINT e = 0; e < o->epochs && !stop; e++) {
         DOUBLE acc = 0.0;
         UINT nb = 0, hits = 0;
         if (shuffle) {
@@ -227,10 +238,29 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
         if (validate && ((o->epoch0 + e + 1) % o->validate == 0 || e + 1 == o->epochs)) {
             hpnn_validation_record r;
             r.epoch = o->epoch0 + e + 1;
-            cpu_validate(k, o->type, o->Xv, o->Tv, o->nv, &r);
+            DOUBLE sum = 0.0;
+            cpu_validate(k, o->type, o->Xv, o->Tv, o->nv, &r, &sum);
             hpnn_metrics_validation("cpu", r.epoch, r.loss, r.correct, r.n);
             val.push_back(r);
+            if (keep && hpnn_best_improves((int)o->keep_best, have_best, sum, r.correct, best_sum, best_hits)) {
+                have_best = true;
+                best_sum = sum;
+                best_hits = r.correct;
+                best_index = (UINT)val.size() - 1;
+                stale = 0;
+                bestW.resize(L);
+                bestV.resize(mom ? L : 0);
+                for (UINT l = 0; l < L; l++) {
+                    const size_t nw = (size_t)layer(l)->n_neurons * layer(l)->n_inputs;
+                    bestW[l].assign(layer(l)->weights, layer(l)->weights + nw);
+                    if (mom) bestV[l].assign(k->dw[l], k->dw[l] + nw);
+                }
+            } else if (keep) {
+                stale++;
+            }
+            if (keep && o->patience && stale == o->patience) stop = true;
         }
+        epochs_run = e + 1;
     }
     auto t1 = std::chrono::steady_clock::now();
     if (st) {
@@ -251,6 +281,10 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
             correct += (g == tr);
         }
         st->correct = correct;
+        st->epochs_run = epochs_run;
+        st->best_epoch = have_best ? val[best_index].epoch : 0;
+        st->best_index = best_index;
+        st->stop_epoch = stop ? val.back().epoch : 0;
         st->val = NULL;
         st->n_val = (UINT)val.size();
         if (!val.empty()) {
@@ -258,6 +292,11 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
             if (!st->val) return FALSE;
             memcpy(st->val, val.data(), val.size() * sizeof(val[0]));
         }
+    }
+    /* [keep_best]: the kernel as it was after the best pass's epoch */
+    for (UINT l = 0; have_best && l < L; l++) {
+        memcpy(layer(l)->weights, bestW[l].data(), bestW[l].size() * sizeof(DOUBLE));
+        if (mom) memcpy(k->dw[l], bestV[l].data(), bestV[l].size() * sizeof(DOUBLE));
     }
     /* the momentum stays in k->dw: nn_dump_state saves it for an exact resume */
     return TRUE;

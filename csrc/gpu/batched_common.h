@@ -168,6 +168,38 @@ struct ResidentSet {
     }
 };
 
+/* [keep_best]: the snapshot of a net's masters (FP32 / T weights and, with BPM, the momentum) in
+ * one allocation beside them, the device segment table hpnn_snapshot_if copies by, and the best
+ * state hpnn_best_commit keeps; dst[i] is the copy of source i */
+struct BestSnap {
+    DevBuf<char> mem;
+    DevBuf<hpnn_snap_seg> table;
+    DevBuf<hpnn_best_state> state;
+    std::vector<hpnn_snap_seg> segs;
+    std::vector<void *> dst;
+    BOOL init(const std::vector<std::pair<const void *, size_t>> &src, hipStream_t s) {
+        size_t total = 0;
+        for (const auto &p : src) total += (p.second + 255) / 256 * 256;
+        HIPCHK(mem.alloc(total ? total : 256));
+        HIPCHK(table.alloc(src.size() ? src.size() : 1));
+        HIPCHK(state.alloc(1));
+        HIPCHK(hipMemsetAsync(state.get(), 0, sizeof(hpnn_best_state), s));
+        size_t off = 0;
+        for (const auto &p : src) {
+            segs.push_back({p.first, mem.get() + off, (unsigned long long)p.second});
+            dst.push_back(mem.get() + off);
+            off += (p.second + 255) / 256 * 256;
+        }
+        if (hpnn_snapshot_table(table.get(), segs.data(), (int)segs.size(), s)) {
+            NN_ERROR(stderr, "[keep_best]: the snapshot table was refused (alignment or too many layers)\n");
+            return FALSE;
+        }
+        return hpnn_best_preload(s) == 0;
+    }
+    unsigned int *take() const { return &state.get()->take; }
+    unsigned int *stop() const { return &state.get()->stop; }
+};
+
 /* data-parallel step over RCCL: one bucket per layer goes into an async all-reduce on the
  * communicator's side stream as soon as it is final (last layer first), so it overlaps the
  * backward of the layers below; the update waits on a join.  ok_so_far = false: this replica

@@ -320,13 +320,26 @@ struct Batched {
     }
 
     /* FP32 master weights (and BPM momentum, into k->dw) -> host FP64 */
-    BOOL download(kernel_ann *k) {
+    BOOL download(kernel_ann *k) { return download_from(k, nullptr); }
+    /* [keep_best]: the buffers a snapshot copies, per layer the masters then the momentum;
+     * download_from reads copies of them in that order (null: the live ones) */
+    std::vector<std::pair<const void *, size_t>> masters() const {
+        std::vector<std::pair<const void *, size_t>> v;
+        for (int l = 0; l < L; l++)
+            for (const float *b : {p.W32[l], p.V32[l]})
+                if (b) v.push_back({b, (size_t)p.Np[l] * p.Kp[l] * 4});
+        return v;
+    }
+    BOOL download_from(kernel_ann *k, void *const *src) {
         HIPCHK(hipStreamSynchronize(s));
         if (p.V32[0]) ann_momentum_init(k);
-        for (int l = 0; l < L; l++) {
+        for (int l = 0, i = 0; l < L; l++) {
             layer_ann *ly = layer_of(k, l);
-            if (!unpad(ly->weights, p.W32[l], ly, l)) return FALSE;
-            if (p.V32[l] && !unpad(k->dw[l], p.V32[l], ly, l)) return FALSE;
+            if (!unpad(ly->weights, src ? (const float *)src[i] : p.W32[l], ly, l)) return FALSE;
+            i++;
+            if (!p.V32[l]) continue;
+            if (!unpad(k->dw[l], src ? (const float *)src[i] : p.V32[l], ly, l)) return FALSE;
+            i++;
         }
         return TRUE;
     }
@@ -599,17 +612,28 @@ struct BatchedFP {
     bool has_dpx() const { return false; }
     void detach_dpx() {}
 
-    BOOL download(kernel_ann *k) {
+    BOOL download(kernel_ann *k) { return download_from(k, nullptr); }
+    /* [keep_best]: as Batched::masters / download_from (unpadded, any shape) */
+    std::vector<std::pair<const void *, size_t>> masters() const {
+        std::vector<std::pair<const void *, size_t>> v;
+        for (int l = 0; l < L; l++)
+            for (const T *b : {W[l], V[l]})
+                if (b) v.push_back({b, (size_t)N[l] * M[l] * sizeof(T)});
+        return v;
+    }
+    BOOL download_from(kernel_ann *k, void *const *src) {
         HIPCHK(hipStreamSynchronize(s));
         if (V[0]) ann_momentum_init(k);
-        for (int l = 0; l < L; l++) {
+        for (int l = 0, j = 0; l < L; l++) {
             layer_ann *ly = layer_of(k, l);
             const size_t nw = (size_t)N[l] * M[l];
             std::vector<T> tmp(nw);
-            HIPCHK(hipMemcpy(tmp.data(), W[l], nw * sizeof(T), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(tmp.data(), src ? (const T *)src[j] : W[l], nw * sizeof(T), hipMemcpyDeviceToHost));
+            j++;
             for (size_t i = 0; i < nw; i++) ly->weights[i] = (DOUBLE)tmp[i];
             if (!V[l]) continue;
-            HIPCHK(hipMemcpy(tmp.data(), V[l], nw * sizeof(T), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(tmp.data(), src ? (const T *)src[j] : V[l], nw * sizeof(T), hipMemcpyDeviceToHost));
+            j++;
             for (size_t i = 0; i < nw; i++) k->dw[l][i] = (DOUBLE)tmp[i];
         }
         return TRUE;

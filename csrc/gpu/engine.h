@@ -60,6 +60,11 @@ typedef struct {
     const DOUBLE *Tv;
     UINT nv;
     UINT validate;
+    /* [keep_best] loss | acc (nn_keep_best; 0: off): the call returns the weights and momentum of
+     * its best validation pass; [patience] P (0: never): stop once P passes in a row have not
+     * improved.  Both need validate > 0 (single-device engines). */
+    UINT keep_best;
+    UINT patience;
 } hpnn_batched_opts;
 
 /* one validation pass: the absolute epoch it followed, the mean loss per sample and the argmax
@@ -80,7 +85,24 @@ typedef struct {
     /* [validate]: n_val records in epoch order, malloc'ed by the engine (the caller frees val) */
     hpnn_validation_record *val;
     UINT n_val;
+    /* [keep_best]: the absolute epoch of the best pass (0: none was taken) and its index in val;
+     * the epochs the call ran (after a stop the GPU engine may have run some past the stopping
+     * pass: they change nothing that is returned); [patience]: the absolute epoch of the
+     * stopping pass (0: no stop), always val[n_val - 1].epoch */
+    UINT best_epoch;
+    UINT best_index;
+    UINT epochs_run;
+    UINT stop_epoch;
 } hpnn_batched_stats;
+
+/* the improvement rule of [keep_best] (one definition for every engine; the device form is
+ * hpnn_best_commit): does a pass with (loss_sum, hits) improve on the best one so far? */
+static inline int hpnn_best_improves(int metric, int have_best, double loss_sum, unsigned int hits,
+                                     double best_loss_sum, unsigned int best_hits) {
+    if (!have_best) return metric == 2 /* NN_KEEP_ACC */ || loss_sum == loss_sum;
+    if (metric == 2) return hits > best_hits || (hits == best_hits && loss_sum < best_loss_sum);
+    return loss_sum < best_loss_sum;
+}
 
 /* the epochs (absolute numbers, ascending) a call of `epochs` epochs after `epoch0` completed
  * ones validates at; out may be NULL; returns the count */

@@ -340,6 +340,41 @@ typedef struct {
 int hpnn_argmax_rows(const float *Z, int ldz, int n_out, int rows, int n_valid, int *guess, hipStream_t stream);
 int hpnn_validate_commit(float *slots, hpnn_val_record *hist, unsigned int *cursor, unsigned int cap,
                          hipStream_t stream);
+/* ---- keep the best validation pass (kernels_best.hip; [keep_best], [patience]) ----
+ * best_commit: one thread, capturable, behind hpnn_validate_commit on the same stream: judges
+ * hist[*cursor - 1] against the best record so far (metric HPNN_BEST_LOSS: a smaller loss sum;
+ * HPNN_BEST_ACC: more hits, the loss breaking ties; nothing is best before the first pass, a
+ * NaN loss is never taken under LOSS, ties do not improve) and sets state->take for this pass.
+ * An improving pass zeroes stale, any other adds one; patience > 0: the pass at which stale ==
+ * patience sets stop, after which the state is frozen (take = 0).  cursor == 0: a no-op. */
+typedef struct {
+    double loss_sum;
+    unsigned int hits, index, stale, stop, valid, take;
+} hpnn_best_state;
+#define HPNN_BEST_LOSS 1
+#define HPNN_BEST_ACC 2
+int hpnn_best_commit(const hpnn_val_record *hist, const unsigned int *cursor, hpnn_best_state *state, int metric,
+                     unsigned int patience, hipStream_t stream);
+/* snapshot_if: one capturable launch that copies every segment of a DEVICE table {src, dst,
+ * bytes} (n_segs <= HPNN_SNAP_MAX_SEGS) when the device word *take, read when the launch runs,
+ * is not 0, and returns at once when it is 0; writes nothing outside [dst, dst + bytes).  bytes: any multiple of
+ * 4; src / dst 16-byte aligned.  hpnn_snapshot_table checks a host table (-1: a pointer is not
+ * aligned, a size no multiple of 4, too many segments; nothing is written) and copies it to the
+ * device table `segs` (16-byte aligned; synchronises: setup, not for a capture).  The launch
+ * itself checks segs / take and skips a segment that breaks the rules.  Neither launch
+ * allocates, copies or synchronises. */
+typedef struct {
+    const void *src;
+    void *dst;
+    unsigned long long bytes;
+} hpnn_snap_seg;
+#define HPNN_SNAP_MAX_SEGS 32
+int hpnn_snapshot_table(hpnn_snap_seg *segs, const hpnn_snap_seg *host_segs, int n_segs, hipStream_t stream);
+int hpnn_snapshot_if(const hpnn_snap_seg *segs, int n_segs, const unsigned int *take, hipStream_t stream);
+/* an empty one-thread launch of kernels_best.hip (capturable), and the same followed by a
+ * synchronise: loads the unit's code object before a capture */
+int hpnn_best_empty_launch(hipStream_t stream);
+int hpnn_best_preload(hipStream_t stream);
 /* profiling (HPNN_TILE_TRACE=1): per-workgroup s_memtime stamps [1024][12] */
 int hpnn_mlp3_tile_trace(unsigned long long *out);
 /* HPNN_G0_TRACE=1 phase stamps of the fused G0 launch: out[512][8] */

@@ -1,6 +1,7 @@
 /*
  * libhpnn batched GPU engine -- training on ONE device: the resident sample set, [shuffle]
- * epoch, [validate] N, the epochs as HIP graph replays and the deferred health readback.
+ * epoch, [validate] N, [keep_best] / [patience], the epochs as HIP graph replays and the
+ * deferred health readback.
  */
 #include <algorithm>
 #include <chrono>
@@ -87,9 +88,26 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
         HIPCHK(hipMemset(vcur.get(), 0, sizeof(unsigned int)));
         NN_OUT(stdout, "batched GPU training: %d held-out samples validated every %u epochs\n", nval, o->validate);
     }
+    /* [keep_best]: behind the commit a one-thread launch judges the record just filed against
+     * the best so far and sets a device flag, and one more launch copies the masters (and the
+     * momentum) into the snapshot when the flag is set -- both part of the captured replay, so
+     * the best of the several passes of one replay is kept while its weights still exist.
+     * [patience]: the same launch sets a stop word; the host reads it with the health words of
+     * the replay (so one replay later) and launches no further replay: at most the rest of the
+     * stopping pass's replay plus one more replay run past it, changing nothing that is returned */
+    const bool keep = validate && o->keep_best != 0;
+    BestSnap best;
+    if (keep) {
+        if (!best.init(net.masters(), s)) return FALSE;
+        NN_OUT(stdout, "batched GPU training: the best validation pass (%s) is kept\n",
+               o->keep_best == NN_KEEP_ACC ? "acc" : "loss");
+    }
     auto validation = [&]() -> bool {
         if (net.evaluate(va.xs, va.T.get(), n_out, nval) &&
-            hpnn_validate_commit(net.vacc(), vhist.get(), vcur.get(), (unsigned int)vsched.size(), s) == 0)
+            hpnn_validate_commit(net.vacc(), vhist.get(), vcur.get(), (unsigned int)vsched.size(), s) == 0 &&
+            (!keep || (hpnn_best_commit(vhist.get(), vcur.get(), best.state.get(), (int)o->keep_best, o->patience,
+                                        s) == 0 &&
+                       hpnn_snapshot_if(best.table.get(), (int)best.segs.size(), best.take(), s) == 0)))
             return true;
         NN_ERROR(stderr, "batched GPU training: the validation pass could not be launched\n");
         return false;
@@ -150,27 +168,36 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
     double ep_loss = 0.0;
     unsigned int ep_hits = 0;
     /* the health of every replay (HealthRing), plus a final check after the last replay; word
-     * [3] is the permutation kernel's error word */
+     * [3] is the permutation kernel's error word, word [4] the stop word of [patience] */
     HealthRing ring;
     BOOL ok = ring.ok();
     int pend = -1, slot = 0;
+    const bool patient = keep && o->patience > 0;
+    bool stopped = false; /* the host has seen the stop word: no further replay */
+    unsigned int hstop = 0;
     auto judge = [&](int sl) -> bool {
         const unsigned int *d = ring.judge(sl);
         if (!d || !net.health_ok(d)) return false;
-        if (d[3] == 0) return true;
-        NN_ERROR(stderr, "batched GPU training: the epoch permutation did not terminate within its bound; stopping\n");
-        return false;
+        if (d[3]) {
+            NN_ERROR(stderr,
+                     "batched GPU training: the epoch permutation did not terminate within its bound; stopping\n");
+            return false;
+        }
+        if (d[4]) stopped = true;
+        return true;
     };
     std::vector<hpnn_val_record> vrec(vsched.size());
     size_t vdone = 0;
-    for (int e = 0; e < E && ok;) {
+    int e = 0;
+    while (e < E && ok && !stopped) {
         const int ne = std::min(epg, E - e);
         auto g = graphs.find(gkey(ne, e));
         ok = (g != graphs.end() && g->second) ? hipGraphLaunch(g->second.get(), s) == hipSuccess : epochs(ne, e);
         e += ne;
         if (ok)
             ok = ring.post(slot, s, net, [&](unsigned int *d) {
-                return !shuffle || hipMemcpyAsync(d + 3, shw.get() + 1, 4, hipMemcpyDeviceToHost, s) == hipSuccess;
+                return (!shuffle || hipMemcpyAsync(d + 3, shw.get() + 1, 4, hipMemcpyDeviceToHost, s) == hipSuccess) &&
+                       (!patient || hipMemcpyAsync(d + 4, best.stop(), 4, hipMemcpyDeviceToHost, s) == hipSuccess);
             });
         if (ok && pend >= 0) ok = judge(pend);
         pend = ok ? slot : -1;
@@ -187,31 +214,49 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
         if (ok && metrics && val_due(e - 1) && vdone < vrec.size()) {
             ok = validation() && hipMemcpyAsync(&vrec[vdone], vhist.get() + vdone, sizeof(hpnn_val_record),
                                                 hipMemcpyDeviceToHost, s) == hipSuccess &&
+                 (!patient || hipMemcpyAsync(&hstop, best.stop(), 4, hipMemcpyDeviceToHost, s) == hipSuccess) &&
                  hipStreamSynchronize(s) == hipSuccess;
             if (ok)
                 hpnn_metrics_validation("gpu", o->epoch0 + e, vrec[vdone].loss_sum / (double)nval, vrec[vdone].hits,
                                         (UINT)nval);
             vdone++;
+            if (ok && hstop) stopped = true;
         }
     }
     if (ok && pend >= 0) ok = judge(pend);
+    /* stopped before the last epoch: the statistics of the last epoch that ran */
+    if (ok && !metrics && e < E) ok = net.read_stats(&ep_loss, &ep_hits);
     auto t1 = std::chrono::steady_clock::now();
+    hpnn_best_state hb;
+    memset(&hb, 0, sizeof hb);
+    if (ok && keep)
+        ok = hipStreamSynchronize(s) == hipSuccess &&
+             hipMemcpy(&hb, best.state.get(), sizeof hb, hipMemcpyDeviceToHost) == hipSuccess;
+    /* the passes up to the stopping one: the best pass and the stale ones behind it (those the
+     * replays filed after it are not reported) */
+    const size_t judged = hb.valid ? (size_t)hb.index + 1 + hb.stale : (size_t)hb.stale;
     if (ok && validate && !metrics) {
         /* the whole history, once; the cursor tells how many passes were filed */
         unsigned int filed = 0;
         ok = hipMemcpy(&filed, vcur.get(), sizeof filed, hipMemcpyDeviceToHost) == hipSuccess &&
              hipMemcpy(vrec.data(), vhist.get(), vrec.size() * sizeof(hpnn_val_record), hipMemcpyDeviceToHost) ==
                  hipSuccess;
-        if (ok && filed != vrec.size()) {
-            NN_ERROR(stderr, "batched GPU training: %u validation records filed, %zu scheduled\n", filed, vrec.size());
+        if (ok && (hb.stop ? filed < judged || judged > vrec.size() : filed != vrec.size())) {
+            NN_ERROR(stderr, "batched GPU training: %u validation records filed, %zu scheduled%s\n", filed,
+                     vrec.size(), hb.stop ? " (stopped early)" : "");
             ok = FALSE;
         }
-        vdone = vrec.size();
+        vdone = hb.stop ? judged : vrec.size();
     }
+    if (ok && validate) vrec.resize(std::min(vdone, vrec.size()));
     graphs.clear();
-    if (ok) ok = net.download(k);
+    if (ok) ok = net.download_from(k, hb.valid ? best.dst.data() : nullptr);
     if (ok && st) {
-        fill_stats(st, std::chrono::duration<double>(t1 - t0).count(), n, o->epochs, ep_loss, ep_hits);
+        fill_stats(st, std::chrono::duration<double>(t1 - t0).count(), n, (UINT)e, ep_loss, ep_hits);
+        st->epochs_run = (UINT)e;
+        st->best_epoch = hb.valid ? vsched[hb.index] : 0;
+        st->best_index = hb.valid ? hb.index : 0;
+        st->stop_epoch = hb.stop && !vrec.empty() ? vsched[vrec.size() - 1] : 0;
         st->val = NULL;
         st->n_val = (UINT)vrec.size();
         if (!vrec.empty()) {

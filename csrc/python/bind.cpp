@@ -439,6 +439,21 @@ PYBIND11_MODULE(_native, m) {
                                    S(stream)),
               "validate_commit");
     });
+    /* [keep_best] (kernels_best.hip); the three return the launcher's code (0, or -1: refused) */
+    m.def("best_commit", [](uptr hist, uptr cursor, uptr state, int metric, unsigned int patience, uptr stream) {
+        return hpnn_best_commit((const hpnn_val_record *)P(hist), (const unsigned int *)P(cursor),
+                                (hpnn_best_state *)P(state), metric, patience, S(stream));
+    });
+    m.def("snapshot_table", [](uptr segs, const std::vector<std::tuple<uptr, uptr, unsigned long long>> &host,
+                               uptr stream) {
+        std::vector<hpnn_snap_seg> h;
+        for (const auto &t : host) h.push_back({P(std::get<0>(t)), P(std::get<1>(t)), std::get<2>(t)});
+        return hpnn_snapshot_table((hpnn_snap_seg *)P(segs), h.data(), (int)h.size(), S(stream));
+    });
+    m.def("snapshot_if", [](uptr segs, int n_segs, uptr take, uptr stream) {
+        return hpnn_snapshot_if((const hpnn_snap_seg *)P(segs), n_segs, (const unsigned int *)P(take), S(stream));
+    });
+    m.def("best_empty_launch", [](uptr stream) { return hpnn_best_empty_launch(S(stream)); });
     m.def("mlp3_tile_grid", [](int Bp, int grid) { return hpnn_mlp3_tile_grid(Bp, grid); });
     m.def("mlp3_tile_trace", []() {
         std::vector<unsigned long long> v(1024 * 12);

@@ -21,6 +21,7 @@ NN_MODE = {"online": 0, "batched": 1}
 NN_DTYPE = {"f64": 0, "f32": 1, "bf16": 2}
 NN_DEVICE = {"auto": 0, "cpu": 1, "gpu": 2}
 NN_SHUFFLE = {"once": 0, "epoch": 1}
+NN_KEEP_BEST = {"off": 0, "loss": 1, "acc": 2}
 
 
 def lib():
@@ -48,6 +49,9 @@ def lib():
             "hpnn_epoch_perm": (None, [u, u, u, vp]),
             "nn_set_validate": (None, [vp, u]), "nn_return_validate": (u, [vp]),
             "nn_get_validation": (u, [vp, u, vp, vp, vp, vp]),
+            "nn_set_keep_best": (None, [vp, i]), "nn_return_keep_best": (i, [vp]),
+            "nn_set_patience": (None, [vp, u]), "nn_return_patience": (u, [vp]),
+            "nn_get_best": (i, [vp, ctypes.POINTER(u), ctypes.POINTER(d), ctypes.POINTER(u), ctypes.POINTER(u)]),
             "nn_set_batch": (None, [vp, u]), "nn_set_epochs": (None, [vp, u]),
             "nn_set_learning_rate": (None, [vp, d]), "nn_set_momentum": (None, [vp, d]),
             "nn_set_seed": (None, [vp, u]), "nn_return_seed": (u, [vp]),
@@ -107,7 +111,7 @@ class Network:
 
     # configuration
     def set(self, mode=None, dtype=None, device=None, batch=None, epochs=None, lr=None, momentum=None, seed=None,
-            shuffle=None, validate=None):
+            shuffle=None, validate=None, keep_best=None, patience=None):
         if mode is not None:
             self.L.nn_set_mode(self.ptr, NN_MODE[mode])
         if dtype is not None:
@@ -128,7 +132,28 @@ class Network:
             self.L.nn_set_shuffle(self.ptr, NN_SHUFFLE[shuffle] if isinstance(shuffle, str) else int(bool(shuffle)))
         if validate is not None:  # N: batched training validates on [test_dir] every N epochs (0 = off)
             self.L.nn_set_validate(self.ptr, int(validate))
+        if keep_best is not None:  # "loss" | "acc": return the state of the best validation pass ("off" / False)
+            self.L.nn_set_keep_best(self.ptr, NN_KEEP_BEST[keep_best or "off"])
+        if patience is not None:  # P: stop after P validation passes without improvement (0 = never)
+            self.L.nn_set_patience(self.ptr, int(patience))
         return self
+
+    @property
+    def keep_best(self):
+        return {v: k for k, v in NN_KEEP_BEST.items()}[self.L.nn_return_keep_best(self.ptr)]
+
+    @property
+    def patience(self):
+        return self.L.nn_return_patience(self.ptr)
+
+    def best(self):
+        """the best validation record of the last train() call with keep_best on: a dict with
+        epoch, loss (mean per sample), correct, n and accuracy; None when there is none"""
+        ep, co, nn, lo = ctypes.c_uint(), ctypes.c_uint(), ctypes.c_uint(), ctypes.c_double()
+        if not self.L.nn_get_best(self.ptr, ctypes.byref(ep), ctypes.byref(lo), ctypes.byref(co), ctypes.byref(nn)):
+            return None
+        return {"epoch": ep.value, "loss": lo.value, "correct": co.value, "n": nn.value,
+                "accuracy": co.value / nn.value if nn.value else 0.0}
 
     @property
     def validate(self):

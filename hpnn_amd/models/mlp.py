@@ -486,6 +486,42 @@ class MLP:
                                _p(None if g is None else g[r0:]), _stream())
         return g
 
+    # ------------------------------------------------------------------ keep the best pass
+    def _masters(self):
+        return [t for l in range(self.L) for t in (self.W32[l], self.V32[l]) if t is not None]
+
+    def keep_best(self, metric="loss", patience=0):
+        """allocate the best state and the snapshot of the FP32 masters (and the momentum) for
+        commit_best (docs/DESIGN.md 3.2g); metric "loss" | "acc", patience 0 = never stop"""
+        if metric not in ops.BEST_METRIC:
+            raise ValueError(f"keep_best: metric {metric!r} (loss | acc)")
+        self._best_metric, self._best_patience = metric, int(patience)
+        self._best = ops.best_state(self.device)
+        self._snap = [torch.zeros_like(t) for t in self._masters()]
+        self._snap_table = ops.snapshot_table(list(zip(self._masters(), self._snap)))
+
+    def commit_best(self, hist, cursor):
+        """behind ops.validate_commit(vstats, hist, cursor) on the current stream: judge the
+        record just filed and copy the masters into the snapshot when it is the best so far
+        (two launches, no host sync; capturable)"""
+        ops.best_commit(hist, cursor, self._best, self._best_metric, self._best_patience)
+        ops.snapshot_if(self._snap_table, self._best[7:8])
+
+    def best_state(self):
+        """the best state as a dict: loss_sum, hits, index (of the best record in the history),
+        stale, stop, valid, take (synchronises)"""
+        return ops.read_best_state(self._best)
+
+    def restore_best(self):
+        """the snapshot of the best pass back into W32 / V32 and the BF16 copies re-derived;
+        False (nothing changed) when no pass was taken"""
+        if not self.best_state()["valid"]:
+            return False
+        for t, s in zip(self._masters(), self._snap):
+            t.copy_(s)
+        self.refresh_bf16()
+        return True
+
     def reset_eval_stats(self):
         self.buf[("vstats", -1)].zero_()
 

@@ -333,6 +333,107 @@ def validate_commit(slots, hist, cursor):
     return hist
 
 
+BEST_METRIC = {"loss": 1, "acc": 2}  # HPNN_BEST_LOSS / HPNN_BEST_ACC (= nn_keep_best)
+BEST_WORDS = ("hits", "index", "stale", "stop", "valid", "take")  # int32 words 2..7 of a best state
+
+
+def best_state(device="cpu"):
+    """a zeroed hpnn_best_state as [8] int32: the float64 loss sum in words 0..1, then hits,
+    index, stale, stop, valid, take"""
+    return torch.zeros(8, dtype=torch.int32, device=device)
+
+
+def read_best_state(state):
+    """the best state as a dict (synchronises)"""
+    s = state.cpu()
+    d = {k: int(s[2 + i]) & 0xffffffff for i, k in enumerate(BEST_WORDS)}
+    d["loss_sum"] = float(s[0:2].view(torch.float64)[0])
+    return d
+
+
+def best_commit(hist, cursor, state, metric="loss", patience=0):
+    """judge the record validate_commit has just filed (hist[cursor - 1]) against the best so far
+    (csrc/gpu/kernels_best.hip; docs/DESIGN.md 3.2g) and set the take word of `state`
+    (best_state()).  metric "loss": a smaller loss sum; "acc": more hits, the loss breaking
+    ties; nothing is best before the first pass (loss: the first pass whose loss is not a NaN is
+    taken), ties do not improve.  An improving pass zeroes stale, any other adds one; patience >
+    0: the pass at which stale == patience sets stop, and the state is frozen from then on.
+    cursor == 0: a no-op.  One capturable one-thread launch; on CPU tensors the same rule in
+    PyTorch, bit for bit."""
+    m = BEST_METRIC[metric] if isinstance(metric, str) else int(metric)
+    if m not in (1, 2):
+        raise ValueError(f"best_commit: metric {metric!r}")
+    if _cpu(hist):
+        c = int(cursor[0])
+        if c == 0 or int(state[5]):
+            state[7] = 0
+            return state
+        loss = float(hist[c - 1, 0])
+        hits = int(hist[c - 1, 1:2].view(torch.int32)[0]) & 0xffffffff
+        b_loss = float(state[0:2].view(torch.float64)[0])
+        b_hits = int(state[2]) & 0xffffffff
+        if not int(state[6]):
+            better = m == 2 or loss == loss
+        elif m == 2:
+            better = hits > b_hits or (hits == b_hits and loss < b_loss)
+        else:
+            better = loss < b_loss
+        if better:
+            state[0:2].copy_(hist[c - 1, 0:1].view(torch.int32))
+            state[2] = hist[c - 1, 1:2].view(torch.int32)[0]
+            state[3], state[4], state[6], state[7] = c - 1, 0, 1, 1
+        else:
+            state[4] += 1
+            state[7] = 0
+        if patience and (int(state[4]) & 0xffffffff) == int(patience):
+            state[5] = 1
+        return state
+    rc = native().best_commit(hist.data_ptr(), cursor.data_ptr(), state.data_ptr(), m, int(patience), _stream())
+    if rc:
+        raise RuntimeError(f"best_commit failed (rc={rc})")
+    return state
+
+
+def snapshot_table(pairs):
+    """the segment table of snapshot_if for (src, dst) tensor pairs of equal byte size (at most
+    32; any multiple of 4 bytes; both 16-byte aligned, else ValueError and nothing is written).
+    Device tensors: a [n, 3] int64 device tensor {src, dst, bytes} (it keeps the pairs alive);
+    CPU tensors: the list itself."""
+    pairs = [(s, d) for s, d in pairs]
+    for s, d in pairs:
+        if s.numel() * s.element_size() != d.numel() * d.element_size():
+            raise ValueError("snapshot_table: src and dst differ in size")
+        if not (s.is_contiguous() and d.is_contiguous()):
+            raise ValueError("snapshot_table: contiguous tensors only")
+    if not pairs or _cpu(pairs[0][0]):
+        if len(pairs) > 32:
+            raise ValueError("snapshot_table: more than 32 segments")
+        return pairs
+    segs = torch.zeros(len(pairs), 3, dtype=torch.int64, device=pairs[0][0].device)
+    rc = native().snapshot_table(segs.data_ptr(), [(s.data_ptr(), d.data_ptr(), s.numel() * s.element_size())
+                                                   for s, d in pairs], _stream())
+    if rc:
+        raise ValueError(f"snapshot_table refused the segments (rc={rc}): 16-byte aligned pointers, sizes a "
+                         "multiple of 4, at most 32 segments")
+    segs.hpnn_pairs = pairs
+    return segs
+
+
+def snapshot_if(segs, take):
+    """copy every segment of a snapshot_table when the word take[0] is not 0 -- read from memory
+    when the launch runs, so a captured launch follows the flag of each replay -- and do nothing
+    when it is 0.  One capturable launch (16-byte vector copies, a 4-byte tail); on CPU tensors
+    the same in PyTorch."""
+    if isinstance(segs, list):
+        if int(take[0]) != 0:
+            for s, d in segs:
+                d.view(-1).view(torch.uint8).copy_(s.view(-1).view(torch.uint8))
+        return
+    rc = native().snapshot_if(segs.data_ptr(), segs.shape[0], take.data_ptr(), _stream())
+    if rc:
+        raise RuntimeError(f"snapshot_if failed (rc={rc})")
+
+
 WIDE2_K0 = (4096,)  # first-layer input widths of hpnn_wide2_front
 WIDE2_TILE = 128  # samples per tile (the batch must be a multiple)
 

@@ -98,6 +98,12 @@ typedef enum {
     NN_SHUFFLE_EPOCH = 1, /* a new order every epoch of batched training (libhpnn/shuffle.h) */
 } nn_shuffle;
 
+typedef enum {
+    NN_KEEP_OFF = 0,  /* the weights after the last epoch are returned */
+    NN_KEEP_LOSS = 1, /* those of the validation pass with the smallest loss */
+    NN_KEEP_ACC = 2,  /* those of the pass with the most hits (the loss breaks ties) */
+} nn_keep_best;
+
 typedef struct {
     nn_runtime *rr;  /* link to the runtime parameters */
     CHAR *name;
@@ -131,6 +137,15 @@ typedef struct {
     UINT validate;
     UINT n_validation;
     void *validation;
+    /* -- [keep_best] loss | acc, [patience] P: batched training returns the state of its best
+     *    validation pass and stops after P passes without improvement; the best record of the
+     *    last nn_train_kernel call (nn_get_best; best_epoch 0: none) -- */
+    nn_keep_best keep_best;
+    UINT patience;
+    UINT best_epoch;
+    DOUBLE best_loss;
+    UINT best_correct;
+    UINT best_n;
 } nn_def;
 
 #define _NN(a, b) nn_##a##_##b
@@ -279,6 +294,21 @@ void _NN(set, validate)(nn_def *conf, UINT every);
 void _NN(get, validate)(nn_def *conf, UINT *every);
 UINT _NN(return, validate)(nn_def *conf);
 UINT _NN(get, validation)(nn_def *conf, UINT max, UINT *epoch, DOUBLE *loss, UINT *correct, UINT *n);
+/* [keep_best] loss | acc (needs [validate]): nn_train_kernel returns the kernel exactly as it was
+ * after the epoch of its best validation pass -- weights, momentum, epochs_done -- so the call is
+ * indistinguishable from one given that many epochs.  loss: the pass with the smallest loss; acc:
+ * the most hits, the loss breaking ties; ties do not improve, a NaN loss is never the smallest.
+ * The best is per call.  [patience] P (needs [keep_best]; 0 = never): training stops at the pass
+ * at which P passes in a row have not improved.  nn_train_kernel prints "BEST: epoch E loss=L
+ * acc=C/N" and, after a stop, "EARLY STOP: epoch E (no improvement in P passes)"; nn_get_best
+ * returns the record of the last call (any pointer may be NULL), FALSE when there is none */
+void _NN(set, keep_best)(nn_def *conf, nn_keep_best keep);
+void _NN(get, keep_best)(nn_def *conf, nn_keep_best *keep);
+nn_keep_best _NN(return, keep_best)(nn_def *conf);
+void _NN(set, patience)(nn_def *conf, UINT passes);
+void _NN(get, patience)(nn_def *conf, UINT *passes);
+UINT _NN(return, patience)(nn_def *conf);
+BOOL _NN(get, best)(nn_def *conf, UINT *epoch, DOUBLE *loss, UINT *correct, UINT *n);
 /* the [shuffle] epoch permutation (libhpnn/shuffle.h): out[i] = index, in the order drawn once
  * from [seed], of the sample at position i of epoch `epoch` (epochs completed before it) */
 void hpnn_epoch_perm(UINT n, UINT seed, UINT epoch, UINT *out);

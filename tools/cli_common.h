@@ -12,6 +12,8 @@
  *   [shuffle] epoch),
  *   -V N (train_nn only) validate on [test_dir] every N epochs of batched training and after
  *   the last one (same as [validate] N),
+ *   -K loss|acc (train_nn only) return the state of the best validation pass (same as
+ *   [keep_best]), -P P (train_nn only) stop after P passes without improvement ([patience] P),
  *   -r FILE exact-resume state (loaded when present, written after training),
  *   -M FILE JSON-lines metrics (same as HPNN_METRICS=FILE),
  *   -T trace ranges + timing table (same as HPNN_TRACE=1).
@@ -33,6 +35,8 @@ typedef struct {
     int force_cpu;
     int reshuffle; /* -R */
     unsigned validate; /* -V N */
+    int keep_best;     /* -K loss|acc */
+    unsigned patience; /* -P P */
     double lr, alpha;
     const char *state;   /* -r */
     const char *metrics; /* -M */
@@ -84,13 +88,13 @@ static int cli_parse(int argc, char **argv, cli_opts *o, int allow_x) {
                 j++;
                 continue;
             }
-            if (strchr("OBSGbemdlarM", c) || (c == 'V' && allow_x)) {
+            if (strchr("OBSGbemdlarM", c) || (strchr("VKP", c) && allow_x)) {
                 const char *val = a[j + 1] ? &a[j + 1] : (i + 1 < argc ? argv[++i] : NULL);
                 if (!val) {
                     _OUT(stderr, "syntax error: missing -%c parameter!\n", c);
                     return -1;
                 }
-                if (strchr("OBSGbeV", c)) {
+                if (strchr("OBSGbeVP", c)) {
                     if (!isdigit((unsigned char)*val) || atoi(val) <= 0) {
                         _OUT(stderr, "syntax error: bad -%c parameter!\n", c);
                         return -1;
@@ -104,6 +108,13 @@ static int cli_parse(int argc, char **argv, cli_opts *o, int allow_x) {
                         case 'b': o->batch = v; o->mode = NN_MODE_BATCHED; break;
                         case 'e': o->epochs = v; break;
                         case 'V': o->validate = v; break;
+                        case 'P': o->patience = v; break;
+                    }
+                } else if (c == 'K') {
+                    o->keep_best = !strcmp(val, "loss") ? NN_KEEP_LOSS : (!strcmp(val, "acc") ? NN_KEEP_ACC : -1);
+                    if (o->keep_best < 0) {
+                        _OUT(stderr, "syntax error: bad -K parameter (loss | acc)!\n");
+                        return -1;
                     }
                 } else if (c == 'm') {
                     o->mode = (val[0] == 'b' || val[0] == 'B') ? NN_MODE_BATCHED : NN_MODE_ONLINE;
@@ -144,6 +155,8 @@ static void cli_apply_conf(const cli_opts *o, nn_def *conf) {
     if (o->force_cpu) _NN(set, device)(conf, NN_DEVICE_CPU);
     if (o->reshuffle) _NN(set, shuffle)(conf, NN_SHUFFLE_EPOCH);
     if (o->validate) _NN(set, validate)(conf, o->validate);
+    if (o->keep_best) _NN(set, keep_best)(conf, (nn_keep_best)o->keep_best);
+    if (o->patience) _NN(set, patience)(conf, o->patience);
     if (o->lr > 0) _NN(set, learning_rate)(conf, o->lr);
     if (o->alpha >= 0) _NN(set, momentum)(conf, o->alpha);
 }

@@ -33,6 +33,8 @@ static void dump_help(void) {
     _OUT(stdout, "-c \tforce the CPU engine.\n");
     _OUT(stdout, "-R \treshuffle the samples every epoch (batched mode; [shuffle] epoch).\n");
     _OUT(stdout, "-V N\tvalidate on [test_dir] every N epochs and after the last (batched mode; [validate] N).\n");
+    _OUT(stdout, "-K M\treturn the state of the best validation pass, M: loss | acc (needs -V; [keep_best]).\n");
+    _OUT(stdout, "-P P\tstop after P validation passes without improvement (needs -K; [patience] P).\n");
     _OUT(stdout, "-r F\texact-resume state file (read if present, written after training).\n");
     _OUT(stdout, "-M F\tJSON-lines metrics file.  -T trace ranges + timing table.\n");
     _OUT(stdout, "***********************************\n");
