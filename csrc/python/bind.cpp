@@ -269,6 +269,48 @@ PYBIND11_MODULE(_native, m) {
         if (rc != -1) check(rc, "gemm_tn8_update");
         return rc == 0;
     });
+    /* the split-K form with the reduction and the step inside the launch; side: None, or the next
+     * layer's job as (D, ldd, H, ldh, slab, N, M, S, W32, V32, Wb, Wt, cnt).  Returns the
+     * launcher's code: 0, -1 (not covered, nothing launched), -2 (the side job does not fit) */
+    m.def("gemm_tn8_fused_update", [](uptr D, int ldd, uptr H, int ldh, int N, int M, int Bt, int splits, uptr slab,
+                                      uptr W32, uptr V32, uptr Wbf, uptr Wt, float lr, float alpha, float scale,
+                                      int momentum, uptr cnt, uptr err, py::object side, uptr stream) {
+        hpnn_tn8_side sd = {};
+        const bool has_side = !side.is_none();
+        if (has_side) {
+            py::tuple t = side.cast<py::tuple>();
+            if (py::len(t) != 13) throw std::runtime_error("gemm_tn8_fused_update: side tuple of 13");
+            sd.D = P(t[0].cast<uptr>()), sd.ldd = t[1].cast<int>();
+            sd.H = P(t[2].cast<uptr>()), sd.ldh = t[3].cast<int>();
+            sd.slab = (float *)P(t[4].cast<uptr>());
+            sd.N = t[5].cast<int>(), sd.M = t[6].cast<int>(), sd.S = t[7].cast<int>();
+            sd.W32 = (float *)P(t[8].cast<uptr>()), sd.V32 = (float *)P(t[9].cast<uptr>());
+            sd.Wb = P(t[10].cast<uptr>()), sd.Wt = P(t[11].cast<uptr>());
+            sd.cnt = (unsigned int *)P(t[12].cast<uptr>());
+        }
+        return hpnn_gemm_tn8_fused_update_side(P(D), ldd, P(H), ldh, N, M, Bt, splits, (float *)P(slab),
+                                               (float *)P(W32), (float *)P(V32), P(Wbf), P(Wt), lr, alpha, scale,
+                                               momentum, (unsigned int *)P(cnt), (unsigned int *)P(err),
+                                               has_side ? &sd : nullptr, S(stream));
+    });
+    m.def("gemm_tn8_bf16out", [](uptr D, int ldd, uptr H, int ldh, uptr G16, int ldg, int N, int M, int Bt,
+                                 uptr stream) {
+        return hpnn_gemm_tn8_bf16out(P(D), ldd, P(H), ldh, P(G16), ldg, N, M, Bt, S(stream));
+    });
+    m.def("gemm_tn8_bf16out_ok",
+          [](int N, int M, int Bt, int ldd, int ldh) { return hpnn_gemm_tn8_bf16out_ok(N, M, Bt, ldd, ldh); });
+    /* pieces of the BF16 exchanges and the replica digest (kernels_misc.hip): the launcher's code */
+    m.def("cast_f32_bf16", [](uptr src, uptr dst, long n, uptr stream) {
+        return hpnn_cast_f32_bf16((const float *)P(src), P(dst), n, S(stream));
+    });
+    m.def("sgd_update_rows_bf16g", [](uptr W32, uptr V32, uptr G16, long n, float lr, float alpha, float scale,
+                                      int momentum, uptr Wbf, uptr stream) {
+        return hpnn_sgd_update_rows_bf16g((float *)P(W32), (float *)P(V32), P(G16), n, lr, alpha, scale, momentum,
+                                          P(Wbf), S(stream));
+    });
+    m.def("hash_words", [](uptr p, long nbytes, long base, uptr out, uptr stream) {
+        return hpnn_hash_words(P(p), nbytes, base, (unsigned long long *)P(out), S(stream));
+    });
     m.def("gemm_nt8_splitk_bf16", [](uptr A, int lda, uptr B, int ldb, uptr C, int ldc, uptr aux, int ldaux, int M,
                                      int N, int K, int epi, int c_f32, int splits, uptr stream) {
         check(hpnn_gemm_nt8_splitk_bf16(P(A), lda, P(B), ldb, P(C), ldc, P(aux), ldaux, M, N, K, epi, c_f32, splits,

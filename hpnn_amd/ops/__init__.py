@@ -91,6 +91,95 @@ def gemm_tn_update(D, H, W32, V32, Wbf, Wt, lr, alpha=0.0, scale=1.0, momentum=F
                                          float(lr), float(alpha), float(scale), int(bool(momentum)), _stream()))
 
 
+class TnSide:
+    """the side job of gemm_tn_fused_update: the next layer's gradient D^T H ([Bt, N] x [Bt, M],
+    S splits into slab [S, N, M]) and its step on W32 / V32 / Wb [N, M] and Wt [M, N]; cnt: one
+    int64 arrival counter, zeroed once and kept for this launch shape."""
+
+    def __init__(self, D, H, S, slab, W32, V32, Wb, Wt, cnt):
+        self.D, self.H, self.S, self.slab = D, H, int(S), slab
+        self.W32, self.V32, self.Wb, self.Wt, self.cnt = W32, V32, Wb, Wt, cnt
+
+
+def _sum_groups_of_8(slab):
+    """the split-K sum of the fused TN update: batches of 16 partials, each group of 8 summed
+    first (csrc/gpu/kernels_8ph.hip, MODE 2)"""
+    g = torch.zeros_like(slab[0])
+    for s0 in range(0, slab.shape[0], 8):
+        t = slab[s0].clone()
+        for s_ in range(s0 + 1, min(s0 + 8, slab.shape[0])):
+            t += slab[s_]
+        g += t
+    return g
+
+
+def _sum_sgd_tile(slab):
+    """the slab sum of sgd_tile (csrc/gpu/kernels_misc.hip): slab 0, then slabs 1.. in four
+    interleaved chains while four remain, the rest into chain 0, chain 0 + ((1 + 2) + 3)"""
+    S = slab.shape[0]
+    gend = 1 + 4 * ((S - 1) // 4)
+    c = [slab[0].clone()] + [torch.zeros_like(slab[0]) for _ in range(3)]
+    for k in range(1, S):
+        c[0 if k >= gend else (k - 1) & 3] += slab[k]
+    return c[0] + ((c[1] + c[2]) + c[3])
+
+
+def gemm_tn_fused_update(D, H, splits, slab, W32, V32, Wbf, Wt, lr, alpha=0.0, scale=1.0, momentum=False, cnt=None,
+                         err=None, side=None):
+    """gemm_tn_update for a gradient over `splits` (>= 2) split-K slices, reduced inside the
+    launch (csrc/gpu/kernels_8ph.hip, MODE 2): every split publishes its partial tile into slab
+    [splits, N, M], the splits of a tile meet through the tile's 64-bit ticket in cnt (int64
+    [512], zeroed once and kept for this GEMM shape: word 16 * tile gains `splits` per launch), then
+    each reduces 1 / splits of the tile and steps it.  err (int32 [1]) is set when a wait timed
+    out.  side (TnSide): the next layer's gradient and step carried by the same launch.
+    Returns the launcher's code: 0, -1 (shape or grid not covered: nothing launched), -2 (the
+    side job does not fit this grid).  The CPU emulation always applies."""
+    Bt, N = D.shape
+    M = H.shape[1]
+    if _cpu(D):
+        for s_, (a, b) in enumerate(split_rows(Bt, splits)):
+            slab[s_].copy_(ref_gemm_tn(D[a:b], H[a:b]))
+        sgd_update(W32, V32, _sum_groups_of_8(slab[:splits]), Wbf, Wt, lr, alpha, scale, momentum)
+        ntiles = (N // 256) * (M // 256)
+        cnt[0:16 * ntiles:16] += splits
+        if side is not None:
+            for s_, (a, b) in enumerate(split_rows(Bt, side.S)):
+                side.slab[s_].copy_(ref_gemm_tn(side.D[a:b], side.H[a:b]))
+            sgd_update(side.W32, side.V32, _sum_sgd_tile(side.slab[:side.S]), side.Wb, side.Wt, lr, alpha, scale,
+                       momentum)
+            side.cnt[0] += ntiles * splits
+        return 0
+    sd = None
+    if side is not None:
+        sd = (side.D.data_ptr(), side.D.stride(0), side.H.data_ptr(), side.H.stride(0), side.slab.data_ptr(),
+              side.D.shape[1], side.H.shape[1], side.S, side.W32.data_ptr(), _ptr(side.V32) if momentum else 0,
+              side.Wb.data_ptr(), side.Wt.data_ptr(), side.cnt.data_ptr())
+    return native().gemm_tn8_fused_update(D.data_ptr(), D.stride(0), H.data_ptr(), H.stride(0), N, M, Bt, int(splits),
+                                          slab.data_ptr(), W32.data_ptr(), _ptr(V32) if momentum else 0,
+                                          Wbf.data_ptr(), Wt.data_ptr(), float(lr), float(alpha), float(scale),
+                                          int(bool(momentum)), cnt.data_ptr(), err.data_ptr(), sd, _stream())
+
+
+def gemm_tn_bf16out_ok(N, M, Bt, ldd, ldh):
+    """whether gemm_tn_bf16out covers the shape (N, M % 256, an even number of 64-row units,
+    operand strides % 8); pure host arithmetic"""
+    return bool(native().gemm_tn8_bf16out_ok(int(N), int(M), int(Bt), int(ldd), int(ldh)))
+
+
+def gemm_tn_bf16out(D, H, G16):
+    """G16[:, :M] (BF16, row stride >= M) = bf16(D^T H) over the whole batch, one rounding of the
+    FP32 sum (csrc/gpu/kernels_8ph.hip, MODE 3: the send buffer of the data-parallel BF16
+    exchange).  Returns the launcher's code: 0, or -1 (shape not covered: nothing launched); the
+    CPU emulation always applies."""
+    Bt, N = D.shape
+    M = H.shape[1]
+    if _cpu(D):
+        G16[:, :M] = ref_gemm_tn(D, H).bfloat16()
+        return 0
+    return native().gemm_tn8_bf16out(D.data_ptr(), D.stride(0), H.data_ptr(), H.stride(0), G16.data_ptr(),
+                                     G16.stride(0), N, M, Bt, _stream())
+
+
 def gemm_tn_reduce(D, H, splits, out, rslab, groups, rout):
     """gemm_tn(D, H, splits, out) and reduce_groups(rslab, groups, rout) in ONE launch:
     the reduction runs on workgroups appended to the GEMM grid (csrc/gpu/kernels.h)."""
@@ -576,6 +665,90 @@ def dact_cast(out, x, H):
         return out
     native().dact_f32_bf16(out.data_ptr(), x.data_ptr(), H.data_ptr(), x.numel(), _stream())
     return out
+
+
+def _misaligned(t, b):
+    return t.data_ptr() % b != 0
+
+
+def cast_f32_bf16(src, dst):
+    """dst (BF16) = bf16(src) (FP32), flat contiguous tensors of n % 4 == 0 elements (the FP32
+    gradient into the send buffer of the BF16 exchange).  Returns the launcher's code: 0, or -2
+    (n, or a pointer not 16- / 8-byte aligned: nothing written)."""
+    n = src.numel()
+    assert dst.numel() == n and src.is_contiguous() and dst.is_contiguous()
+    if _cpu(src):
+        if n <= 0 or n % 4 or _misaligned(src, 16) or _misaligned(dst, 8):
+            return -2
+        dst.copy_(src.bfloat16())
+        return 0
+    return native().cast_f32_bf16(src.data_ptr(), dst.data_ptr(), n, _stream())
+
+
+def sgd_update_rows_bf16g(W32, V32, G16, Wbf, lr, alpha=0.0, scale=1.0, momentum=False):
+    """the step of sgd_update on n % 4 == 0 contiguous elements from their BF16 gradient sum
+    G16: W32 / V32 FP32 masters, Wbf = bf16(W32) (a rank's rows in the sharded data-parallel
+    step).  Returns the launcher's code: 0, or -2 (n, alignment, momentum without V32: nothing
+    written)."""
+    n = W32.numel()
+    assert G16.numel() == n and Wbf.numel() == n and W32.is_contiguous() and G16.is_contiguous()
+    if _cpu(W32):
+        if n <= 0 or n % 4 or (momentum and V32 is None) or _misaligned(W32, 16) or \
+                (momentum and _misaligned(V32, 16)) or _misaligned(G16, 8) or _misaligned(Wbf, 8):
+            return -2
+        g = G16.float() * scale
+        if momentum:
+            V32 += lr * g
+            W32 += V32
+            V32 *= alpha
+        else:
+            W32 += lr * g
+        Wbf.copy_(W32.bfloat16())
+        return 0
+    return native().sgd_update_rows_bf16g(W32.data_ptr(), _ptr(V32) if momentum else 0, G16.data_ptr(), n, float(lr),
+                                          float(alpha), float(scale), int(bool(momentum)), Wbf.data_ptr(), _stream())
+
+
+def transpose_bf16(Wb, Wt):
+    """Wt [K, N] = Wb^T for a contiguous BF16 [N, K] matrix, N % 32 == 0, K % 32 == 0."""
+    N, K = Wb.shape
+    assert Wt.shape == (K, N) and Wb.is_contiguous() and Wt.is_contiguous()
+    if _cpu(Wb):
+        if N % 32 or K % 32:
+            raise RuntimeError("transpose_bf16 failed (rc=-2)")
+        Wt.copy_(Wb.t())
+        return Wt
+    native().transpose_bf16(Wb.data_ptr(), Wt.data_ptr(), N, K, _stream())
+    return Wt
+
+
+_HASH_GOLD, _HASH_M1, _HASH_M2 = 0x9e3779b97f4a7c15, 0xff51afd7ed558ccd, 0xc4ceb9fe1a85ec53
+
+
+def hash_words(t, out, base=0, nbytes=None):
+    """out[0] (int64 [1]) += the order-independent digest of the first nbytes (default: all) of
+    the contiguous tensor t: the wrapping 64-bit sum over its 4-byte words w_i of
+    mix64((w_i << 32) ^ (i + base) ^ 0x9e3779b97f4a7c15), mix64 the murmur3 finalizer
+    (csrc/gpu/kernels_misc.hip).  Returns the launcher's code: 0, or -1 (nbytes % 4)."""
+    assert t.is_contiguous() and out.dtype == torch.int64 and out.numel() == 1
+    nbytes = t.numel() * t.element_size() if nbytes is None else int(nbytes)
+    if _cpu(t):
+        import numpy as np
+        if nbytes < 0 or nbytes % 4:
+            return -1
+        if nbytes == 0:
+            return 0
+        w = t.view(-1).view(torch.uint8)[:nbytes].numpy().view("<u4").astype(np.uint64)
+        x = (w << np.uint64(32)) ^ (np.arange(w.size, dtype=np.uint64) + np.uint64(base)) ^ np.uint64(_HASH_GOLD)
+        x ^= x >> np.uint64(33)
+        x *= np.uint64(_HASH_M1)
+        x ^= x >> np.uint64(33)
+        x *= np.uint64(_HASH_M2)
+        x ^= x >> np.uint64(33)
+        h = (int(np.add.reduce(x, dtype=np.uint64)) + int(out[0])) & 0xffffffffffffffff
+        out[0] = h - (1 << 64) if h >> 63 else h
+        return 0
+    return native().hash_words(t.data_ptr(), nbytes, int(base), out.data_ptr(), _stream())
 
 
 def pack_bf16(src, dst):
