@@ -5,12 +5,31 @@
  *                  in one pass (replaces the reference's sigmoid/softmax_acc/
  *                  fw_scal/amb/amb_smax/dsigmoid_mul_diff/dsmax_diff kernels
  *                  plus the host-synchronising cublasDasum, cuda_ann.cu:41-113,
- *                  cuda_snn.cu:42-147).  One wave64 per sample, wave-level
- *                  shuffles, one atomic per block; correct for any width
- *                  (the reference reductions read block 0 only: N<=2048).
- *                  SNN uses the reference softmax e^{z-1}/(TINY+sum e^{z-1})
- *                  evaluated in the max-shifted form (identical value, no
- *                  overflow).
+ *                  cuda_snn.cu:42-147).  Row-level shuffles, one atomic per
+ *                  block; correct for any width (the reference reductions
+ *                  read block 0 only: N<=2048).  SNN uses the reference
+ *                  softmax e^{z-1}/(TINY+sum e^{z-1}) evaluated in the
+ *                  max-shifted form (identical value, no overflow).
+ *                  One template output_delta_kernel<W, V, STEPS>: W lanes per
+ *                  row, V consecutive columns per lane and step, the row in
+ *                  registers for STEPS steps or streamed (STEPS = 0).
+ *                  hpnn_output_delta picks one of five mappings:
+ *                    <1, 32, 1>     ld <= 32: one lane per row, at most 256
+ *                                   blocks, so the stat atomics stay few
+ *                    <16, 16, 1>    64 < n_out, ld <= 256, ld % 16 == 0 (RRUFF:
+ *                                   230): four rows per wave, the five row
+ *                                   reductions over 16 lanes (4 shuffle steps,
+ *                                   not 6) and for 4 rows at once; one row per
+ *                                   wave spent ~17 us of 16384 x 230 in them
+ *                    <64, 1, 1..4>  n_out <= 256, any ld: one row per wave and
+ *                                   per grid step, Z read once instead of three
+ *                                   times; rows of one wave would serialize
+ *                                   their three dependent reductions
+ *                    <64, 4, 0>     wider, ld % 4 == 0 (synthetic 4096-wide
+ *                                   ANN): float4 loads, 8-byte delta stores; at
+ *                                   256 B per wave instruction the one below
+ *                                   ran 8192 x 4096 at ~2 TB/s
+ *                    <64, 1, 0>     any other row stride
  *   reduce_slabs : deterministic sum of split-K partial slabs.
  *   sgd_update   : slab reduce + BP / BPM update on the FP32 master, then
  *                  BF16 W and BF16 W^T (through an LDS transpose so both
@@ -34,22 +53,26 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v) {
+/* xor-butterfly reductions over the W lanes of a row (W = 1: nothing to do) */
+template <int W>
+__device__ __forceinline__ float row_sum(float v) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, W);
     return v;
 }
-__device__ __forceinline__ float wave_max(float v) {
+template <int W>
+__device__ __forceinline__ float row_max(float v) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    for (int o = W / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, W));
     return v;
 }
 /* first index of the maximum (ties -> lowest index), -1 for empty lanes */
-__device__ __forceinline__ void wave_argmax(float &v, int &i) {
+template <int W>
+__device__ __forceinline__ void row_argmax(float &v, int &i) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        float ov = __shfl_xor(v, o, 64);
-        int oi = __shfl_xor(i, o, 64);
+    for (int o = W / 2; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(v, o, W);
+        const int oi = __shfl_xor(i, o, W);
         if (oi >= 0 && (i < 0 || ov > v || (ov == v && oi < i))) {
             v = ov;
             i = oi;
@@ -64,7 +87,7 @@ __device__ __forceinline__ void block_reduce_store(float my_loss, unsigned int m
     __shared__ float sloss[4];
     __shared__ unsigned int shit[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    my_loss = wave_sum(my_loss);
+    my_loss = row_sum<64>(my_loss);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) my_hit += __shfl_xor(my_hit, o, 64);
     if (lane == 0) {
@@ -80,398 +103,49 @@ __device__ __forceinline__ void block_reduce_store(float my_loss, unsigned int m
     }
 }
 
-/* narrow outputs (n_out <= 64): one LANE per sample row, grid-stride, <= 256 blocks
- * so the loss/accuracy atomics stay few (one per block) */
-template <int MAXO>
-__global__ __launch_bounds__(256) void output_delta_rows_kernel(const float *__restrict__ Z, int ldz,
-                                                                const float *__restrict__ T, int ldt,
-                                                                const int *__restrict__ labels, float t_hi, float t_lo,
-                                                                __bf16 *__restrict__ D, int ldd, float *__restrict__ O,
-                                                                int ldo, float *__restrict__ loss_acc,
-                                                                unsigned int *__restrict__ correct, int B, int n_valid,
-                                                                int n_out, int type) {
-    float my_loss = 0.f;
-    unsigned int my_hit = 0;
-    for (int row = blockIdx.x * blockDim.x + threadIdx.x; row < B; row += gridDim.x * blockDim.x) {
-        const bool valid = row < n_valid;
-        float z[MAXO];
-        const float *zr = Z + (size_t)row * ldz;
-#pragma unroll
-        for (int c = 0; c < MAXO; c++) z[c] = c < n_out ? zr[c] : 0.f;
-        float zmax = -INFINITY;
+/* what a lane gathers over its columns of a row: the loss terms and both argmax candidates */
+struct OdLane {
+    float l = 0.f, bo = -INFINITY, bt = -INFINITY;
+    int io = -1, it = -1;
+};
+
+/* The per-element part of output_delta, for column c of a row: the output o from x (z for
+ * ANN / LNN, e^{z - zmax} for SNN, where inv = 1 / the shifted denominator), and for a valid
+ * row the target (label or dense), the loss term, both argmax candidates (first maximum:
+ * columns come in ascending order) and the delta, which is returned (0 for a padding row).
+ * A t == 0 softmax term would add +-0: skipping it leaves one logf per one-hot row. */
+__device__ __forceinline__ float od_element(int type, float x, float inv, bool valid, bool dense, float t_dense,
+                                            int lab, float t_hi, float t_lo, int c, float &o, OdLane &a) {
+    if (type == 2) o = x * inv;
+    else if (type == 0) o = 2.0f / (1.0f + __expf(-x)) - 1.0f;
+    else o = x;
+    float d = 0.f;
+    if (valid) {
+        const float t = dense ? t_dense : (c == lab ? t_hi : t_lo);
         if (type == 2) {
-#pragma unroll
-            for (int c = 0; c < MAXO; c++)
-                if (c < n_out) zmax = fmaxf(zmax, z[c]);
+            if (t != 0.f && o > 0.f) a.l += t * logf(o + TINY);
+            d = t - o;
+        } else if (type == 0) {
+            a.l += (t - o) * (t - o);
+            d = (t - o) * (-0.5f * (o * o - 1.0f));
+        } else {
+            a.l += (t - o) * (t - o);
+            d = t - o;
         }
-        float denom = 0.f;
-        if (type == 2) {
-#pragma unroll
-            for (int c = 0; c < MAXO; c++)
-                if (c < n_out) denom += __expf(z[c] - zmax);
-            denom += __expf(fminf(logf(TINY) + 1.0f - zmax, 80.f));
-        }
-        const float inv = type == 2 ? 1.0f / denom : 0.f;
-        const int lab = (labels && valid) ? labels[row] : -1;
-        float l = 0.f, bo = -INFINITY, bt = -INFINITY;
-        int io = -1, it = -1;
-        typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-        __bf16 dv[MAXO];
-#pragma unroll
-        for (int c = 0; c < MAXO; c++) {
-            float d = 0.f;
-            if (c < n_out) {
-                float o;
-                if (type == 2) o = __expf(z[c] - zmax) * inv;
-                else if (type == 0) o = 2.0f / (1.0f + __expf(-z[c])) - 1.0f;
-                else o = z[c];
-                if (valid) {
-                    const float t = labels ? (c == lab ? t_hi : t_lo) : T[(size_t)row * ldt + c];
-                    if (type == 2) {
-                        if (o > 0.f) l += t * logf(o + TINY);
-                        d = t - o;
-                    } else if (type == 0) {
-                        l += (t - o) * (t - o);
-                        d = (t - o) * (-0.5f * (o * o - 1.0f));
-                    } else {
-                        l += (t - o) * (t - o);
-                        d = t - o;
-                    }
-                    if (o > bo) { bo = o; io = c; }
-                    if (t > bt) { bt = t; it = c; }
-                }
-                if (O) O[(size_t)row * ldo + c] = o;
-            }
-            dv[c] = (__bf16)d;
-        }
-        /* delta row: ldd bf16 (ldd <= MAXO, multiple of 4) */
-        __bf16 *dr = D + (size_t)row * ldd;
-#pragma unroll
-        for (int c = 0; c < MAXO; c += 4)
-            if (c < ldd) *(bf16x4 *)(dr + c) = bf16x4{dv[c], dv[c + 1], dv[c + 2], dv[c + 3]};
-        if (valid) {
-            my_loss += (type == 2) ? -l / (float)n_out : 0.5f * l;
-            my_hit += (io == it) ? 1u : 0u;
-        }
+        if (o > a.bo) { a.bo = o; a.io = c; }
+        if (t > a.bt) { a.bt = t; a.it = c; }
     }
-    block_reduce_store(my_loss, my_hit, loss_acc, correct);
+    return d;
 }
 
-/* wide outputs up to 64*NPL classes (RRUFF: 230): one wave per sample row, the row kept in
- * registers (NPL values per lane) so Z is read once instead of three times, and one row
- * per wave (the grid covers the batch): the three dependent wave reductions of a row no
- * longer serialize over many rows per wave */
-template <int NPL>
-__global__ __launch_bounds__(256) void output_delta_reg_kernel(const float *__restrict__ Z, int ldz,
-                                                               const float *__restrict__ T, int ldt,
-                                                               const int *__restrict__ labels, float t_hi, float t_lo,
-                                                               __bf16 *__restrict__ D, int ldd, float *__restrict__ O,
-                                                               int ldo, float *__restrict__ loss_acc,
-                                                               unsigned int *__restrict__ correct, int B, int n_valid,
-                                                               int n_out, int type) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float my_loss = 0.f;
-    unsigned int my_hit = 0;
-    for (int row = blockIdx.x * 4 + wave; row < B; row += gridDim.x * 4) {
-        const bool valid = row < n_valid;
-        const int lab = (labels && valid) ? labels[row] : -1;
-        float z[NPL];
-#pragma unroll
-        for (int j = 0; j < NPL; j++) {
-            const int c = lane + 64 * j;
-            z[j] = c < n_out ? Z[(size_t)row * ldz + c] : -INFINITY;
-        }
-        float inv = 0.f, zmax = 0.f;
-        if (type == 2) {
-            zmax = z[0];
-#pragma unroll
-            for (int j = 1; j < NPL; j++) zmax = fmaxf(zmax, z[j]);
-            zmax = wave_max(zmax);
-            float denom = 0.f;
-#pragma unroll
-            for (int j = 0; j < NPL; j++)
-                if (lane + 64 * j < n_out) denom += __expf(z[j] - zmax);
-            denom = wave_sum(denom);
-            /* reference: e^{z-1} / (TINY + sum e^{z-1}); shifted by m=zmax */
-            denom += __expf(fminf(logf(TINY) + 1.0f - zmax, 80.f));
-            inv = 1.0f / denom;
-        }
-        float bo = -INFINITY, bt = -INFINITY;
-        int io = -1, it = -1;
-        float l = 0.f;
-#pragma unroll
-        for (int j = 0; j < NPL; j++) {
-            const int c = lane + 64 * j;
-            float d = 0.f;
-            if (c < n_out) {
-                float o;
-                if (type == 2) o = __expf(z[j] - zmax) * inv;
-                else if (type == 0) o = 2.0f / (1.0f + __expf(-z[j])) - 1.0f;
-                else o = z[j];
-                if (valid) {
-                    const float t = labels ? (c == lab ? t_hi : t_lo) : T[(size_t)row * ldt + c];
-                    if (type == 2) {
-                        if (o > 0.f) l += t * logf(o + TINY);
-                        d = t - o;
-                    } else if (type == 0) {
-                        l += (t - o) * (t - o);
-                        d = (t - o) * (-0.5f * (o * o - 1.0f));
-                    } else {
-                        l += (t - o) * (t - o);
-                        d = t - o;
-                    }
-                    if (o > bo) { bo = o; io = c; }
-                    if (t > bt) { bt = t; it = c; }
-                }
-                if (O) O[(size_t)row * ldo + c] = o;
-            }
-            if (c < ldd) D[(size_t)row * ldd + c] = (__bf16)d;
-        }
-        for (int c = 64 * NPL + lane; c < ldd; c += 64) D[(size_t)row * ldd + c] = (__bf16)0.f;
-        l = wave_sum(l);
-        wave_argmax(bo, io);
-        wave_argmax(bt, it);
-        if (valid && lane == 0) {
-            my_loss += (type == 2) ? -l / (float)n_out : 0.5f * l;
-            my_hit += (io == it) ? 1u : 0u;
-        }
-    }
-    block_reduce_store(my_loss, my_hit, loss_acc, correct);
-}
-
-/* wide outputs up to 256 classes (RRUFF: 230), FOUR rows per wave: 16 lanes per row,
- * lane i of a row group owning columns [16 i, 16 i + 16) (four float4 loads, two 16-byte
- * delta stores).  The five row reductions (max, sum, loss, two argmax) run over 16 lanes
- * (4 shuffle steps instead of 6) and for 4 rows at once; the one-row-per-wave kernel above
- * spent ~17 us on 16384 x 230 in these dependent reductions.  Needs ldz, ldd (and ldo)
- * multiples of 16, ldd <= 256. */
-__device__ __forceinline__ float g16_max(float v) {
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 16));
-    return v;
-}
-__device__ __forceinline__ float g16_sum(float v) {
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 16);
-    return v;
-}
-__device__ __forceinline__ void g16_argmax(float &v, int &i) {
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o, 16);
-        const int oi = __shfl_xor(i, o, 16);
-        if (oi >= 0 && (i < 0 || ov > v || (ov == v && oi < i))) {
-            v = ov;
-            i = oi;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void output_delta_q_kernel(const float *__restrict__ Z, int ldz,
-                                                             const float *__restrict__ T, int ldt,
-                                                             const int *__restrict__ labels, float t_hi, float t_lo,
-                                                             __bf16 *__restrict__ D, int ldd, float *__restrict__ O,
-                                                             int ldo, float *__restrict__ loss_acc,
-                                                             unsigned int *__restrict__ correct, int B, int n_valid,
-                                                             int n_out, int type) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int gi = lane & 15, c0 = 16 * gi;
-    float my_loss = 0.f;
-    unsigned int my_hit = 0;
-    for (int row0 = (blockIdx.x * 4 + wave) * 4; row0 < B; row0 += gridDim.x * 16) {
-        const int row = row0 + (lane >> 4);
-        const bool in = row < B, valid = row < n_valid;
-        const int lab = (labels && valid) ? labels[row] : -1;
-        float z[16];
-        if (in && c0 < ldz) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const float4 v = *(const float4 *)(Z + (size_t)row * ldz + c0 + 4 * j);
-                z[4 * j] = v.x;
-                z[4 * j + 1] = v.y;
-                z[4 * j + 2] = v.z;
-                z[4 * j + 3] = v.w;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 16; j++)
-            if (!in || c0 + j >= n_out) z[j] = -INFINITY;
-        float inv = 0.f, zmax = 0.f;
-        if (type == 2) {
-            zmax = z[0];
-#pragma unroll
-            for (int j = 1; j < 16; j++) zmax = fmaxf(zmax, z[j]);
-            zmax = g16_max(zmax);
-            float denom = 0.f;
-#pragma unroll
-            for (int j = 0; j < 16; j++) { /* z[j] <- e^{z - max}: computed once */
-                z[j] = c0 + j < n_out ? __expf(z[j] - zmax) : 0.f;
-                denom += z[j];
-            }
-            denom = g16_sum(denom);
-            /* reference: e^{z-1} / (TINY + sum e^{z-1}); shifted by m=zmax */
-            denom += __expf(fminf(logf(TINY) + 1.0f - zmax, 80.f));
-            inv = 1.0f / denom;
-        }
-        float bo = -INFINITY, bt = -INFINITY, l = 0.f;
-        int io = -1, it = -1;
-        typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-        bf16x8 dv[2];
-        float ov[16];
-#pragma unroll
-        for (int j = 0; j < 16; j++) {
-            const int c = c0 + j;
-            float d = 0.f, o = 0.f;
-            if (in && c < n_out) {
-                if (type == 2) o = z[j] * inv;
-                else if (type == 0) o = 2.0f / (1.0f + __expf(-z[j])) - 1.0f;
-                else o = z[j];
-                if (valid) {
-                    const float t = labels ? (c == lab ? t_hi : t_lo) : T[(size_t)row * ldt + c];
-                    if (type == 2) {
-                        if (t != 0.f && o > 0.f) l += t * logf(o + TINY); /* one-hot: one log per row */
-                        d = t - o;
-                    } else if (type == 0) {
-                        l += (t - o) * (t - o);
-                        d = (t - o) * (-0.5f * (o * o - 1.0f));
-                    } else {
-                        l += (t - o) * (t - o);
-                        d = t - o;
-                    }
-                    if (o > bo) { bo = o; io = c; }
-                    if (t > bt) { bt = t; it = c; }
-                }
-            }
-            ov[j] = o;
-            dv[j >> 3][j & 7] = (__bf16)d;
-        }
-        if (in && c0 < ldd) {
-            *(bf16x8 *)(D + (size_t)row * ldd + c0) = dv[0];
-            *(bf16x8 *)(D + (size_t)row * ldd + c0 + 8) = dv[1];
-        }
-        if (O && in && c0 < ldo) {
-#pragma unroll
-            for (int j = 0; j < 16; j++)
-                if (c0 + j < n_out) O[(size_t)row * ldo + c0 + j] = ov[j];
-        }
-        l = g16_sum(l);
-        g16_argmax(bo, io);
-        g16_argmax(bt, it);
-        if (valid && gi == 0) {
-            my_loss += (type == 2) ? -l / (float)n_out : 0.5f * l;
-            my_hit += (io == it) ? 1u : 0u;
-        }
-    }
-    block_reduce_store(my_loss, my_hit, loss_acc, correct);
-}
-
-/* very wide outputs (> 256 classes, e.g. the synthetic 4096-wide ANN): one wave per row,
- * every lane handling 4 consecutive columns per step (float4 Z / T loads, 8-byte delta
- * stores); needs ldz and ldd multiples of 4.  The scalar kernel below moved
- * 256 B per wave instruction and ran the 8192 x 4096 output at ~2 TB/s. */
-__global__ __launch_bounds__(256) void output_delta_v4_kernel(const float *__restrict__ Z, int ldz,
-                                                              const float *__restrict__ T, int ldt,
-                                                              const int *__restrict__ labels, float t_hi, float t_lo,
-                                                              __bf16 *__restrict__ D, int ldd, float *__restrict__ O,
-                                                              int ldo, float *__restrict__ loss_acc,
-                                                              unsigned int *__restrict__ correct, int B, int n_valid,
-                                                              int n_out, int type) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-    float my_loss = 0.f;
-    unsigned int my_hit = 0;
-    const int cend = ldd > n_out ? ldd : n_out;
-    for (int row = blockIdx.x * 4 + wave; row < B; row += gridDim.x * 4) {
-        const bool valid = row < n_valid;
-        const int lab = (labels && valid) ? labels[row] : -1;
-        const float *zr = Z + (size_t)row * ldz;
-        float zmax = -INFINITY, denom = 0.f;
-        if (type == 2) {
-            for (int c = 4 * lane; c < n_out; c += 256) {
-                const float4 v = *(const float4 *)(zr + c);
-                const float e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int r = 0; r < 4; r++)
-                    if (c + r < n_out) zmax = fmaxf(zmax, e[r]);
-            }
-            zmax = wave_max(zmax);
-            for (int c = 4 * lane; c < n_out; c += 256) {
-                const float4 v = *(const float4 *)(zr + c);
-                const float e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int r = 0; r < 4; r++)
-                    if (c + r < n_out) denom += __expf(e[r] - zmax);
-            }
-            denom = wave_sum(denom);
-            denom += __expf(fminf(logf(TINY) + 1.0f - zmax, 80.f));
-        }
-        const float inv = type == 2 ? 1.0f / denom : 0.f;
-        float bo = -INFINITY, bt = -INFINITY, l = 0.f;
-        int io = -1, it = -1;
-        for (int c = 4 * lane; c < cend; c += 256) {
-            float e[4] = {0.f, 0.f, 0.f, 0.f}, tv[4] = {t_lo, t_lo, t_lo, t_lo};
-            if (c < n_out) {
-                const float4 v = *(const float4 *)(zr + c);
-                e[0] = v.x; e[1] = v.y; e[2] = v.z; e[3] = v.w;
-                if (!labels && valid) {
-                    const float *tr = T + (size_t)row * ldt + c;
-                    if ((ldt & 3) == 0 && ((uintptr_t)T & 15) == 0) {
-                        const float4 w = *(const float4 *)tr;
-                        tv[0] = w.x; tv[1] = w.y; tv[2] = w.z; tv[3] = w.w;
-                    } else { /* unaligned target rows: scalar loads, same values */
-#pragma unroll
-                        for (int r = 0; r < 4; r++) tv[r] = c + r < n_out ? tr[r] : t_lo;
-                    }
-                }
-            }
-            bf16x4 dv;
-            float ov[4];
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int cc = c + r;
-                float d = 0.f, o = 0.f;
-                if (cc < n_out) {
-                    if (type == 2) o = __expf(e[r] - zmax) * inv;
-                    else if (type == 0) o = 2.0f / (1.0f + __expf(-e[r])) - 1.0f;
-                    else o = e[r];
-                    if (valid) {
-                        const float t = labels ? (cc == lab ? t_hi : t_lo) : tv[r];
-                        if (type == 2) {
-                            if (t != 0.f && o > 0.f) l += t * logf(o + TINY);
-                            d = t - o;
-                        } else if (type == 0) {
-                            l += (t - o) * (t - o);
-                            d = (t - o) * (-0.5f * (o * o - 1.0f));
-                        } else {
-                            l += (t - o) * (t - o);
-                            d = t - o;
-                        }
-                        if (o > bo) { bo = o; io = cc; }
-                        if (t > bt) { bt = t; it = cc; }
-                    }
-                }
-                ov[r] = o;
-                dv[r] = (__bf16)d;
-            }
-            if (c < ldd) *(bf16x4 *)(D + (size_t)row * ldd + c) = dv;
-            if (O && c < n_out) {
-#pragma unroll
-                for (int r = 0; r < 4; r++)
-                    if (c + r < n_out) O[(size_t)row * ldo + c + r] = ov[r];
-            }
-        }
-        l = wave_sum(l);
-        wave_argmax(bo, io);
-        wave_argmax(bt, it);
-        if (valid && lane == 0) {
-            my_loss += (type == 2) ? -l / (float)n_out : 0.5f * l;
-            my_hit += (io == it) ? 1u : 0u;
-        }
-    }
-    block_reduce_store(my_loss, my_hit, loss_acc, correct);
-}
-
-/* wide outputs: one WAVE per sample row, grid-stride */
+/* The output layer of a per-layer BF16 step: W lanes per row (64 / W rows per wave, 4 waves),
+ * lane li owning the V consecutive columns V li + j + W V step of its row.  STEPS > 0 keeps
+ * the row in registers (Z is read once; the row must fit W V STEPS columns), STEPS == 0
+ * streams it from memory in the max, denominator and output passes.  A lane adds its columns
+ * in ascending order and the row total is the butterfly over W lanes: the softmax bits of a
+ * form are fixed by (W, V).  With V % 4 == 0 and W > 1 the caller guarantees ldz % V == 0,
+ * ldd % DV == 0 and aligned Z / D (vector loads and stores); W == 1 knows ldd % 4 == 0 only. */
+template <int W, int V, int STEPS>
 __global__ __launch_bounds__(256) void output_delta_kernel(const float *__restrict__ Z, int ldz,
                                                            const float *__restrict__ T, int ldt,
                                                            const int *__restrict__ labels, float t_hi, float t_lo,
@@ -479,61 +153,161 @@ __global__ __launch_bounds__(256) void output_delta_kernel(const float *__restri
                                                            int ldo, float *__restrict__ loss_acc,
                                                            unsigned int *__restrict__ correct, int B, int n_valid,
                                                            int n_out, int type) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr bool ZVEC = V % 4 == 0 && W > 1;                     /* float4 loads of Z */
+    constexpr int DV = V % 8 == 0 && W > 1 ? 8 : V % 4 == 0 ? 4 : 1; /* columns per delta store */
+    constexpr int NS = STEPS > 0 ? STEPS : 1;
+    typedef __attribute__((ext_vector_type(DV > 1 ? DV : 2))) __bf16 bf16xd;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane % W;
+    const bool dense = labels == nullptr;
+    const bool tvec = V % 4 == 0 && (ldt & 3) == 0 && ((uintptr_t)T & 15) == 0;
     float my_loss = 0.f;
     unsigned int my_hit = 0;
-    for (int row = blockIdx.x * 4 + wave; row < B; row += gridDim.x * 4) {
+    /* the W lanes of a row leave the loop together, so the row reductions stay among live lanes */
+    for (int row = (blockIdx.x * 4 + wave) * (64 / W) + lane / W; row < B; row += gridDim.x * 4 * (64 / W)) {
         const bool valid = row < n_valid;
         const int lab = (labels && valid) ? labels[row] : -1;
-        float zmax = -INFINITY;
-        if (type == 2) {
-            for (int c = lane; c < n_out; c += 64) zmax = fmaxf(zmax, Z[(size_t)row * ldz + c]);
-            zmax = wave_max(zmax);
+        const float *zr = Z + (size_t)row * ldz;
+
+        /* the V values of one step at column c; -inf past the row's end */
+        auto load_z = [&](int c, float *z) __attribute__((always_inline)) {
+            if constexpr (ZVEC) { /* c < n_out <= ldz, both multiples of V: all V inside the row's stride */
+                if (c < n_out) {
+#pragma unroll
+                    for (int j = 0; j < V; j += 4) {
+                        const float4 v = *(const float4 *)(zr + c + j);
+                        z[j] = v.x; z[j + 1] = v.y; z[j + 2] = v.z; z[j + 3] = v.w;
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < V; j++)
+                    if (c + j >= n_out) z[j] = -INFINITY;
+            } else {
+#pragma unroll
+                for (int j = 0; j < V; j++) z[j] = c + j < n_out ? zr[c + j] : -INFINITY;
+            }
+        };
+
+        float z[NS * V];
+        if constexpr (STEPS > 0) {
+#pragma unroll
+            for (int s = 0; s < STEPS; s++) load_z(V * li + W * V * s, z + V * s);
         }
-        float denom = 0.f;
+        float inv = 0.f, zmax = -INFINITY;
         if (type == 2) {
-            for (int c = lane; c < n_out; c += 64) denom += __expf(Z[(size_t)row * ldz + c] - zmax);
-            denom = wave_sum(denom);
+            float denom = 0.f;
+            if constexpr (STEPS > 0) {
+#pragma unroll
+                for (int j = 0; j < NS * V; j++) zmax = fmaxf(zmax, z[j]);
+                zmax = row_max<W>(zmax);
+#pragma unroll
+                for (int j = 0; j < NS * V; j++) { /* z <- e^{z - zmax}: computed once */
+                    z[j] = V * li + W * V * (j / V) + j % V < n_out ? __expf(z[j] - zmax) : 0.f;
+                    denom += z[j];
+                }
+            } else {
+                for (int c = V * li; c < n_out; c += W * V) {
+                    load_z(c, z);
+#pragma unroll
+                    for (int j = 0; j < V; j++) zmax = fmaxf(zmax, z[j]);
+                }
+                zmax = row_max<W>(zmax);
+                for (int c = V * li; c < n_out; c += W * V) {
+                    load_z(c, z);
+#pragma unroll
+                    for (int j = 0; j < V; j++)
+                        if (c + j < n_out) denom += __expf(z[j] - zmax);
+                }
+            }
+            denom = row_sum<W>(denom);
             /* reference: e^{z-1} / (TINY + sum e^{z-1}); shifted by m=zmax */
             denom += __expf(fminf(logf(TINY) + 1.0f - zmax, 80.f));
+            inv = 1.0f / denom;
         }
-        const float inv = type == 2 ? 1.0f / denom : 0.f;
-        float bo = -INFINITY, bt = -INFINITY;
-        int io = -1, it = -1;
-        float l = 0.f;
-        for (int c = lane; c < (ldd > n_out ? ldd : n_out); c += 64) {
-            float d = 0.f;
-            if (c < n_out) {
-                const float z = Z[(size_t)row * ldz + c];
-                float o;
-                if (type == 2) o = __expf(z - zmax) * inv;
-                else if (type == 0) o = 2.0f / (1.0f + __expf(-z)) - 1.0f;
-                else o = z;
-                if (valid) {
-                    const float t = labels ? (c == lab ? t_hi : t_lo) : T[(size_t)row * ldt + c];
-                    if (type == 2) {
-                        if (o > 0.f) l += t * logf(o + TINY);
-                        d = t - o;
-                    } else if (type == 0) {
-                        l += (t - o) * (t - o);
-                        d = (t - o) * (-0.5f * (o * o - 1.0f));
-                    } else {
-                        l += (t - o) * (t - o);
-                        d = t - o;
-                    }
-                    if (o > bo) { bo = o; io = c; }
-                    if (t > bt) { bt = t; it = c; }
+
+        OdLane a;
+        __bf16 *dr = D + (size_t)row * ldd;
+        /* DV columns from c: deltas (zero past n_out and in padding rows) stored as produced */
+        auto store_d = [&](int c, const __bf16 *dv) __attribute__((always_inline)) {
+            if (c < ldd) {
+                if constexpr (DV == 1) dr[c] = dv[0];
+                else {
+                    bf16xd v;
+#pragma unroll
+                    for (int r = 0; r < DV; r++) v[r] = dv[r];
+                    *(bf16xd *)(dr + c) = v;
                 }
-                if (O) O[(size_t)row * ldo + c] = o;
             }
-            if (c < ldd) D[(size_t)row * ldd + c] = (__bf16)d;
+        };
+        /* the V columns of one step from c, x = z or the e^{z - zmax} kept in registers */
+        auto emit = [&](int type, int c, const float *x) __attribute__((always_inline)) {
+#pragma unroll
+            for (int k = 0; k < V; k += DV) {
+                __bf16 dv[DV] = {};
+                if (c + k < n_out) {
+                    float tv[DV];
+#pragma unroll
+                    for (int r = 0; r < DV; r++) tv[r] = t_lo;
+                    if (dense && valid) {
+                        const float *tr = T + (size_t)row * ldt + c + k;
+                        if (tvec) {
+                            if constexpr (V % 4 == 0) {
+#pragma unroll
+                                for (int q = 0; q < DV; q += 4)
+                                    if (c + k + q < n_out) {
+                                        const float4 w = *(const float4 *)(tr + q);
+                                        tv[q] = w.x; tv[q + 1] = w.y; tv[q + 2] = w.z; tv[q + 3] = w.w;
+                                    }
+                            }
+                        } else { /* scalar loads of the same values: unaligned target rows, V == 1 */
+#pragma unroll
+                            for (int r = 0; r < DV; r++)
+                                if (c + k + r < n_out) tv[r] = tr[r];
+                        }
+                    }
+#pragma unroll
+                    for (int r = 0; r < DV; r++) {
+                        const int cc = c + k + r;
+                        if (cc < n_out) {
+                            const float xe = (STEPS == 0 && type == 2) ? __expf(x[k + r] - zmax) : x[k + r];
+                            float o;
+                            dv[r] = (__bf16)od_element(type, xe, inv, valid, dense, tv[r], lab, t_hi, t_lo, cc, o, a);
+                            if (O) O[(size_t)row * ldo + cc] = o;
+                        }
+                    }
+                }
+                store_d(c + k, dv);
+            }
+        };
+        int c = V * li;
+        if constexpr (STEPS > 0) {
+            /* compiled once per net type: left to a choice per column, the compiler computes all
+             * three outputs and selects (the 16-lane form ran 15% longer); the streamed forms
+             * below are bound by memory and would pay for three loops with occupancy */
+            auto pass = [&](int ty) __attribute__((always_inline)) {
+#pragma unroll
+                for (int s = 0; s < STEPS; s++, c += W * V) emit(ty, c, z + V * s);
+            };
+            if (type == 2) pass(2);
+            else if (type == 0) pass(0);
+            else pass(1);
+        } else {
+            for (; c < n_out; c += W * V) {
+                load_z(c, z);
+                emit(type, c, z);
+            }
         }
-        l = wave_sum(l);
-        wave_argmax(bo, io);
-        wave_argmax(bt, it);
-        if (valid && lane == 0) {
-            my_loss += (type == 2) ? -l / (float)n_out : 0.5f * l;
-            my_hit += (io == it) ? 1u : 0u;
+        /* zero fill of the columns after the last one that held an output, up to ldd */
+        for (; c < ldd; c += W * V) {
+            __bf16 zero[DV] = {};
+#pragma unroll
+            for (int k = 0; k < V; k += DV) store_d(c + k, zero);
+        }
+        a.l = row_sum<W>(a.l);
+        row_argmax<W>(a.bo, a.io);
+        row_argmax<W>(a.bt, a.it);
+        if (valid && li == 0) {
+            my_loss += (type == 2) ? -a.l / (float)n_out : 0.5f * a.l;
+            my_hit += (a.io == a.it) ? 1u : 0u;
         }
     }
     block_reduce_store(my_loss, my_hit, loss_acc, correct);
@@ -864,12 +638,6 @@ inline int grid_for(long n, int bs) {
 
 }  // namespace
 
-/* HPNN_OD_WAVE=1: one row per wave for wide outputs (the kernel before output_delta_q) */
-static bool od_wave_mode() {
-    static const bool v = [] { const char *e = getenv("HPNN_OD_WAVE"); return e && e[0] == '1'; }();
-    return v;
-}
-
 /* order-independent 64-bit digest of a buffer's 4-byte words: the wrapping sum over i of a
  * murmur3 finalizer of (word << 32 | i).  Equal buffers give equal digests on every device
  * and run (integer adds commute); one changed bit changes it.  Used to check that data-
@@ -964,37 +732,25 @@ extern "C" int hpnn_output_delta(const float *Z, int ldz, const float *T, int ld
                                  hipStream_t stream) {
     if (B <= 0 || n_out <= 0 || ldz < n_out || ldd < n_out) return -1;
     if (!labels && !T) return -1;
-    if (ldd <= 32 && ldd % 4 == 0) {
-        const int grid = (B + 255) / 256 < 256 ? (B + 255) / 256 : 256;
-        hipLaunchKernelGGL(output_delta_rows_kernel<32>, dim3(grid), dim3(256), 0, stream, Z, ldz, T, ldt, labels,
-                           t_hi, t_lo, (__bf16 *)D, ldd, O, ldo, loss_acc, correct, B, n_valid, n_out, type);
-    } else if (n_out > 64 && ldz % 16 == 0 && ldd % 16 == 0 && ldd <= 256 && ldz >= ldd && (!O || ldo % 16 == 0) &&
-               !od_wave_mode()) {
-        /* four rows per wave (16 lanes per row): the grid covers the batch */
-        const int grid = (B + 15) / 16 < 4096 ? (B + 15) / 16 : 4096;
-        hipLaunchKernelGGL(output_delta_q_kernel, dim3(grid), dim3(256), 0, stream, Z, ldz, T, ldt, labels, t_hi, t_lo,
-                           (__bf16 *)D, ldd, O, ldo, loss_acc, correct, B, n_valid, n_out, type);
-    } else if (n_out <= 256) {
-        /* one row per wave: the grid covers the batch (up to 16 waves per CU) */
-        const int grid = (B + 3) / 4 < 4096 ? (B + 3) / 4 : 4096;
-#define HPNN_OD(NPL_)                                                                                              \
-    hipLaunchKernelGGL(output_delta_reg_kernel<NPL_>, dim3(grid), dim3(256), 0, stream, Z, ldz, T, ldt, labels, t_hi, \
-                       t_lo, (__bf16 *)D, ldd, O, ldo, loss_acc, correct, B, n_valid, n_out, type)
-        if (n_out <= 64) HPNN_OD(1);
-        else if (n_out <= 128) HPNN_OD(2);
-        else if (n_out <= 192) HPNN_OD(3);
-        else HPNN_OD(4);
+    /* the shape rule: which mapping of output_delta_kernel<W, V, STEPS> takes the row */
+    const auto grid = [B](int rows_per_block, int cap) {
+        const int g = (B + rows_per_block - 1) / rows_per_block;
+        return dim3(g < cap ? g : cap);
+    };
+#define HPNN_OD(W_, V_, STEPS_, GRID_)                                                                          \
+    hipLaunchKernelGGL((output_delta_kernel<W_, V_, STEPS_>), GRID_, dim3(256), 0, stream, Z, ldz, T, ldt, labels, \
+                       t_hi, t_lo, (__bf16 *)D, ldd, O, ldo, loss_acc, correct, B, n_valid, n_out, type)
+    if (ldd <= 32 && ldd % 4 == 0) HPNN_OD(1, 32, 1, grid(256, 256));
+    else if (n_out > 64 && ldz % 16 == 0 && ldd % 16 == 0 && ldd <= 256 && ldz >= ldd && (!O || ldo % 16 == 0))
+        HPNN_OD(16, 16, 1, grid(16, 4096)); /* four rows per wave: the grid covers the batch */
+    else if (n_out <= 64) HPNN_OD(64, 1, 1, grid(4, 4096)); /* one row per wave: up to 16 waves per CU */
+    else if (n_out <= 128) HPNN_OD(64, 1, 2, grid(4, 4096));
+    else if (n_out <= 192) HPNN_OD(64, 1, 3, grid(4, 4096));
+    else if (n_out <= 256) HPNN_OD(64, 1, 4, grid(4, 4096));
+    else if (ldz % 4 == 0 && ldd % 4 == 0 && ((uintptr_t)Z & 15) == 0 && ((uintptr_t)D & 7) == 0)
+        HPNN_OD(64, 4, 0, grid(4, 4096));
+    else HPNN_OD(64, 1, 0, grid(4, 4096));
 #undef HPNN_OD
-    } else if (ldz % 4 == 0 && ldd % 4 == 0 && ((uintptr_t)Z & 15) == 0 && ((uintptr_t)D & 7) == 0 &&
-               !od_wave_mode()) {
-        const int grid = (B + 3) / 4 < 4096 ? (B + 3) / 4 : 4096;
-        hipLaunchKernelGGL(output_delta_v4_kernel, dim3(grid), dim3(256), 0, stream, Z, ldz, T, ldt, labels, t_hi,
-                           t_lo, (__bf16 *)D, ldd, O, ldo, loss_acc, correct, B, n_valid, n_out, type);
-    } else {
-        const int grid = (B + 3) / 4 < 4096 ? (B + 3) / 4 : 4096;
-        hipLaunchKernelGGL(output_delta_kernel, dim3(grid), dim3(256), 0, stream, Z, ldz, T, ldt, labels, t_hi,
-                           t_lo, (__bf16 *)D, ldd, O, ldo, loss_acc, correct, B, n_valid, n_out, type);
-    }
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

@@ -331,20 +331,50 @@ def test_gemm_tn_integer_exact(gpu):
     assert torch.equal(G, ops.ref_gemm_tn(D, H))
 
 
+def _first_argmax(o):
+    """first index of each row's maximum (torch.argmax leaves the choice among ties open)"""
+    cols = torch.arange(o.shape[1], device=o.device).expand_as(o)
+    return torch.where(o == o.max(1, keepdim=True).values, cols, o.shape[1]).min(1).values
+
+
 @pytest.mark.parametrize("net_type", [ops.TYPE_SNN, ops.TYPE_ANN, ops.TYPE_LNN])
 @pytest.mark.parametrize("n_out,ldz,B", [(10, 32, 256), (230, 256, 256), (64, 64, 256), (100, 128, 256),
                                         (150, 160, 256), (256, 256, 256), (300, 320, 256), (230, 256, 20000),
-                                        (4096, 4096, 512), (1001, 1024, 300)])
+                                        (4096, 4096, 512), (1001, 1024, 300),
+                                        # one lane per row: full width with a partial second block; ld < 32
+                                        (32, 32, 300), (5, 8, 77),
+                                        # one wave per row in registers, 1..4 columns per lane; (256, 264):
+                                        # zero fill past the 256 register columns
+                                        (40, 48, 77), (33, 64, 300), (100, 104, 77), (150, 152, 77),
+                                        (230, 232, 77), (256, 264, 77),
+                                        # 16 lanes per row: lanes past ld; rows >= B inside the last wave
+                                        (65, 80, 77), (256, 256, 77),
+                                        # streamed, 4 columns per lane: dense T has ldt = n_out, so 257 takes
+                                        # the scalar T loads and 300 the 16-byte ones
+                                        (257, 260, 77), (300, 320, 77),
+                                        # streamed, one column per lane (ld no multiple of 4)
+                                        (300, 301, 77), (257, 258, 77)])
 def test_output_delta(gpu, net_type, n_out, ldz, B):
+    """every arm of hpnn_output_delta's shape rule (csrc/gpu/kernels_misc.hip) and the edges of each"""
     n_valid = B - 56
     torch.manual_seed(n_out + net_type)
     Z = _rand(B, ldz, scale=3.0)
     labels = torch.randint(0, n_out, (B,), device="cuda", dtype=torch.int32)
+    # every third row has its maximum twice, one column or half a row apart (inside one lane's
+    # columns and across lanes), and is labelled with the lower one: a hit only if ties go to
+    # the first index
+    r = torch.arange(0, B, 3, device="cuda")
+    c1 = r % n_out
+    c2 = (c1 + torch.where(r % 2 == 1, 1, n_out // 2)) % n_out
+    Z[r, c1] = Z[r, c2] = 10.0
+    labels[r] = torch.minimum(c1, c2).int()
+    if net_type == ops.TYPE_SNN:
+        Z[2::5, :n_out] -= 40.0  # e^{z-1} sums to ~1e-17 here: the TINY term decides the softmax
     hi, lo = (1.0, 0.0) if net_type == ops.TYPE_SNN else (1.0, -1.0)
     T = torch.full((B, n_out), lo, device="cuda")
     T[torch.arange(B), labels.long()] = hi
-    D = torch.empty(B, ldz, dtype=torch.bfloat16, device="cuda")
-    O = torch.empty(B, ldz, device="cuda")
+    D = torch.full((B, ldz), 7.0, dtype=torch.bfloat16, device="cuda")
+    O = torch.full((B, ldz), 7.0, device="cuda")
     stats = torch.zeros(64, 16, device="cuda")  # HPNN_STAT_SLOTS x HPNN_STAT_STRIDE
     ops.output_delta(Z, n_out, net_type, D, labels=labels, t_hi=hi, t_lo=lo, n_valid=n_valid, O=O,
                      loss_acc=stats[0, 0:1], correct=stats[0, 1:2])
@@ -352,17 +382,45 @@ def test_output_delta(gpu, net_type, n_out, ldz, B):
     corr = stats[:, 1].contiguous().view(torch.int32).sum()
     o, d, l = ops.ref_output(Z, n_out, net_type, T)
     assert (O[:, :n_out] - o).abs().max().item() < 1e-5
+    if ldz > n_out:
+        assert (O[:, n_out:] == 7.0).all()  # O is written up to n_out only
     assert (D[:n_valid, :n_out].float() - d[:n_valid]).abs().max().item() < 1e-2 * max(1, d.abs().max().item())
     assert D[n_valid:].float().abs().max().item() == 0.0
     if ldz > n_out:
         assert D[:, n_out:].float().abs().max().item() == 0.0
     assert abs(loss.item() - l[:n_valid].sum().item()) < 1e-3 * max(1.0, abs(l[:n_valid].sum().item()))
-    hits = (o[:n_valid].argmax(1) == labels[:n_valid].long()).sum().item()
-    assert corr.item() == hits
+    hits = (_first_argmax(o[:n_valid]) == labels[:n_valid].long()).sum().item()
+    assert 0 < hits < n_valid and corr.item() == hits
     # dense targets give the same delta
-    D2 = torch.empty_like(D)
+    D2 = torch.full_like(D, 7.0)
     ops.output_delta(Z, n_out, net_type, D2, T=T, n_valid=n_valid)
     assert torch.equal(D, D2)
+
+
+@pytest.mark.parametrize("net_type", [ops.TYPE_ANN, ops.TYPE_LNN])
+@pytest.mark.parametrize("n_out,lds", [(230, (256, 232)), (300, (320, 301))])
+def test_output_delta_forms_agree(gpu, net_type, n_out, lds):
+    """ANN / LNN outputs depend on no row reduction, so the forms of hpnn_output_delta give the
+    same bits on the same row: 16 lanes per row (ld 256) against one wave per row in registers
+    (ld 232), and the two streamed forms, 4 columns per lane (ld 320) against one (ld 301)"""
+    B, n_valid = 77, 60
+    torch.manual_seed(n_out + net_type)
+    Zs = _rand(B, n_out, scale=3.0)
+    labels = torch.randint(0, n_out, (B,), device="cuda", dtype=torch.int32)
+    res = []
+    for ld in lds:
+        Z = torch.zeros(B, ld, device="cuda")
+        Z[:, :n_out] = Zs
+        D = torch.full((B, ld), 7.0, dtype=torch.bfloat16, device="cuda")
+        O = torch.full((B, ld), 7.0, device="cuda")
+        stats = torch.zeros(64, 16, device="cuda")
+        ops.output_delta(Z, n_out, net_type, D, labels=labels, t_hi=1.0, t_lo=-1.0, n_valid=n_valid, O=O,
+                         loss_acc=stats[0, 0:1], correct=stats[0, 1:2])
+        res.append((D[:, :n_out].clone(), O[:, :n_out].clone(),
+                    stats[:, 1].contiguous().view(torch.int32).sum().item()))
+    assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
+    assert res[0][2] == res[1][2]
+    assert res[0][0][:n_valid].float().abs().max().item() > 0
 
 
 @pytest.mark.parametrize("momentum", [False, True])
