@@ -20,17 +20,8 @@
  *    (A rows 0-127, A rows 128-255, B rows 0-127, B rows 128-255), 128 KiB total, filled by
  *    LDS-DMA (global_load_lds_dwordx4) with the swizzle of nt_off<8> applied on the source
  *    address (conflict-free ds_read_b128);
- *  - one iteration = 2 K-tiles = 8 phases; phase p computes one quadrant:
- *        [ds_reads of the quadrant's new operands; LDS-DMA issue; counted vmcnt]
- *        s_barrier; lgkmcnt(0); setprio 1; 16 MFMAs; setprio 0; s_barrier
- *    quadrant order (0,0) (0,1) (1,1) (1,0): 12, 4, 8 and 0 ds_read_b128 per phase;
- *  - the waves of M-half 1 run one barrier behind those of M-half 0 (one extra barrier at
- *    the start), so on every SIMD one wave issues MFMAs while the other reads LDS;
- *  - prefetch: a half-tile is restaged two phases after its last read (the stagger makes
- *    one phase unsafe) and waited for with a counted vmcnt one phase before its first
- *    read, never vmcnt(0) in the steady state:
- *        P1: A(o) -> O     P4: B(e+2) -> E, vmcnt(4)     P5: A(e+2) -> E
- *        P8: B(o+2) -> O, vmcnt(4)                       (e = 2i, o = 2i + 1)
+ *  - one iteration = 2 K-tiles = 8 phases, one quadrant per phase, the two M-halves of the
+ *    workgroup one barrier apart (pipe8 below: the one schedule of the NT and TN kernels);
  *  - XCD-aware block order: each XCD gets a contiguous run of output tiles (bijective for
  *    any grid), so neighbouring tiles that share A / B panels share that XCD's L2.
  * Requires M % 256 == 0, N % 256 == 0, K % 128 == 0.
@@ -40,6 +31,7 @@
 #include <stdlib.h>
 
 #include <mutex>
+#include <type_traits>
 
 #include "kernels.h"
 
@@ -63,6 +55,119 @@ __device__ __forceinline__ void vm_wait() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
+/* XCD-aware, bijective for any grid: blocks b, b + 8, b + 16, ... (one XCD) take consecutive
+ * work items */
+__device__ __forceinline__ int xcd_remap(int bid, int total) {
+    const int xcd = bid & 7, q8 = total >> 3, r8 = total & 7;
+    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+}
+
+/* The 8-phase schedule over KT (even) K-tiles, K-tile kt in LDS buffer kt & 1.  The kernel
+ * hands in what its operands mean:
+ *   read_a(kt, mi)  ds_reads of A quadrant mi into the A registers
+ *   read_b(kt, ni)  ds_reads of B quadrant ni into B register slot ni
+ *   stage_a(kt), stage_b(kt)   LDS-DMA of K-tile kt's A / B half-tiles (stage_b: 4 loads per wave)
+ *   mma(mi, ni)     the 16 MFMAs of quadrant (mi, ni) from the A registers and slot ni
+ * MQ: M-quadrants per wave (2: the 128 x 64 wave tile; 1: TN with 128-wide tiles).
+ *  - phase p computes one quadrant:
+ *        [ds_reads of the quadrant's new operands; LDS-DMA issue; counted vmcnt]
+ *        s_barrier; lgkmcnt(0); setprio 1; 16 MFMAs; setprio 0; s_barrier
+ *    quadrant order (0,0) (0,1) (1,1) (1,0): 12, 4, 8 and 0 ds_read_b128 per phase (NT); MQ 1:
+ *    (0,0) (0,1), 4 phases per iteration;
+ *  - the waves of M-half 1 run one barrier behind those of M-half 0 (one extra barrier at
+ *    the start, paired at the end), so on every SIMD one wave issues MFMAs while the other
+ *    reads LDS;
+ *  - prefetch: a half-tile is restaged two phases after its last read (the stagger makes
+ *    one phase unsafe) and waited for with a counted vmcnt one phase before its first
+ *    read, never vmcnt(0) in the steady state -- vmcnt(4) leaves only the B loads just
+ *    issued in flight.  In K-tile kt's phases (e = 2i, o = 2i + 1: P1-P4 / P5-P8):
+ *        first: A(kt + 1) into the other buffer, whose A was last read in P3 / P7 of K-tile
+ *               kt - 1
+ *        last:  B(kt + 2) into this buffer, whose B was last read in the second phase, then
+ *               vmcnt(4): A(kt + 1) has landed, B(kt + 1) did a K-tile ago
+ *    A wave's wait covers its own loads only: the other waves see them after the wait AND a
+ *    barrier, and the waves one barrier behind have not reached that wait one barrier
+ *    later -- hence a whole phase (two barriers) between the wait and the first read.
+ *  - MQ 1 has two phases per K-tile, which leaves no room for both halves of that rule: B is
+ *    restaged right after the phase of its last read (the loads take far longer to land than
+ *    the reads in flight need), and everything in flight -- A(kt + 1), B(kt + 1) -- is waited
+ *    for with vmcnt(0) before the second phase, a whole phase before its first read.  (With
+ *    the wait after the second phase a wave read the next K-tile right behind its own wait,
+ *    pieces of slower waves included: a K-tile now and then was read before it had landed.) */
+template <int MQ, class RA, class RB, class SA, class SB, class MM>
+__device__ __forceinline__ void pipe8(int KT, int wm, RA read_a, RB read_b, SA stage_a, SB stage_b, MM mma) {
+    auto phase = [&](int mi, int ni) __attribute__((always_inline)) {
+        __builtin_amdgcn_s_barrier();
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_setprio(1);
+        mma(mi, ni);
+        __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+    };
+    /* na: K-tile kt + 1 exists (A restaged), nb: K-tile kt + 2 exists (B restaged) */
+    auto ktile = [&](int kt, bool na, bool nb) __attribute__((always_inline)) {
+        read_a(kt, 0);
+        read_b(kt, 0);
+        if (na) stage_a(kt + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        phase(0, 0);
+        read_b(kt, 1);
+        if constexpr (MQ == 1) vm_wait<0>(); /* K-tile kt + 1 complete */
+        __builtin_amdgcn_sched_barrier(0);
+        phase(0, 1);
+        if constexpr (MQ == 2) {
+            read_a(kt, 1);
+            __builtin_amdgcn_sched_barrier(0);
+            phase(1, 1);
+            if (nb) { /* K-tile kt + 1 complete */
+                stage_b(kt + 2);
+                vm_wait<4>();
+            } else {
+                vm_wait<0>();
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            phase(1, 0);
+        } else if (nb) {
+            stage_b(kt + 2);
+        }
+    };
+    /* prologue: K-tile 0 (A, B) and B of K-tile 1; K-tile 0 landed everywhere */
+    stage_a(0);
+    stage_b(0);
+    stage_b(1);
+    vm_wait<4>();
+    __builtin_amdgcn_s_barrier();
+    if (wm == 1) __builtin_amdgcn_s_barrier(); /* the stagger */
+    for (int e = 0; e < KT; e += 2) {
+        const bool ne = e + 2 < KT, no = e + 3 < KT;
+        ktile(e, true, ne);
+        ktile(e + 1, ne, no);
+    }
+    if (wm == 0) __builtin_amdgcn_s_barrier(); /* pair the stagger barrier */
+}
+
+/* 4 consecutive features f.. of sample b: the epilogue (aux = h for f'(h)), then one store */
+template <int EPI, bool CF32>
+__device__ __forceinline__ void epi_store4(void *C, int ldc, const __bf16 *aux, int ldaux, int b, int f, f32x4 v) {
+    if constexpr (EPI == HPNN_EPI_ACT) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) v[r] = hpnn::bipolar(v[r]);
+    } else if constexpr (EPI == HPNN_EPI_DACT) {
+        const bf16x4 h = *(const bf16x4 *)(aux + (size_t)b * ldaux + f);
+#pragma unroll
+        for (int r = 0; r < 4; r++) v[r] *= hpnn::dbipolar((float)h[r]);
+    }
+    if constexpr (CF32) {
+        *(f32x4 *)((float *)C + (size_t)b * ldc + f) = v;
+    } else {
+        bf16x4 o;
+#pragma unroll
+        for (int r = 0; r < 4; r++) o[r] = (__bf16)v[r];
+        *(bf16x4 *)((__bf16 *)C + (size_t)b * ldc + f) = o;
+    }
+}
 
 template <int EPI, bool CF32>
 __global__ __launch_bounds__(512) void gemm_nt8_kernel(const __bf16 *__restrict__ A, int lda,
@@ -73,10 +178,7 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(const __bf16 *__restrict_
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3; /* wm = stagger group */
-    /* XCD-aware, bijective: blocks b, b+8, b+16, ... (one XCD) take consecutive tiles */
-    const int total = ntiles * splits;
-    const int bid = blockIdx.x, xcd = bid & 7, q8 = total >> 3, r8 = total & 7;
-    const int w = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const int w = xcd_remap(blockIdx.x, ntiles * splits);
     /* split-K (splits > 1, EPI_NONE into FP32 slabs cstride floats apart): split s takes
      * K-tiles [s KT, (s + 1) KT) */
     const int tile = w % ntiles, split = w / ntiles;
@@ -118,149 +220,57 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(const __bf16 *__restrict_
                 for (int i = 0; i < 2; i++) acc[a][b][j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int r16 = lane & 15, q = lane >> 4;
-    /* operand registers, flattened: ra[j * 2 + kk] (4 frags x 2 k32), rb[i * 2 + kk] */
-    bf16x8 ra[8], rb0[4], rb1[4];
-    auto read_a = [&](const char *buf, int mi) __attribute__((always_inline)) {
-        const char *img = buf + wm * HALF;
+    /* operand registers, flattened: ra[j * 2 + kk] (4 frags x 2 k32), rb[ni][i * 2 + kk] */
+    bf16x8 ra[8], rb[2][4];
+    auto read_a = [&](int kt, int mi) __attribute__((always_inline)) {
+        const char *img = lds + (kt & 1) * KBUF + wm * HALF;
 #pragma unroll
         for (int j = 0; j < 4; j++)
 #pragma unroll
             for (int kk = 0; kk < 2; kk++)
                 ra[j * 2 + kk] = *(const bf16x8 *)(img + off8(mi * 64 + j * 16 + r16, kk * 4 + q));
-    
     };
-    auto read_b = [&](const char *buf, int ni, bf16x8 (&rb)[4]) __attribute__((always_inline)) {
-        const char *img = buf + (2 + (wn >> 1)) * HALF;
+    auto read_b = [&](int kt, int ni) __attribute__((always_inline)) {
+        const char *img = lds + (kt & 1) * KBUF + (2 + (wn >> 1)) * HALF;
 #pragma unroll
         for (int i = 0; i < 2; i++)
 #pragma unroll
             for (int kk = 0; kk < 2; kk++)
-                rb[i * 2 + kk] = *(const bf16x8 *)(img + off8((wn & 1) * 64 + ni * 32 + i * 16 + r16, kk * 4 + q));
-    
+                rb[ni][i * 2 + kk] =
+                    *(const bf16x8 *)(img + off8((wn & 1) * 64 + ni * 32 + i * 16 + r16, kk * 4 + q));
     };
-    auto mma = [&](int mi, int ni, const bf16x8 (&rb)[4]) __attribute__((always_inline)) {
-        __builtin_amdgcn_s_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
+    auto mma = [&](int mi, int ni) __attribute__((always_inline)) {
 #pragma unroll
         for (int kk = 0; kk < 2; kk++)
 #pragma unroll
             for (int j = 0; j < 4; j++)
 #pragma unroll
                 for (int i = 0; i < 2; i++)
-                    acc[mi][ni][j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rb[i * 2 + kk], ra[j * 2 + kk],
+                    acc[mi][ni][j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rb[ni][i * 2 + kk], ra[j * 2 + kk],
                                                                                 acc[mi][ni][j][i], 0, 0, 0);
-    
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
     };
+    pipe8<2>(
+        KT, wm, read_a, read_b,
+        [&](int kt) __attribute__((always_inline)) {
+            stage(0, kt);
+            stage(1, kt);
+        },
+        [&](int kt) __attribute__((always_inline)) {
+            stage(2, kt);
+            stage(3, kt);
+        },
+        mma);
 
-    /* prologue: K-tile 0 (A, B) -> E, B of K-tile 1 -> O; K-tile 0 landed everywhere */
-    stage(0, 0);
-    stage(1, 0);
-    stage(2, 0);
-    stage(3, 0);
-    stage(2, 1);
-    stage(3, 1);
-    vm_wait<4>();
-    __builtin_amdgcn_s_barrier();
-    if (wm == 1) __builtin_amdgcn_s_barrier(); /* the stagger */
-
-    for (int e = 0; e < KT; e += 2) {
-        const int o = e + 1;
-        const bool ne = e + 2 < KT, no = o + 2 < KT;
-        const char *bE = lds + (e & 1) * KBUF, *bO = lds + (o & 1) * KBUF;
-        /* P1 */
-        read_a(bE, 0);
-        read_b(bE, 0, rb0);
-        stage(0, o);
-        stage(1, o);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(0, 0, rb0);
-        /* P2 */
-        read_b(bE, 1, rb1);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(0, 1, rb1);
-        /* P3 */
-        read_a(bE, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(1, 1, rb1);
-        /* P4: restage E's B for K-tile e+2; K-tile o complete */
-        if (ne) {
-            stage(2, e + 2);
-            stage(3, e + 2);
-            vm_wait<4>();
-        } else {
-            vm_wait<0>();
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        mma(1, 0, rb0);
-        /* P5 */
-        read_a(bO, 0);
-        read_b(bO, 0, rb0);
-        if (ne) {
-            stage(0, e + 2);
-            stage(1, e + 2);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        mma(0, 0, rb0);
-        /* P6 */
-        read_b(bO, 1, rb1);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(0, 1, rb1);
-        /* P7 */
-        read_a(bO, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(1, 1, rb1);
-        /* P8: restage O's B for K-tile o+2; K-tile e+2 complete */
-        if (no) {
-            stage(2, o + 2);
-            stage(3, o + 2);
-            vm_wait<4>();
-        } else {
-            vm_wait<0>();
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        mma(1, 0, rb0);
-    }
-    if (wm == 0) __builtin_amdgcn_s_barrier(); /* pair the stagger barrier */
-
-    /* 4 consecutive features f.. of sample b per store */
-    auto emit = [&](int b, int f, f32x4 v) __attribute__((always_inline)) {
-        if constexpr (EPI == HPNN_EPI_ACT) {
-#pragma unroll
-            for (int r = 0; r < 4; r++) v[r] = hpnn::bipolar(v[r]);
-        } else if constexpr (EPI == HPNN_EPI_DACT) {
-            const bf16x4 h = *(const bf16x4 *)(aux + (size_t)b * ldaux + f);
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const float y = (float)h[r];
-                v[r] *= -0.5f * (y * y - 1.0f);
-            }
-        }
-        if constexpr (CF32) {
-            *(f32x4 *)((float *)C + (size_t)b * ldc + f) = v;
-        } else {
-            bf16x4 o;
-#pragma unroll
-            for (int r = 0; r < 4; r++) o[r] = (__bf16)v[r];
-            *(bf16x4 *)((__bf16 *)C + (size_t)b * ldc + f) = o;
-        }
-    };
 #pragma unroll
     for (int mi = 0; mi < 2; mi++)
 #pragma unroll
-        for (int ni = 0; ni < 2; ni++) {
+        for (int ni = 0; ni < 2; ni++)
 #pragma unroll
             for (int j = 0; j < 4; j++)
 #pragma unroll
                 for (int i = 0; i < 2; i++)
-                    emit(m0 + wm * 128 + mi * 64 + j * 16 + r16, n0 + wn * 64 + ni * 32 + i * 16 + 4 * q,
-                         acc[mi][ni][j][i]);
-        
-        }
+                    epi_store4<EPI, CF32>(C, ldc, aux, ldaux, m0 + wm * 128 + mi * 64 + j * 16 + r16,
+                                          n0 + wn * 64 + ni * 32 + i * 16 + 4 * q, acc[mi][ni][j][i]);
 }
 
 /* ---------------------------------------------------------------------- */
@@ -286,6 +296,64 @@ struct Tn8Upd {
 };
 
 constexpr unsigned long long TN8_TIMEOUT = 1000000000ULL; /* wall-clock ticks (~10 s) */
+
+/* The step on W[n][m .. m + 3] (idx = their offset in W32 / V32 / Wb) from the gradient g and
+ * the loaded w, v:  v += lr * (g * scale); w += v; v *= alpha  (no momentum: w += lr * (g *
+ * scale)), then the W32 / V32 stores, the BF16 copy and the scatter into the transposed copy
+ * Wt[mt + r][nt], row stride ldt (W^T itself, or MODE 1's LDS image of its wave tile).
+ * FMA: the side job (true) spells the contraction out, fma(lr, g * scale, v), which is what
+ * sgd_tile (kernels_misc.hip) compiles to for the separate update launch it stands in for (a
+ * free choice of the compiler measured 1 ulp apart on a few elements).  MODE 1 and MODE 2
+ * (false) keep the plain expression: there the compiler contracts it for some elements of a
+ * float4 and not for others (MODE 1 with momentum: the last two of the four), so spelling it
+ * out either way changes their results (measured: profiles/8ph_refactor/README.md) */
+template <bool FMA>
+__device__ __forceinline__ void sgd_step4(const Tn8Upd &u, float *W32, float *V32, __bf16 *Wb, size_t idx, f32x4 g,
+                                          f32x4 ww, f32x4 vv, __bf16 *Wt, int ldt, int mt, int nt) {
+    auto axpy = [&](float g1, float x) __attribute__((always_inline)) {
+        if constexpr (FMA) return __builtin_fmaf(u.lr, g1 * u.scale, x);
+        else return x + u.lr * (g1 * u.scale);
+    };
+    if (u.momentum) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            vv[r] = axpy(g[r], vv[r]);
+            ww[r] += vv[r];
+            vv[r] *= u.alpha;
+        }
+        *(f32x4 *)(V32 + idx) = vv;
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; r++) ww[r] = axpy(g[r], ww[r]);
+    }
+    *(f32x4 *)(W32 + idx) = ww;
+    bf16x4 wb;
+#pragma unroll
+    for (int r = 0; r < 4; r++) wb[r] = (__bf16)ww[r];
+    *(bf16x4 *)(Wb + idx) = wb;
+#pragma unroll
+    for (int r = 0; r < 4; r++) Wt[(size_t)(mt + r) * ldt + nt] = wb[r];
+}
+
+/* the 4 x 2 fragments of quadrant (mi, ni) of a TN wave tile: f(i, j, n, m), the fragment's
+ * 4 consecutive m of one n, relative to the wave tile's corner */
+template <class F>
+__device__ __forceinline__ void quad_frags(int mi, int ni, int lane, F f) {
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int j = 0; j < 2; j++) f(i, j, ni * 32 + j * 16 + (lane & 15), mi * 64 + i * 16 + 4 * (lane >> 4));
+}
+/* every fragment of the wave tile (MQ M-quadrants): f(n, m, acc) */
+template <int MQ, class F>
+__device__ __forceinline__ void for_each_frag(const f32x4 (&acc)[2][2][4][2], int lane, F f) {
+#pragma unroll
+    for (int mi = 0; mi < MQ; mi++)
+#pragma unroll
+        for (int ni = 0; ni < 2; ni++)
+            quad_frags(mi, ni, lane, [&](int i, int j, int n, int m)
+                                         __attribute__((always_inline)) { f(n, m, acc[mi][ni][i][j]); });
+}
 
 /* MODE 2 side job (hpnn_gemm_tn8_fused_update_side): the NEXT layer's weight gradient
  * G1 = D^T H of a two-layer net (RRUFF: 230 x 230 over the batch) and its step, carried
@@ -427,27 +495,7 @@ __device__ __forceinline__ void side_reduce_step(const Tn8Side &s, const Tn8Upd 
             }
         }
         g += (g1 + g2) + g3;
-        /* the contraction spelled out: sgd_tile's compiled step is fma(lr, g * scale, v) (a
-         * free choice of the compiler here measured 1-ulp apart on a few elements) */
-        if (u.momentum) {
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                vv[r] = __builtin_fmaf(u.lr, g[r] * u.scale, vv[r]);
-                ww[r] += vv[r];
-                vv[r] *= u.alpha;
-            }
-            *(f32x4 *)(s.V32 + idx) = vv;
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; r++) ww[r] = __builtin_fmaf(u.lr, g[r] * u.scale, ww[r]);
-        }
-        *(f32x4 *)(s.W32 + idx) = ww;
-        bf16x4 wb;
-#pragma unroll
-        for (int r = 0; r < 4; r++) wb[r] = (__bf16)ww[r];
-        *(bf16x4 *)(s.Wb + idx) = wb;
-#pragma unroll
-        for (int r = 0; r < 4; r++) s.Wt[(size_t)(m + r) * s.N + n] = wb[r];
+        sgd_step4<true>(u, s.W32, s.V32, s.Wb, idx, g, ww, vv, s.Wt, s.N, m, n);
     }
 }
 
@@ -480,20 +528,11 @@ __global__ __launch_bounds__(512) void gemm_tn8_kernel(const __bf16 *__restrict_
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
-    int tile, split;
-    if (splits == 1) {
-        const int bid = blockIdx.x, xcd = bid & 7, q8 = ntiles >> 3, r8 = ntiles & 7;
-        tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-        split = 0;
-    } else {
-        /* XCD-aware, bijective (as gemm_nt8_kernel): each XCD takes a contiguous run of
-         * split-major work items, i.e. whole K slices for every tile, so a slice of D (shared
-         * by all tiles) is fetched into one XCD's L2 once instead of into every XCD's */
-        const int total = ntiles * splits, bid = blockIdx.x, xcd = bid & 7, q8 = total >> 3, r8 = total & 7;
-        const int w = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-        tile = w % ntiles;
-        split = w / ntiles;
-    }
+    /* each XCD takes a contiguous run of split-major work items, i.e. whole K slices for every
+     * tile, so a slice of D (shared by all tiles) is fetched into one XCD's L2 once instead of
+     * into every XCD's; one split: a run of tiles */
+    const int w = xcd_remap(blockIdx.x, ntiles * splits);
+    const int tile = splits == 1 ? w : w % ntiles, split = splits == 1 ? 0 : w / ntiles;
     static_assert(TM == 256 || (TM == 128 && MODE == 2), "tile width");
     const int tn = tile % tiles_n, tm = tile / tiles_n;
     const int m0 = tm * TM, n0 = tn * 256;
@@ -575,28 +614,24 @@ __global__ __launch_bounds__(512) void gemm_tn8_kernel(const __bf16 *__restrict_
         hpnn::s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         return __builtin_bit_cast(bf16x8, v);
     };
-    bf16x8 rh[4][2], rd0[2][2], rd1[2][2];
-    auto read_h = [&](const char *buf, int mi) __attribute__((always_inline)) {
-        /* TM 128: one H half-tile, M-half wm owns its columns 64 wm.. (mi unused) */
-        const char *img = buf + (TM == 256 ? wm * HALF : 0);
+    bf16x8 rh[4][2], rd[2][2][2]; /* rd[ni][j][kk] */
+    auto read_h = [&](int kt, int mi) __attribute__((always_inline)) {
+        /* TM 128: one H half-tile, M-half wm owns its columns 64 wm.. (mi is 0) */
+        const char *img = lds + (kt & 1) * KBUF + (TM == 256 ? wm * HALF : 0);
         const int c0 = TM == 256 ? mi * 64 : wm * 64;
 #pragma unroll
         for (int i = 0; i < 4; i++)
 #pragma unroll
             for (int kk = 0; kk < 2; kk++) rh[i][kk] = ftr(img, kk * 32, c0 + i * 16);
     };
-    auto read_d = [&](const char *buf, int ni, bf16x8 (&rd)[2][2]) __attribute__((always_inline)) {
-        const char *img = buf + (2 + (wn >> 1)) * HALF;
+    auto read_d = [&](int kt, int ni) __attribute__((always_inline)) {
+        const char *img = lds + (kt & 1) * KBUF + (2 + (wn >> 1)) * HALF;
 #pragma unroll
         for (int j = 0; j < 2; j++)
 #pragma unroll
-            for (int kk = 0; kk < 2; kk++) rd[j][kk] = ftr(img, kk * 32, (wn & 1) * 64 + ni * 32 + j * 16);
+            for (int kk = 0; kk < 2; kk++) rd[ni][j][kk] = ftr(img, kk * 32, (wn & 1) * 64 + ni * 32 + j * 16);
     };
-    auto mma = [&](int mi, int ni, const bf16x8 (&rd)[2][2]) __attribute__((always_inline)) {
-        __builtin_amdgcn_s_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
+    auto mma = [&](int mi, int ni) __attribute__((always_inline)) {
 #pragma unroll
         for (int kk = 0; kk < 2; kk++)
 #pragma unroll
@@ -604,131 +639,30 @@ __global__ __launch_bounds__(512) void gemm_tn8_kernel(const __bf16 *__restrict_
 #pragma unroll
                 for (int j = 0; j < 2; j++)
                     acc[mi][ni][i][j] =
-                        __builtin_amdgcn_mfma_f32_16x16x32_bf16(rh[i][kk], rd[j][kk], acc[mi][ni][i][j], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
+                        __builtin_amdgcn_mfma_f32_16x16x32_bf16(rh[i][kk], rd[ni][j][kk], acc[mi][ni][i][j], 0, 0, 0);
     };
-
-    /* the schedule of gemm_nt8_kernel with H in the role of A and D in that of B */
-    stage(0, 0);
-    if constexpr (TM == 256) stage(1, 0);
-    stage(2, 0);
-    stage(3, 0);
-    stage(2, 1);
-    stage(3, 1);
-    vm_wait<4>();
-    __builtin_amdgcn_s_barrier();
-    if (wm == 1) __builtin_amdgcn_s_barrier();
-
-    if constexpr (TM == 128) {
-        /* 4 phases per 2 K-tiles, quadrants (0,0) (0,1) of the one M-quadrant; H(o) is restaged
-         * at the top (its O slot was last read two phases before the previous iteration's
-         * end), D(e+2) after the even phases, H(e+2) once the odd H is read, D(o+2) last; the
-         * counted waits leave only the D pieces just issued in flight */
-        for (int e = 0; e < KT; e += 2) {
-            const int o = e + 1;
-            const bool ne = e + 2 < KT, no = o + 2 < KT;
-            const char *bE = lds + (e & 1) * KBUF, *bO = lds + (o & 1) * KBUF;
-            read_h(bE, 0);
-            read_d(bE, 0, rd0);
-            stage(0, o);
-            __builtin_amdgcn_sched_barrier(0);
-            mma(0, 0, rd0);
-            read_d(bE, 1, rd1);
-            __builtin_amdgcn_sched_barrier(0);
-            mma(0, 1, rd1);
-            if (ne) {
-                stage(2, e + 2);
-                stage(3, e + 2);
-                vm_wait<4>();
-            } else {
-                vm_wait<0>();
-            }
-            read_h(bO, 0);
-            read_d(bO, 0, rd0);
-            if (ne) stage(0, e + 2);
-            __builtin_amdgcn_sched_barrier(0);
-            mma(0, 0, rd0);
-            read_d(bO, 1, rd1);
-            __builtin_amdgcn_sched_barrier(0);
-            mma(0, 1, rd1);
-            if (no) {
-                stage(2, o + 2);
-                stage(3, o + 2);
-                vm_wait<4>();
-            } else {
-                vm_wait<0>();
-            }
-        }
-    } else
-    for (int e = 0; e < KT; e += 2) {
-        const int o = e + 1;
-        const bool ne = e + 2 < KT, no = o + 2 < KT;
-        const char *bE = lds + (e & 1) * KBUF, *bO = lds + (o & 1) * KBUF;
-        read_h(bE, 0);
-        read_d(bE, 0, rd0);
-        stage(0, o);
-        stage(1, o);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(0, 0, rd0);
-        read_d(bE, 1, rd1);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(0, 1, rd1);
-        read_h(bE, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(1, 1, rd1);
-        if (ne) {
-            stage(2, e + 2);
-            stage(3, e + 2);
-            vm_wait<4>();
-        } else {
-            vm_wait<0>();
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        mma(1, 0, rd0);
-        read_h(bO, 0);
-        read_d(bO, 0, rd0);
-        if (ne) {
-            stage(0, e + 2);
-            stage(1, e + 2);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        mma(0, 0, rd0);
-        read_d(bO, 1, rd1);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(0, 1, rd1);
-        read_h(bO, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(1, 1, rd1);
-        if (no) {
-            stage(2, o + 2);
-            stage(3, o + 2);
-            vm_wait<4>();
-        } else {
-            vm_wait<0>();
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        mma(1, 0, rd0);
-    }
-    if (wm == 0) __builtin_amdgcn_s_barrier();
+    /* H in the role of A, D in that of B */
+    pipe8<TM / 128>(
+        KT, wm, read_h, read_d,
+        [&](int kt) __attribute__((always_inline)) {
+            stage(0, kt);
+            if constexpr (TM == 256) stage(1, kt);
+        },
+        [&](int kt) __attribute__((always_inline)) {
+            stage(2, kt);
+            stage(3, kt);
+        },
+        mma);
     mark(2);
 
     float *out = slab + (size_t)split * N * ldg;
-    const int r16 = lane & 15, q = lane >> 4;
+    /* the wave tile's corner; a fragment's offset in an [N][ldg] matrix */
+    const int nw = n0 + wn * 64, mw = m0 + wm * (TM / 2);
+    auto frag_off = [&](int n, int m) __attribute__((always_inline)) { return (size_t)(nw + n) * ldg + mw + m; };
     if constexpr (MODE == 2) {
-#pragma unroll
-        for (int mi = 0; mi < TM / 128; mi++)
-#pragma unroll
-            for (int ni = 0; ni < 2; ni++)
-#pragma unroll
-                for (int i = 0; i < 4; i++)
-#pragma unroll
-                    for (int j = 0; j < 2; j++) {
-                        const int n = n0 + wn * 64 + ni * 32 + j * 16 + r16;
-                        const int m = m0 + wm * (TM / 2) + mi * 64 + i * 16 + 4 * q;
-                        hpnn::st_sc1(out + (size_t)n * ldg + m, acc[mi][ni][i][j]);
-                    }
+        for_each_frag<TM / 128>(acc, lane, [&](int n, int m, const f32x4 &g) __attribute__((always_inline)) {
+            hpnn::st_sc1(out + frag_off(n, m), g);
+        });
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         /* 64-bit tickets (mfma_common.h): no wrap */
@@ -773,83 +707,29 @@ __global__ __launch_bounds__(512) void gemm_tn8_kernel(const __bf16 *__restrict_
                         g += t;
                     }
             }
-            if (upd.momentum) {
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    vv[r] += upd.lr * (g[r] * upd.scale);
-                    ww[r] += vv[r];
-                    vv[r] *= upd.alpha;
-                }
-                *(f32x4 *)(upd.V32 + idx) = vv;
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; r++) ww[r] += upd.lr * (g[r] * upd.scale);
-            }
-            *(f32x4 *)(upd.W32 + idx) = ww;
-            bf16x4 wb;
-#pragma unroll
-            for (int r = 0; r < 4; r++) wb[r] = (__bf16)ww[r];
-            *(bf16x4 *)(upd.Wb + idx) = wb;
-#pragma unroll
-            for (int r = 0; r < 4; r++) upd.Wt[(size_t)(m + r) * N + n] = wb[r];
+            sgd_step4<false>(upd, upd.W32, upd.V32, upd.Wb, idx, g, ww, vv, upd.Wt, N, m, n);
         }
         mark(7);
     } else if constexpr (MODE == 1) {
         /* W [N][ldg]: W32 / V32 / Wb row-major, Wt [ldg][N].  Per quadrant: all loads
          * first (8 fragments in flight), then the step, then the stores -- a load / use /
          * store chain per fragment would leave the epilogue latency-bound */
-        float *__restrict__ W32 = upd.W32;
-        float *__restrict__ V32 = upd.V32;
-        __bf16 *__restrict__ Wb = upd.Wb;
-        __bf16 *__restrict__ Wt = upd.Wt;
         __bf16 *tw = (__bf16 *)(lds + wave * 16384);
 #pragma unroll
         for (int mi = 0; mi < 2; mi++)
 #pragma unroll
             for (int ni = 0; ni < 2; ni++) {
                 f32x4 w[4][2], v[4][2];
-#pragma unroll
-                for (int i = 0; i < 4; i++)
-#pragma unroll
-                    for (int j = 0; j < 2; j++) {
-                        const size_t idx = (size_t)(n0 + wn * 64 + ni * 32 + j * 16 + r16) * ldg +
-                                           (m0 + wm * 128 + mi * 64 + i * 16 + 4 * q);
-                        w[i][j] = *(const f32x4 *)(W32 + idx);
-                        if (upd.momentum) v[i][j] = *(const f32x4 *)(V32 + idx);
-                    }
-#pragma unroll
-                for (int i = 0; i < 4; i++)
-#pragma unroll
-                    for (int j = 0; j < 2; j++) {
-                        const int n = n0 + wn * 64 + ni * 32 + j * 16 + r16;
-                        const int m = m0 + wm * 128 + mi * 64 + i * 16 + 4 * q;
-                        const size_t idx = (size_t)n * ldg + m;
-                        const f32x4 g = acc[mi][ni][i][j];
-                        f32x4 ww = w[i][j];
-                        if (upd.momentum) {
-                            f32x4 vv = v[i][j];
-#pragma unroll
-                            for (int r = 0; r < 4; r++) {
-                                vv[r] += upd.lr * (g[r] * upd.scale);
-                                ww[r] += vv[r];
-                                vv[r] *= upd.alpha;
-                            }
-                            *(f32x4 *)(V32 + idx) = vv;
-                        } else {
-#pragma unroll
-                            for (int r = 0; r < 4; r++) ww[r] += upd.lr * (g[r] * upd.scale);
-                        }
-                        *(f32x4 *)(W32 + idx) = ww;
-                        bf16x4 wb;
-#pragma unroll
-                        for (int r = 0; r < 4; r++) wb[r] = (__bf16)ww[r];
-                        *(bf16x4 *)(Wb + idx) = wb;
-                        /* W^T through this wave's 16 KiB of the (now idle) LDS: [m][n] image of
-                         * its 128 x 64 tile, written out below in 16-byte row pieces */
-                        const int ml = mi * 64 + i * 16 + 4 * q, nl = ni * 32 + j * 16 + r16;
-#pragma unroll
-                        for (int r = 0; r < 4; r++) tw[(ml + r) * 64 + nl] = wb[r];
-                    }
+                quad_frags(mi, ni, lane, [&](int i, int j, int n, int m) __attribute__((always_inline)) {
+                    w[i][j] = *(const f32x4 *)(upd.W32 + frag_off(n, m));
+                    if (upd.momentum) v[i][j] = *(const f32x4 *)(upd.V32 + frag_off(n, m));
+                });
+                /* W^T through this wave's 16 KiB of the (now idle) LDS: [m][n] image of its
+                 * 128 x 64 tile, written out below in 16-byte row pieces */
+                quad_frags(mi, ni, lane, [&](int i, int j, int n, int m) __attribute__((always_inline)) {
+                    sgd_step4<false>(upd, upd.W32, upd.V32, upd.Wb, frag_off(n, m), acc[mi][ni][i][j], w[i][j], v[i][j],
+                                     tw, 64, m, n);
+                });
             }
         /* every wave is past its last operand read of the main loop (the final barriers),
          * and the region is this wave's own: LDS ops of one wave complete in order; the
@@ -861,37 +741,19 @@ __global__ __launch_bounds__(512) void gemm_tn8_kernel(const __bf16 *__restrict_
 #pragma unroll
         for (int t = 0; t < 16; t++) {
             const int e = t * 64 + lane, ml = e >> 3, nc = (e & 7) * 8;
-            *(bf16x8 *)(Wt + (size_t)(m0 + wm * 128 + ml) * N + n0 + wn * 64 + nc) = *(const bf16x8 *)(tw + ml * 64 + nc);
+            *(bf16x8 *)(upd.Wt + (size_t)(mw + ml) * N + nw + nc) = *(const bf16x8 *)(tw + ml * 64 + nc);
         }
     } else if constexpr (MODE == 3) {
+        for_each_frag<2>(acc, lane, [&](int n, int m, const f32x4 &g) __attribute__((always_inline)) {
+            bf16x4 gb;
 #pragma unroll
-        for (int mi = 0; mi < 2; mi++)
-#pragma unroll
-            for (int ni = 0; ni < 2; ni++)
-#pragma unroll
-                for (int i = 0; i < 4; i++)
-#pragma unroll
-                    for (int j = 0; j < 2; j++) {
-                        const int n = n0 + wn * 64 + ni * 32 + j * 16 + r16;
-                        const int m = m0 + wm * 128 + mi * 64 + i * 16 + 4 * q;
-                        bf16x4 gb;
-#pragma unroll
-                        for (int r = 0; r < 4; r++) gb[r] = (__bf16)acc[mi][ni][i][j][r];
-                        *(bf16x4 *)(upd.Wb + (size_t)n * ldg + m) = gb;
-                    }
+            for (int r = 0; r < 4; r++) gb[r] = (__bf16)g[r];
+            *(bf16x4 *)(upd.Wb + frag_off(n, m)) = gb;
+        });
     } else {
-#pragma unroll
-        for (int mi = 0; mi < 2; mi++)
-#pragma unroll
-            for (int ni = 0; ni < 2; ni++)
-#pragma unroll
-                for (int i = 0; i < 4; i++)
-#pragma unroll
-                    for (int j = 0; j < 2; j++) {
-                        const int n = n0 + wn * 64 + ni * 32 + j * 16 + r16;
-                        const int m = m0 + wm * 128 + mi * 64 + i * 16 + 4 * q;
-                        *(f32x4 *)(out + (size_t)n * ldg + m) = acc[mi][ni][i][j];
-                    }
+        for_each_frag<2>(acc, lane, [&](int n, int m, const f32x4 &g) __attribute__((always_inline)) {
+            *(f32x4 *)(out + frag_off(n, m)) = g;
+        });
     }
 }
 
@@ -915,25 +777,7 @@ __global__ __launch_bounds__(256) void nt_splitk_epi_kernel(const float *__restr
         const int b = (int)(e * 4 / N), f = (int)(e * 4 % N);
         f32x4 v = ((const f32x4 *)P)[e];
         for (int s = 1; s < S; s++) v += ((const f32x4 *)(P + (size_t)s * cstride))[e];
-        if constexpr (EPI == HPNN_EPI_ACT) {
-#pragma unroll
-            for (int r = 0; r < 4; r++) v[r] = hpnn::bipolar(v[r]);
-        } else if constexpr (EPI == HPNN_EPI_DACT) {
-            const bf16x4 h = *(const bf16x4 *)(aux + (size_t)b * ldaux + f);
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const float y = (float)h[r];
-                v[r] *= -0.5f * (y * y - 1.0f);
-            }
-        }
-        if constexpr (CF32) {
-            *(f32x4 *)((float *)C + (size_t)b * ldc + f) = v;
-        } else {
-            bf16x4 o;
-#pragma unroll
-            for (int r = 0; r < 4; r++) o[r] = (__bf16)v[r];
-            *(bf16x4 *)((__bf16 *)C + (size_t)b * ldc + f) = o;
-        }
+        epi_store4<EPI, CF32>(C, ldc, aux, ldaux, b, f, v);
     }
 }
 
@@ -945,6 +789,35 @@ int splitk_epi(const float *P, int S, long cstride, int M, int N, const void *au
     hipLaunchKernelGGL((nt_splitk_epi_kernel<EPI, CF32>), dim3(blocks), dim3(256), 0, s, P, S, cstride, M, N,
                        (const __bf16 *)aux, ldaux, C, ldc);
     return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+/* f(integral_constant<int, EPI>, bool_constant<CF32>) for the run-time epi / c_f32 */
+template <class F>
+int by_epi(int epi, int c_f32, F f) {
+    auto e = [&](auto cf) {
+        if (epi == HPNN_EPI_NONE) return f(std::integral_constant<int, HPNN_EPI_NONE>{}, cf);
+        if (epi == HPNN_EPI_ACT) return f(std::integral_constant<int, HPNN_EPI_ACT>{}, cf);
+        return f(std::integral_constant<int, HPNN_EPI_DACT>{}, cf);
+    };
+    return c_f32 ? e(std::true_type{}) : e(std::false_type{});
+}
+
+/* what every TN launch asks of its shape: 256 x 256 tiles, 64-row units, an even number of
+ * them per split, 32-bit staging offsets */
+bool tn8_shape_ok(int N, int M, int Bt, int ldd, int ldh, int splits = 1) {
+    if (N % 256 || M % 256 || Bt % 128 || ldd % 8 || ldh % 8 || splits < 1) return false;
+    if ((Bt / 64) % splits || (Bt / 64 / splits) % 2) return false;
+    return (size_t)ldd * 2 * 64 < (1u << 31) && (size_t)ldh * 2 * 64 < (1u << 31);
+}
+
+/* environment settings; the callers keep them in function-local statics (read once per process) */
+int env_int(const char *name, int dflt) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+bool env_flag(const char *name, bool dflt) { /* "0..." switches a default-on flag off, "1..." a default-off one on */
+    const char *e = getenv(name);
+    return e ? (dflt ? e[0] != '0' : e[0] == '1') : dflt;
 }
 
 /* split-K workspace, one per device (train_nn -G drives several GPUs from one process, one
@@ -980,23 +853,16 @@ extern "C" int hpnn_gemm_nt8_bf16(const void *A, int lda, const void *B, int ldb
     if (lda % 8 || ldb % 8 || ldc % 4 || ((uintptr_t)A & 15) || ((uintptr_t)B & 15)) return -1;
     if ((size_t)lda * 2 * 256 >= (1u << 31) || (size_t)ldb * 2 * 256 >= (1u << 31)) return -1; /* 32-bit offsets */
     if (epi == HPNN_EPI_DACT && (!aux || ldaux % 4)) return -1;
-    if (c_f32) {
-        if (epi == HPNN_EPI_NONE) return launch8<HPNN_EPI_NONE, true>(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, stream);
-        if (epi == HPNN_EPI_ACT) return launch8<HPNN_EPI_ACT, true>(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, stream);
-        return launch8<HPNN_EPI_DACT, true>(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, stream);
-    }
-    if (epi == HPNN_EPI_NONE) return launch8<HPNN_EPI_NONE, false>(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, stream);
-    if (epi == HPNN_EPI_ACT) return launch8<HPNN_EPI_ACT, false>(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, stream);
-    return launch8<HPNN_EPI_DACT, false>(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, stream);
+    return by_epi(epi, c_f32, [&](auto E, auto F) {
+        return launch8<decltype(E)::value, decltype(F)::value>(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, stream);
+    });
 }
 
 /* TN entry for gemm_tn_dispatch (kernels_mfma.hip): -1 when the shape does not fit */
 int hpnn_gemm_tn8_launch(const void *D, int ldd, const void *H, int ldh, float *slab, int ldg, int N, int M, int Bt,
                          int splits, hipStream_t stream, const hpnn::TnTail &tail) {
-    if (N % 256 || M % 256 || Bt % 128 || splits < 1 || ldd % 8 || ldh % 8 || ldg % 4) return -1;
+    if (!tn8_shape_ok(N, M, Bt, ldd, ldh, splits) || ldg % 4) return -1;
     const int units = Bt / 64;
-    if (units % splits || (units / splits) % 2) return -1;
-    if ((size_t)ldd * 2 * 64 >= (1u << 31) || (size_t)ldh * 2 * 64 >= (1u << 31)) return -1;
     const int tiles_n = N / 256, ntiles = tiles_n * (M / 256);
     hipLaunchKernelGGL(gemm_tn8_kernel<0>, dim3(ntiles * splits + tail.blocks), dim3(512), 0, stream,
                        (const __bf16 *)D, ldd, (const __bf16 *)H, ldh, slab, ldg, N, units, splits, tiles_n, ntiles,
@@ -1006,23 +872,19 @@ int hpnn_gemm_tn8_launch(const void *D, int ldd, const void *H, int ldh, float *
 
 /* the shape check of hpnn_gemm_tn8_bf16out (without the pointer alignment): 1 when it fits */
 extern "C" int hpnn_gemm_tn8_bf16out_ok(int N, int M, int Bt, int ldd, int ldh) {
-    if (N % 256 || M % 256 || Bt % 128 || ldd % 8 || ldh % 8 || (Bt / 64) % 2) return 0;
-    return (size_t)ldd * 2 * 64 < (1u << 31) && (size_t)ldh * 2 * 64 < (1u << 31);
+    return tn8_shape_ok(N, M, Bt, ldd, ldh);
 }
 
 /* G = D^T H over the whole batch (one split), rounded to BF16 into G16 [N][ldg]: -1 when the
  * shape does not fit the 8-phase kernel */
 extern "C" int hpnn_gemm_tn8_bf16out(const void *D, int ldd, const void *H, int ldh, void *G16, int ldg, int N, int M,
                                      int Bt, hipStream_t stream) {
-    if (N % 256 || M % 256 || Bt % 128 || ldd % 8 || ldh % 8 || ldg % 4 || ((uintptr_t)G16 & 7)) return -1;
-    const int units = Bt / 64;
-    if (units % 2) return -1;
-    if ((size_t)ldd * 2 * 64 >= (1u << 31) || (size_t)ldh * 2 * 64 >= (1u << 31)) return -1;
+    if (!tn8_shape_ok(N, M, Bt, ldd, ldh) || ldg % 4 || ((uintptr_t)G16 & 7)) return -1;
     const int tiles_n = N / 256, ntiles = tiles_n * (M / 256);
     Tn8Upd u{};
     u.Wb = (__bf16 *)G16;
     hipLaunchKernelGGL(gemm_tn8_kernel<3>, dim3(ntiles), dim3(512), 0, stream, (const __bf16 *)D, ldd,
-                       (const __bf16 *)H, ldh, nullptr, ldg, N, units, 1, tiles_n, ntiles, hpnn::TnTail{}, u, Tn8Side{});
+                       (const __bf16 *)H, ldh, nullptr, ldg, N, Bt / 64, 1, tiles_n, ntiles, hpnn::TnTail{}, u, Tn8Side{});
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
@@ -1034,10 +896,9 @@ extern "C" int hpnn_gemm_tn8_bf16out(const void *D, int ldd, const void *H, int 
 extern "C" int hpnn_gemm_tn8_update(const void *D, int ldd, const void *H, int ldh, int N, int M, int Bt, float *W32,
                                     float *V32, void *Wbf, void *Wt, float lr, float alpha, float scale, int momentum,
                                     hipStream_t stream) {
-    if (N % 256 || M % 256 || Bt % 128 || ldd % 8 || ldh % 8 || !W32 || !Wbf || !Wt || (momentum && !V32)) return -1;
+    if (!tn8_shape_ok(N, M, Bt, ldd, ldh) || !W32 || !Wbf || !Wt || (momentum && !V32)) return -1;
     /* the epilogue moves W32 / V32 as float4 and W / W^T as 8- and 16-byte pieces */
     if (((uintptr_t)W32 | (uintptr_t)(momentum ? V32 : W32) | (uintptr_t)Wbf | (uintptr_t)Wt) & 15) return -1;
-    if ((size_t)ldd * 2 * 64 >= (1u << 31) || (size_t)ldh * 2 * 64 >= (1u << 31)) return -1;
     const int tiles_n = N / 256, ntiles = tiles_n * (M / 256);
     const Tn8Upd u{W32, V32, (__bf16 *)Wbf, (__bf16 *)Wt, lr, alpha, scale, momentum, nullptr, nullptr};
     hipLaunchKernelGGL(gemm_tn8_kernel<1>, dim3(ntiles), dim3(512), 0, stream, (const __bf16 *)D, ldd,
@@ -1053,7 +914,7 @@ extern "C" int hpnn_gemm_tn8_fused_update_side(const void *D, int ldd, const voi
                                                int splits, float *slab, float *W32, float *V32, void *Wbf, void *Wt,
                                                float lr, float alpha, float scale, int momentum, unsigned int *cnt,
                                                unsigned int *err, const hpnn_tn8_side *sd, hipStream_t stream) {
-    static const bool on = [] { const char *e = getenv("HPNN_TN8_FUSED"); return !(e && e[0] == '0'); }();
+    static const bool on = env_flag("HPNN_TN8_FUSED", true);
     /* every split of a tile waits for the others: the whole grid must be resident at once */
     static const int cap = hpnn_resident_capacity((const void *)gemm_tn8_kernel<2>, 512, 0);
     static int cus = 0;
@@ -1063,22 +924,18 @@ extern "C" int hpnn_gemm_tn8_fused_update_side(const void *D, int ldd, const voi
             cus = -1;
     }
     if (!on || splits < 2 || !slab || !cnt || !err) return -1;
-    if (N % 256 || M % 256 || Bt % 128 || ldd % 8 || ldh % 8 || !W32 || !Wbf || !Wt || (momentum && !V32)) return -1;
+    if (!tn8_shape_ok(N, M, Bt, ldd, ldh, splits) || !W32 || !Wbf || !Wt || (momentum && !V32)) return -1;
     if (((uintptr_t)W32 | (uintptr_t)(momentum ? V32 : W32) | (uintptr_t)Wbf | (uintptr_t)slab) & 15) return -1;
-    if ((size_t)ldd * 2 * 64 >= (1u << 31) || (size_t)ldh * 2 * 64 >= (1u << 31)) return -1;
     const int units = Bt / 64;
-    if (units % splits || (units / splits) % 2) return -1;
     /* 256 x 128 tiles at half the splits (HPNN_TN8_TM=128; same grid, half the partial bytes) */
-    static const int tm_req = [] { const char *e = getenv("HPNN_TN8_TM"); return e ? atoi(e) : 256; }();
+    static const int tm_req = env_int("HPNN_TN8_TM", 256);
     const bool t128 = tm_req == 128 && splits % 2 == 0 && (units / (splits / 2)) % 2 == 0;
     if (t128) splits /= 2;
-    const int TMv = t128 ? 128 : 256;
-    if (M % TMv) return -1;
-    const int tiles_n = N / 256, ntiles = tiles_n * (M / TMv);
+    const int tiles_n = N / 256, ntiles = tiles_n * (M / (t128 ? 128 : 256));
     /* 64-bit tickets: 32 words apart in 1024, up to 32 tiles (a block the caller keeps for this GEMM shape: the
      * counters are monotonic, every launch must add `splits` per tile); at least min_wg workgroups (HPNN_TN8_MINWG, default
      * half the CUs: fewer splits leave the chip idle while each reduces a larger share) */
-    static const int min_wg = [] { const char *e = getenv("HPNN_TN8_MINWG"); return e ? atoi(e) : 0; }();
+    static const int min_wg = env_int("HPNN_TN8_MINWG", 0);
     if (ntiles > 32 || ntiles * splits > cap || ntiles * splits < (min_wg > 0 ? min_wg : cus / 2)) return -1;
     const Tn8Upd u{W32, V32, (__bf16 *)Wbf, (__bf16 *)Wt, lr, alpha, scale, momentum, cnt, err};
     Tn8Side side{};
@@ -1096,7 +953,7 @@ extern "C" int hpnn_gemm_tn8_fused_update_side(const void *D, int ldd, const voi
         side = Tn8Side{(const __bf16 *)sd->D, (const __bf16 *)sd->H, sd->slab, sd->W32, sd->V32, (__bf16 *)sd->Wb,
                        (__bf16 *)sd->Wt, sd->cnt, sd->ldd, sd->ldh, sd->N, sd->M, su, sd->S, sd->N / 64, tiles, jobs, 1};
     }
-    static const bool trace = [] { const char *e = getenv("HPNN_TN8_TRACE"); return e && e[0] == '1'; }();
+    static const bool trace = env_flag("HPNN_TN8_TRACE", false);
     auto kern = t128 ? (trace ? gemm_tn8_kernel<2, true, 128> : gemm_tn8_kernel<2, false, 128>)
                      : (trace ? gemm_tn8_kernel<2, true> : gemm_tn8_kernel<2, false>);
     hipLaunchKernelGGL(kern, dim3(ntiles * splits), dim3(512), 0, stream, (const __bf16 *)D, ldd, (const __bf16 *)H, ldh, slab, M, N, units, splits, tiles_n,
@@ -1133,16 +990,9 @@ extern "C" int hpnn_gemm_nt8_splitk_bf16(const void *A, int lda, const void *B, 
     if (!P) return -1;
     int rc = launch8<HPNN_EPI_NONE, true>(A, lda, B, ldb, P, N, nullptr, 0, M, N, K, stream, splits, cstride);
     if (rc) return rc;
-#define HPNN_SKE(E_, F_) return splitk_epi<E_, F_>(P, splits, cstride, M, N, aux, ldaux, C, ldc, stream)
-    if (c_f32) {
-        if (epi == HPNN_EPI_NONE) HPNN_SKE(HPNN_EPI_NONE, true);
-        if (epi == HPNN_EPI_ACT) HPNN_SKE(HPNN_EPI_ACT, true);
-        HPNN_SKE(HPNN_EPI_DACT, true);
-    }
-    if (epi == HPNN_EPI_NONE) HPNN_SKE(HPNN_EPI_NONE, false);
-    if (epi == HPNN_EPI_ACT) HPNN_SKE(HPNN_EPI_ACT, false);
-    HPNN_SKE(HPNN_EPI_DACT, false);
-#undef HPNN_SKE
+    return by_epi(epi, c_f32, [&](auto E, auto F) {
+        return splitk_epi<decltype(E)::value, decltype(F)::value>(P, splits, cstride, M, N, aux, ldaux, C, ldc, stream);
+    });
 }
 
 

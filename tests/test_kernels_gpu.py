@@ -176,6 +176,52 @@ def test_gemm_nt8_splitk(gpu, M, N, K, S, epi):
         assert err <= tol * max(1.0, scale), (f32, err, scale)
 
 
+@pytest.mark.parametrize("M,N,K,S", [(256, 256, 128, 1), (256, 256, 256, 1), (512, 256, 384, 1), (256, 256, 256, 2)])
+@pytest.mark.parametrize("epi", [ops.EPI_NONE, ops.EPI_ACT, ops.EPI_DACT])
+def test_gemm_nt8_integer_exact(gpu, M, N, K, S, epi):
+    """a dropped, doubled or misplaced K-tile of the 8-phase schedule shows up exactly: operands are
+    integers in [-3, 3] (|sum| <= 9 K, exact in FP32 in any order), aux is from {0, +-0.5, +-1}, so
+    f'(aux) is 0.5, 0.375 or 0 and the product stays exact.  EPI_NONE / EPI_DACT: the FP32 output
+    equals the float64 reference bit for bit, the BF16 output that reference rounded once; EPI_ACT
+    (__expf / rcp) keeps the tolerance of test_gemm_nt8.  K = 128: one iteration, nothing restaged,
+    both tail waits; 256: one restage of each kind; 384: three K-tile pairs over two tiles; S = 2: the
+    split-K form.  The output is NaN-filled, its padding columns must stay NaN."""
+    from hpnn_amd._lib import native
+    gen = torch.Generator().manual_seed(M + 3 * N + K + S + epi)
+    A = torch.randint(-3, 4, (M, K + 64), generator=gen).to(gpu).bfloat16()[:, :K]
+    B = torch.randint(-3, 4, (N, K + 32), generator=gen).to(gpu).bfloat16()[:, :K]
+    aux = None
+    if epi == ops.EPI_DACT:
+        aux = (torch.randint(-2, 3, (M, N + 32), generator=gen).to(gpu) * 0.5).bfloat16()[:, :N]
+    R = A.double() @ B.double().t()
+    assert float(R.abs().max()) <= 9 * K
+    if epi == ops.EPI_ACT:
+        R = ops.bipolar(R)
+    elif epi == ops.EPI_DACT:
+        R = R * (-0.5 * (aux.double() ** 2 - 1.0))
+        assert torch.equal(R.float().double(), R)
+    stream = torch.cuda.current_stream().cuda_stream
+    for f32 in (False, True):
+        buf = torch.full((M, N + 64), float("nan"), dtype=torch.float32 if f32 else torch.bfloat16, device=gpu)
+        C = buf[:, :N]
+        args = (A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), C.data_ptr(), C.stride(0),
+                aux.data_ptr() if aux is not None else 0, aux.stride(0) if aux is not None else 0, M, N, K, epi,
+                int(f32))
+        if S == 1:
+            native().gemm_nt8_bf16(*args, stream)
+        else:
+            native().gemm_nt8_splitk_bf16(*args, S, stream)
+        assert bool(torch.isnan(buf[:, N:]).all()), (f32, "padding columns written")
+        if epi == ops.EPI_ACT:
+            tol = 2e-2 if not f32 else 2e-3
+            err = (C.double() - R).abs().max().item()
+            scale = R.abs().max().item() + 1e-6
+            assert err <= tol * max(1.0, scale), (f32, err, scale)
+        else:
+            want = R.float() if f32 else R.float().bfloat16()
+            assert torch.equal(C, want), (f32, int((C != want).sum()), (C.double() - R).abs().max().item())
+
+
 def test_gemm_nt8_rejects_bad_shapes(gpu):
     from hpnn_amd._lib import native
     A = torch.zeros(256, 192, dtype=torch.bfloat16, device="cuda")
