@@ -52,6 +52,10 @@ $(BUILD)/%.o: %.hip $(HDRS) $(HIPSTAMP)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# the CG decisions (include/libhpnn/cg.h) are the same numbers on the host and on the device:
+# no FP contraction in their device unit either (CXXFLAGS has it off already)
+$(BUILD)/csrc/gpu/kernels_cg.o: HIPFLAGS += -ffp-contract=off
+
 $(LIB): $(CORE_OBJ) $(HIP_OBJ)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^ $(LDFLAGS) -Wl,-soname,libhpnn.so

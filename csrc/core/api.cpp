@@ -78,6 +78,9 @@ extern "C" void _NN(deinit, conf)(nn_def *conf) {
     free(conf->validation);
     conf->validation = NULL;
     conf->n_validation = 0;
+    free(conf->cg_history);
+    conf->cg_history = NULL;
+    conf->n_cg_history = 0;
     conf->name = conf->f_kernel = conf->samples = conf->tests = NULL;
 }
 
@@ -133,6 +136,10 @@ extern "C" UINT _NN(get, validation)(nn_def *c, UINT max, UINT *epoch, DOUBLE *l
         if (n) n[i] = r[i].n;
     }
     return r ? c->n_validation : 0;
+}
+extern "C" const hpnn_cg_record *_NN(get, cg_history)(nn_def *c, UINT *n) {
+    if (n) *n = c && c->cg_history ? c->n_cg_history : 0;
+    return c ? (const hpnn_cg_record *)c->cg_history : NULL;
 }
 extern "C" void _NN(set, keep_best)(nn_def *c, nn_keep_best v) {
     c->keep_best = (v == NN_KEEP_LOSS || v == NN_KEEP_ACC) ? v : NN_KEEP_OFF;
@@ -549,9 +556,22 @@ static DOUBLE default_alpha(const nn_def *conf) { return conf->momentum >= 0 ? c
 extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
     if (!conf || !conf->kernel || !conf->samples || conf->type == NN_TYPE_UKN) return FALSE;
     kernel_ann *k = KERN(conf);
-    if (conf->train != NN_TRAIN_BP && conf->train != NN_TRAIN_BPM) {
+    if (conf->train != NN_TRAIN_BP && conf->train != NN_TRAIN_BPM && conf->train != NN_TRAIN_CG) {
         NN_ERROR(stdout, "unimplemented training type!\n");
         return FALSE;
+    }
+    if (conf->train == NN_TRAIN_CG) {
+        /* one CG iteration sums over the whole sample set: there is none in online mode */
+        if (conf->mode != NN_MODE_BATCHED) {
+            NN_ERROR(stderr, "[train] CG needs [mode] batched (one iteration per epoch over the whole sample set); "
+                             "online mode trains with BP or BPM\n");
+            return FALSE;
+        }
+        if (conf->dtype == NN_DTYPE_BF16) {
+            NN_ERROR(stderr, "[train] CG: the line search compares losses that the BF16 forward cannot resolve; "
+                             "use [dtype] f32 or f64\n");
+            return FALSE;
+        }
     }
     HpnnTraceRange tr("nn_train_kernel");
     HpnnSamples src;
@@ -580,6 +600,9 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
         conf->validation = NULL;
         conf->n_validation = 0;
         conf->best_epoch = 0;
+        free(conf->cg_history);
+        conf->cg_history = NULL;
+        conf->n_cg_history = 0;
         if (conf->keep_best && !conf->validate) {
             NN_ERROR(stderr, "[keep_best] needs [validate] N: there is no validation pass to keep the best of\n");
             return FALSE;
@@ -654,6 +677,20 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
         NN_OUT(stdout, "BATCHED TRAINING: %llu samples in %.6f s (%.1f samples/s) loss=%.10f acc=%u/%u\n",
                (unsigned long long)st.samples, st.seconds, st.seconds > 0 ? st.samples / st.seconds : 0.0,
                st.epoch_loss, st.correct, n);
+        for (UINT i = 0; ok && i < st.n_cg; i++) {
+            const hpnn_cg_record &r = st.cg[i];
+            NN_OUT(stdout, "CG: epoch %u loss=%.10f beta=%.10g alpha=%.10g trial=%d%s\n", o.epoch0 + i + 1, r.f0, r.beta,
+                   r.alpha, r.trial == HPNN_CG_NONE ? -1 : (int)r.trial, (r.flags & HPNN_CG_FAILED) ? " FAILED" : "");
+            if (hpnn_metrics_active()) {
+                char buf[384];
+                snprintf(buf, sizeof buf,
+                         "\"engine\": \"%s\", \"epoch\": %u, \"f0\": %.17g, \"f1\": %.17g, \"beta\": %.17g, "
+                         "\"alpha\": %.17g, \"trial\": %d, \"flags\": %u",
+                         gpu ? "gpu" : "cpu", o.epoch0 + i + 1, r.f0, r.f1, r.beta, r.alpha,
+                         r.trial == HPNN_CG_NONE ? -1 : (int)r.trial, r.flags);
+                hpnn_metrics_emit("cg", buf);
+            }
+        }
         for (UINT i = 0; ok && i < st.n_val; i++)
             NN_OUT(stdout, "VALIDATION: epoch %u loss=%.10f acc=%u/%u\n", st.val[i].epoch, st.val[i].loss,
                    st.val[i].correct, st.val[i].n);
@@ -686,8 +723,11 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
         if (ok) {
             conf->validation = st.val;
             conf->n_validation = st.n_val;
+            conf->cg_history = st.cg;
+            conf->n_cg_history = st.n_cg;
         } else {
             free(st.val);
+            free(st.cg);
         }
         if (hpnn_metrics_active()) {
             char buf[384];

@@ -24,6 +24,7 @@
 
 #include "../core/runtime_internal.h"
 #include "../gpu/engine.h"
+#include "cpu_cg.h"
 
 static inline DOUBLE act(DOUBLE x) { return 2.0 / (1.0 + exp(-1.0 * x)) - 1.0; }
 static inline DOUBLE dact(DOUBLE y) { return -0.5 * (y * y - 1.0); }
@@ -187,8 +188,14 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
     const UINT B = o->batch ? o->batch : 1;
     /* [shuffle] epoch: epoch e trains on a permuted copy, position i = sample src(i) of
      * <libhpnn/shuffle.h> for (n, seed, epochs completed); one batch per epoch: nothing to do */
-    const bool shuffle = o->shuffle && B < n;
-    if (o->shuffle && !shuffle) NN_OUT(stdout, "batched CPU training: one batch per epoch, no reshuffle\n");
+    /* [train] CG: one epoch = one conjugate-gradient iteration over the whole set (cpu_cg.cpp);
+     * the sample order only changes a summation order, so nothing is reshuffled */
+    const bool cg = o->train == NN_TRAIN_CG;
+    const bool shuffle = o->shuffle && B < n && !cg;
+    if (o->shuffle && cg) NN_OUT(stdout, "batched CPU training: CG sums over the whole set, no reshuffle\n");
+    else if (o->shuffle && !shuffle) NN_OUT(stdout, "batched CPU training: one batch per epoch, no reshuffle\n");
+    HpnnCpuCg cgs;
+    if (cg) cgs.init(k, o->lr, n, o->epochs);
     std::vector<DOUBLE> Xs, Ts;
     std::vector<unsigned int> perm;
     if (shuffle) {
@@ -223,7 +230,18 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
                 memcpy(&Ts[(size_t)i * k->n_outputs], T + (size_t)perm[i] * k->n_outputs, sizeof(DOUBLE) * k->n_outputs);
             }
         }
-        for (UINT s = 0; s < n; s += B) {
+        if (cg) {
+            cgs.iterate(k, o->type, X, T, n, B, [&](DOUBLE *sum, UINT *h) {
+                hpnn_validation_record r;
+                cpu_validate(k, o->type, X, T, n, &r, sum);
+                *h = r.correct;
+            });
+            last = acc = cgs.hist[e].f0;
+            hits = cgs.st.hits0;
+            nb = 1;
+            samples += n;
+        }
+        for (UINT s = 0; s < n && !cg; s += B) {
             UINT b = (n - s < B) ? n - s : B;
             last = hpnn_cpu_batched_step(k, o->type, Xe + (size_t)s * k->n_inputs, Te + (size_t)s * k->n_outputs, b,
                                          o->lr, mom, o->alpha, &hits);
@@ -291,6 +309,13 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
             st->val = (hpnn_validation_record *)malloc(val.size() * sizeof(val[0]));
             if (!st->val) return FALSE;
             memcpy(st->val, val.data(), val.size() * sizeof(val[0]));
+        }
+        st->cg = NULL;
+        st->n_cg = cg ? epochs_run : 0;
+        if (st->n_cg) {
+            st->cg = (hpnn_cg_record *)malloc(st->n_cg * sizeof(hpnn_cg_record));
+            if (!st->cg) return FALSE;
+            memcpy(st->cg, cgs.hist.data(), st->n_cg * sizeof(hpnn_cg_record));
         }
     }
     /* [keep_best]: the kernel as it was after the best pass's epoch */

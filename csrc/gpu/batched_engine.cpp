@@ -25,11 +25,26 @@ extern "C" BOOL hpnn_gpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
         NN_ERROR(stderr, "GPU batched engine: unsupported dtype %d\n", (int)o->dtype);
         return FALSE;
     }
-    if (o->tp) return hpnn_gpu_train_tp(k, X, T, n, o, st);
     const char *lb = getenv("HPNN_LOOPBACK_RANKS");
     const int lbr = lb ? atoi(lb) : 0;
     const char *fr = getenv("HPNN_FORCE_RCCL");
     const char *nd = getenv("HPNN_NATIVE_DP");
+    if (o->train == NN_TRAIN_CG) {
+        /* [train] CG exists on one device only: its decisions live in one device's memory
+         * (train_single refuses [dtype] bf16) */
+        if (o->tp) {
+            NN_ERROR(stderr, "[train] CG is not supported by tensor-parallel batched training; use one GPU "
+                             "([parallel] dp, 1 GPU) or [train] BP / BPM\n");
+            return FALSE;
+        }
+        if (lbr >= 2 || hpnn_boot_world() > 1 || o->n_gpu > 1 || (fr && fr[0] == '1') || getenv("HPNN_DP_FORCE")) {
+            NN_ERROR(stderr, "[train] CG is not supported by data-parallel batched training; use one GPU or "
+                             "[train] BP / BPM\n");
+            return FALSE;
+        }
+        return train_single(k, X, T, n, o, st);
+    }
+    if (o->tp) return hpnn_gpu_train_tp(k, X, T, n, o, st);
     if (lbr >= 2) return train_dp(k, X, T, n, o, st, lbr, true);
     /* one process per GPU under a launcher (torchrun --no-python bin/train_nn ...);
      * HPNN_DP_FORCE=1: the same path with ONE rank under a launcher (its step structure and

@@ -72,6 +72,7 @@ struct Batched {
     typedef float grad_t;   /* flat gradient buffer (the all-reduce payload) */
     static constexpr hpnn_comm_dtype comm_dt = HPNN_DT_F32;
     static const char *name() { return "bf16"; }
+    static constexpr bool has_cg = false; /* [train] CG: FP64 / FP32 only (its losses need their precision) */
     static constexpr size_t ACC_BYTES = HPNN_STAT_SLOTS * HPNN_STAT_STRIDE * 4;
     static int reduce_sum(grad_t *buf, int G, size_t count, hipStream_t st) {
         return hpnn_reduce_slabs(buf, G, (long)count, (long)count, buf, st);
@@ -433,6 +434,92 @@ struct BatchedFP {
         return upload_x(src, rows, cols, rows, vs);
     }
     float *vacc() { return vslots; }
+
+    /* [train] CG (kernels_cg.hip, docs/DESIGN.md 3.2h): g, g_prev, d and W0 beside the weights in
+     * one allocation (each layer's piece 256-byte aligned), the segment table, the device state
+     * and history, the partials of the dot products and stat slots of CG's own -- allocated by
+     * init_cg only */
+    static constexpr bool has_cg = true;
+    DevBuf<char> cg_mem;
+    DevBuf<hpnn_cg_seg> cg_table;
+    DevBuf<hpnn_cg_state> cg_state;
+    DevBuf<hpnn_cg_record> cg_hist;
+    DevBuf<double> cg_part;
+    DevBuf<float> cg_slots;
+    BOOL init_cg(double a_init, UINT n, UINT iterations) {
+        size_t off[17] = {0};
+        for (int l = 0; l < L; l++) off[l + 1] = off[l] + ((size_t)N[l] * M[l] * sizeof(T) + 255) / 256 * 256;
+        HIPCHK(cg_mem.alloc(4 * off[L]));
+        HIPCHK(hipMemsetAsync(cg_mem.get(), 0, 4 * off[L], s)); /* g_prev = d = 0: the first dots are finite */
+        HIPCHK(cg_table.alloc(L));
+        HIPCHK(cg_state.alloc(1));
+        HIPCHK(cg_hist.alloc(iterations ? iterations : 1));
+        HIPCHK(cg_part.alloc(3 * HPNN_CG_DOT_WGS));
+        HIPCHK(cg_slots.alloc(ACC_BYTES / sizeof(float)));
+        HIPCHK(hipMemsetAsync(cg_slots.get(), 0, ACC_BYTES, s));
+        HIPCHK(hipMemsetAsync(cg_hist.get(), 0, (iterations ? iterations : 1) * sizeof(hpnn_cg_record), s));
+        std::vector<hpnn_cg_seg> h(L);
+        for (int l = 0; l < L; l++) {
+            char *b = cg_mem.get() + off[l];
+            h[l] = {W[l], b, b + off[L], b + 2 * off[L], b + 3 * off[L], slab[l], S[l], (long)N[l] * M[l],
+                    (unsigned long long)N[l] * M[l]};
+        }
+        hpnn_cg_state st;
+        hpnn_cg_state_init(&st, a_init, n, iterations);
+        HIPCHK(hipMemcpyAsync(cg_state.get(), &st, sizeof st, hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (hpnn_cg_table(F64, cg_table.get(), h.data(), L, s)) {
+            NN_ERROR(stderr, "[train] CG: the segment table was refused (alignment or too many layers)\n");
+            return FALSE;
+        }
+        return hpnn_cg_preload(s) == 0;
+    }
+    /* the forward-only loss of the training set into CG's slots: whole Bp-row chunks, as the
+     * gradient pass forwards them, so f0 and a trial at the same weights are the same number */
+    BOOL evaluate_cg(const XSet &xs, const T *Tt, int ldt, int n) {
+        for (long row = 0; row < n; row += Bp) {
+            if (!forward(at(xs, row), Bp)) return FALSE;
+            if (hpnn_cg_loss(F64, Z, N[L - 1], Tt + (size_t)row * ldt, ldt, cg_slots.get(),
+                             (int)std::min((long)Bp, n - row), n_out, type, s))
+                return FALSE;
+        }
+        return TRUE;
+    }
+    /* one CG iteration over the n resident samples (xs / Tt padded to whole Bp-row chunks): every
+     * launch on the stream, every decision on the device */
+    BOOL iterate_cg(const XSet &xs, const T *Tt, int ldt, int n) {
+        hpnn_cg_seg *tb = cg_table.get();
+        hpnn_cg_state *st = cg_state.get();
+        for (long row = 0; row < n; row += Bp) {
+            const int nv = (int)std::min((long)Bp, n - row);
+            const T *tr = Tt + (size_t)row * ldt;
+            if (!backprop(at(xs, row), tr, ldt, nv)) return FALSE;
+            if (hpnn_cg_loss(F64, Z, N[L - 1], tr, ldt, cg_slots.get(), nv, n_out, type, s) ||
+                hpnn_cg_accumulate(F64, tb, L, row == 0, row + Bp >= n ? 1.0 / (double)n : 1.0, s))
+                return FALSE;
+        }
+        if (hpnn_cg_file(cg_slots.get(), st, cg_hist.get(), HPNN_CG_FINAL, s) ||
+            hpnn_cg_dots(F64, tb, L, cg_part.get(), st, s) || hpnn_cg_direction(st, s) ||
+            hpnn_cg_begin(F64, tb, L, st, s))
+            return FALSE;
+        for (int j = 0; j <= HPNN_CG_FINAL; j++) {
+            if (hpnn_cg_trial(F64, tb, L, st, j, s)) return FALSE;
+            if (j == HPNN_CG_FINAL) break;
+            if (!evaluate_cg(xs, Tt, ldt, n) || hpnn_cg_file(cg_slots.get(), st, cg_hist.get(), j, s)) return FALSE;
+        }
+        return hpnn_debug_check("batched CG iteration (fp)") == 0;
+    }
+    /* the records filed so far (synchronises) */
+    BOOL read_cg(std::vector<hpnn_cg_record> &out) {
+        hpnn_cg_state st;
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipMemcpy(&st, cg_state.get(), sizeof st, hipMemcpyDeviceToHost));
+        out.resize(std::min(st.cursor, st.cap));
+        if (!out.empty())
+            HIPCHK(hipMemcpy(out.data(), cg_hist.get(), out.size() * sizeof(hpnn_cg_record), hipMemcpyDeviceToHost));
+        return TRUE;
+    }
+
     BOOL evaluate(const XSet &vs, const T *Tt, int ldt, int nv) {
         for (long row = 0; row < nv; row += Bp) {
             const int rows = (int)std::min((long)Bp, nv - row);

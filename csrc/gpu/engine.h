@@ -14,6 +14,7 @@
 #ifndef HPNN_GPU_ENGINE_H
 #define HPNN_GPU_ENGINE_H
 #include <libhpnn/ann.h>
+#include <libhpnn/cg.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -93,6 +94,10 @@ typedef struct {
     UINT best_index;
     UINT epochs_run;
     UINT stop_epoch;
+    /* [train] CG: one record per iteration (= epoch) of the call up to the last one that counts,
+     * malloc'ed by the engine (the caller frees cg) */
+    hpnn_cg_record *cg;
+    UINT n_cg;
 } hpnn_batched_stats;
 
 /* the improvement rule of [keep_best] (one definition for every engine; the device form is
@@ -131,6 +136,21 @@ BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UIN
 /* one minibatch step on the CPU: returns mean loss before the update */
 DOUBLE hpnn_cpu_batched_step(kernel_ann *k, nn_type type, const DOUBLE *X, const DOUBLE *T, UINT b,
                              DOUBLE lr, BOOL momentum, DOUBLE alpha, UINT *hits /* may be NULL: += argmax hits */);
+
+/* ---- [train] CG on the host (the FP64 oracle and the CPU form of hpnn_amd.ops.cg_*): the
+ * rules of <libhpnn/cg.h> on host memory; f64 selects double, else float ---- */
+/* G[l] (+)= sum_b delta_l^b (x) h_{l-1}^b over the B samples, in sample order (first: G is
+ * overwritten); returns the loss SUM of the batch, *hits += argmax hits */
+DOUBLE hpnn_cpu_batched_grad(kernel_ann *k, nn_type type, const DOUBLE *X, const DOUBLE *T, UINT b, DOUBLE **G,
+                             BOOL first, UINT *hits);
+void hpnn_cg_host_init(hpnn_cg_state *s, double a_init, unsigned int n, unsigned int cap);
+void hpnn_cg_host_accumulate(int f64, void *g, const void *slab, int S, long sstride, long n, int first, double scale);
+/* out[0..2] += <g,g>, <g,g_prev>, <g,d>: FP64 products added in element order */
+void hpnn_cg_host_dots(int f64, const void *g, const void *gprev, const void *d, long n, double *out);
+void hpnn_cg_host_direction(hpnn_cg_state *s);
+void hpnn_cg_host_begin(int f64, const void *w, void *w0, const void *g, void *gprev, void *d, long n, double beta);
+void hpnn_cg_host_trial(int f64, void *w, const void *w0, const void *d, long n, double a);
+void hpnn_cg_host_file(hpnn_cg_state *s, hpnn_cg_record *hist, unsigned int j, double loss_sum, unsigned int hits);
 
 #ifdef __cplusplus
 }

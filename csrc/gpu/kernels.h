@@ -15,6 +15,7 @@
 #ifndef HPNN_GPU_KERNELS_H
 #define HPNN_GPU_KERNELS_H
 #include <hip/hip_runtime_api.h>
+#include <libhpnn/cg.h>
 #include <libhpnn/xar.h>
 
 #ifdef __cplusplus
@@ -375,6 +376,46 @@ int hpnn_snapshot_if(const hpnn_snap_seg *segs, int n_segs, const unsigned int *
  * synchronise: loads the unit's code object before a capture */
 int hpnn_best_empty_launch(hipStream_t stream);
 int hpnn_best_preload(hipStream_t stream);
+/* ---- conjugate-gradient trainer (kernels_cg.hip; [train] CG, rules in <libhpnn/cg.h>) ----
+ * Every launch is capturable, allocates nothing and reads its scalars (beta, the steps a_j) from
+ * the DEVICE state when it runs.  f64 selects double, else float.  A segment is one layer:
+ * n elements of W, W0, g, g_prev, d (element aligned; only the pointers a launch uses need be
+ * set) and the S gradient slabs sstride elements apart that accumulate adds.  hpnn_cg_table
+ * checks a host table (-1: refused, nothing written) and copies it to the device (synchronises:
+ * setup).  Return: 0 launched, -1 refused, -5 launch error. */
+typedef struct {
+    void *w, *w0, *g, *gprev, *d;
+    const void *slab;
+    int S;
+    long sstride;
+    unsigned long long n;
+} hpnn_cg_seg;
+#define HPNN_CG_MAX_SEGS 16
+#define HPNN_CG_DOT_WGS 64 /* partial triples of hpnn_cg_dots: partials holds 3 * 64 doubles */
+int hpnn_cg_table(int f64, hpnn_cg_seg *segs, const hpnn_cg_seg *host_segs, int n_segs, hipStream_t stream);
+/* g = ((first ? 0 : g) + slab[0] + ... + slab[S-1]) * scale, in slab order */
+int hpnn_cg_accumulate(int f64, const hpnn_cg_seg *segs, int n_segs, int first, double scale, hipStream_t stream);
+/* state->gg, gp, gd = <g,g>, <g,g_prev>, <g,d> over all segments: FP64 sums of FP64 products,
+ * bitwise reproducible (two launches: the partials, then their sum in index order) */
+int hpnn_cg_dots(int f64, const hpnn_cg_seg *segs, int n_segs, double *partials, hpnn_cg_state *state,
+                 hipStream_t stream);
+/* one thread: hpnn_cg_rule_direction on the device state */
+int hpnn_cg_direction(hpnn_cg_state *state, hipStream_t stream);
+/* d = fma(beta, d, g) (beta = 0: d = g), g_prev = g, W0 = W */
+int hpnn_cg_begin(int f64, const hpnn_cg_seg *segs, int n_segs, const hpnn_cg_state *state, hipStream_t stream);
+/* W = fma(a[j], d, W0), one fma in T; a[j] = 0: W = W0 bit for bit.  j <= HPNN_CG_FINAL */
+int hpnn_cg_trial(int f64, const hpnn_cg_seg *segs, int n_segs, const hpnn_cg_state *state, int j,
+                  hipStream_t stream);
+/* the output layer forward only over rows [0, n_valid) of the logits Z (type 0 ANN, 1 LNN, 2 SNN,
+ * as hpnn_output_fp): loss sum (FP64, floats 2..3 of a slot) and argmax hits (word 1) added into
+ * the 64 stat slots, bitwise reproducible: 64 workgroups, one writer per slot, no atomics */
+int hpnn_cg_loss(int f64, const void *Z, int ldz, const void *T, int ldt, float *slots, int n_valid, int n_out,
+                 int type, hipStream_t stream);
+/* one 64-lane workgroup: the 64 stat slots (layout of hpnn_validate_commit) summed in slot order
+ * and zeroed, then hpnn_cg_rule_file(state, hist, j, sum, hits); hist may be NULL */
+int hpnn_cg_file(float *slots, hpnn_cg_state *state, hpnn_cg_record *hist, int j, hipStream_t stream);
+/* loads the unit's code object (an empty launch and a synchronise) before a capture */
+int hpnn_cg_preload(hipStream_t stream);
 /* profiling (HPNN_TILE_TRACE=1): per-workgroup s_memtime stamps [1024][12] */
 int hpnn_mlp3_tile_trace(unsigned long long *out);
 /* HPNN_G0_TRACE=1 phase stamps of the fused G0 launch: out[512][8] */

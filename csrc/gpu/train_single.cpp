@@ -23,6 +23,12 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
     hipStream_t s = hpnn_rt_stream(0, 0);
     const int B = (int)(o->batch ? o->batch : 256);
     const bool mom = o->train == NN_TRAIN_BPM;
+    const bool cg = o->train == NN_TRAIN_CG;
+    if (cg && !Net::has_cg) {
+        NN_ERROR(stderr, "[train] CG: the line search compares losses that the BF16 forward cannot resolve; "
+                         "use [dtype] f32 or f64\n");
+        return FALSE;
+    }
     const int n_in = (int)k->n_inputs, n_out = (int)k->n_outputs;
     Net net;
     if (!net.init(k, B, o->type, mom, s, B % 32 == 0)) return FALSE;
@@ -38,8 +44,9 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
      * (n, seed, epochs completed) and the gathers of the canonical row-major copies into it,
      * all on the compute stream (so inside the captured epoch).  One batch per epoch: the
      * order only changes the summation order, nothing is reshuffled. */
-    const bool shuffle = o->shuffle && n_batches > 1;
-    if (o->shuffle && !shuffle) NN_OUT(stdout, "batched GPU training: one batch per epoch, no reshuffle\n");
+    const bool shuffle = o->shuffle && n_batches > 1 && !cg;
+    if (o->shuffle && cg) NN_OUT(stdout, "batched GPU training: CG sums over the whole set, no reshuffle\n");
+    else if (o->shuffle && !shuffle) NN_OUT(stdout, "batched GPU training: one batch per epoch, no reshuffle\n");
     ResidentSet<TT> cn;
     DevBuf<int> perm;
     DevBuf<unsigned int> shw; /* [0] the epoch word, [1] the permutation kernel's error word */
@@ -112,7 +119,19 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
         NN_ERROR(stderr, "batched GPU training: the validation pass could not be launched\n");
         return false;
     };
+    /* [train] CG: one epoch = one conjugate-gradient iteration over the whole set (the gradient
+     * in chunks of B rows, then the fixed-work line search: kernels_cg.hip); its state, like the
+     * best of [keep_best], lives for this call only */
+    if constexpr (Net::has_cg) {
+        if (cg) {
+            if (!net.init_cg(o->lr, n, o->epochs)) return FALSE;
+            NN_OUT(stdout, "batched GPU training: conjugate gradient, one iteration per epoch\n");
+        }
+    }
     auto epoch = [&]() -> bool {
+        if constexpr (Net::has_cg) {
+            if (cg) return net.iterate_cg(xs, Td, n_out, (int)n);
+        }
         if (shuffle && !reshuffle()) {
             NN_ERROR(stderr, "batched GPU training: the epoch reshuffle could not be launched\n");
             return false;
@@ -143,7 +162,9 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
      * [validate] N the replay is a whole number of validation periods where that fits a graph,
      * so every replay has the same pattern of passes; a graph is keyed by its epochs and the
      * offsets of its passes (the last replay, shorter or with the closing pass, is another key) */
-    int epg = metrics ? 1 : std::max(1, std::min(E, 32 / std::max(1, n_batches)));
+    /* a CG iteration (a gradient pass and seven forward passes) launches about as much as three
+     * epochs of steps */
+    int epg = metrics ? 1 : std::max(1, std::min(E, 32 / (std::max(1, n_batches) * (cg ? 3 : 1))));
     if (validate && !metrics && (long)o->validate * n_batches <= 4096)
         epg = std::min(E, (int)((epg + o->validate - 1) / o->validate * o->validate));
     auto gkey = [&](int ne, int e0) {
@@ -249,6 +270,20 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
         vdone = hb.stop ? judged : vrec.size();
     }
     if (ok && validate) vrec.resize(std::min(vdone, vrec.size()));
+    /* [train] CG: the history, once; the epoch's loss is the FP64 f0 of its record.  After a stop
+     * the iterations that ran past the stopping pass are not reported */
+    std::vector<hpnn_cg_record> crec;
+    if constexpr (Net::has_cg) {
+        if (ok && cg) {
+            ok = net.read_cg(crec);
+            if (ok && crec.size() < (size_t)e) {
+                NN_ERROR(stderr, "batched GPU training: %zu CG records filed, %d iterations run\n", crec.size(), e);
+                ok = FALSE;
+            }
+            if (ok && e > 0) ep_loss = crec[e - 1].f0 * (double)n;
+            if (ok) crec.resize(hb.stop && !vrec.empty() ? vsched[vrec.size() - 1] - o->epoch0 : (size_t)e);
+        }
+    }
     graphs.clear();
     if (ok) ok = net.download_from(k, hb.valid ? best.dst.data() : nullptr);
     if (ok && st) {
@@ -257,6 +292,13 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
         st->best_epoch = hb.valid ? vsched[hb.index] : 0;
         st->best_index = hb.valid ? hb.index : 0;
         st->stop_epoch = hb.stop && !vrec.empty() ? vsched[vrec.size() - 1] : 0;
+        st->cg = NULL;
+        st->n_cg = (UINT)crec.size();
+        if (!crec.empty()) {
+            st->cg = (hpnn_cg_record *)malloc(crec.size() * sizeof(hpnn_cg_record));
+            if (!st->cg) ok = FALSE;
+            else memcpy(st->cg, crec.data(), crec.size() * sizeof(hpnn_cg_record));
+        }
         st->val = NULL;
         st->n_val = (UINT)vrec.size();
         if (!vrec.empty()) {

@@ -17,6 +17,7 @@
 #include <pybind11/stl.h>
 
 #include "../gpu/kernels.h"
+#include "../gpu/engine.h"
 #include "../gpu/bplan.h"
 #include "../dist/dp_exchange.h"
 #include <libhpnn/comm.h>
@@ -496,6 +497,64 @@ PYBIND11_MODULE(_native, m) {
         return hpnn_snapshot_if((const hpnn_snap_seg *)P(segs), n_segs, (const unsigned int *)P(take), S(stream));
     });
     m.def("best_empty_launch", [](uptr stream) { return hpnn_best_empty_launch(S(stream)); });
+    /* [train] CG (kernels_cg.hip); each returns the launcher's code (0, or -1: refused).  A segment
+     * is (w, w0, g, gprev, d, slab, S, sstride, n) with device addresses (0 = unused) */
+    m.attr("CG_STATE_BYTES") = (int)sizeof(hpnn_cg_state);
+    m.attr("CG_RECORD_BYTES") = (int)sizeof(hpnn_cg_record);
+    m.attr("CG_SEG_BYTES") = (int)sizeof(hpnn_cg_seg);
+    m.attr("CG_DOT_WGS") = (int)HPNN_CG_DOT_WGS;
+    m.def("cg_table", [](int f64, uptr segs,
+                         const std::vector<std::tuple<uptr, uptr, uptr, uptr, uptr, uptr, int, long, unsigned long long>>
+                             &host,
+                         uptr stream) {
+        std::vector<hpnn_cg_seg> h;
+        for (const auto &t : host)
+            h.push_back({P(std::get<0>(t)), P(std::get<1>(t)), P(std::get<2>(t)), P(std::get<3>(t)), P(std::get<4>(t)),
+                         P(std::get<5>(t)), std::get<6>(t), std::get<7>(t), std::get<8>(t)});
+        return hpnn_cg_table(f64, (hpnn_cg_seg *)P(segs), h.data(), (int)h.size(), S(stream));
+    });
+    m.def("cg_preload", [](uptr stream) { return hpnn_cg_preload(S(stream)); });
+    m.def("cg_accumulate", [](int f64, uptr segs, int n_segs, int first, double scale, uptr stream) {
+        return hpnn_cg_accumulate(f64, (const hpnn_cg_seg *)P(segs), n_segs, first, scale, S(stream));
+    });
+    m.def("cg_dots", [](int f64, uptr segs, int n_segs, uptr partials, uptr state, uptr stream) {
+        return hpnn_cg_dots(f64, (const hpnn_cg_seg *)P(segs), n_segs, (double *)P(partials), (hpnn_cg_state *)P(state),
+                            S(stream));
+    });
+    m.def("cg_direction", [](uptr state, uptr stream) { return hpnn_cg_direction((hpnn_cg_state *)P(state), S(stream)); });
+    m.def("cg_begin", [](int f64, uptr segs, int n_segs, uptr state, uptr stream) {
+        return hpnn_cg_begin(f64, (const hpnn_cg_seg *)P(segs), n_segs, (const hpnn_cg_state *)P(state), S(stream));
+    });
+    m.def("cg_trial", [](int f64, uptr segs, int n_segs, uptr state, int j, uptr stream) {
+        return hpnn_cg_trial(f64, (const hpnn_cg_seg *)P(segs), n_segs, (const hpnn_cg_state *)P(state), j, S(stream));
+    });
+    m.def("cg_loss", [](int f64, uptr Z, int ldz, uptr T, int ldt, uptr slots, int n_valid, int n_out, int type,
+                        uptr stream) {
+        return hpnn_cg_loss(f64, P(Z), ldz, P(T), ldt, (float *)P(slots), n_valid, n_out, type, S(stream));
+    });
+    m.def("cg_file", [](uptr slots, uptr state, uptr hist, int j, uptr stream) {
+        return hpnn_cg_file((float *)P(slots), (hpnn_cg_state *)P(state), (hpnn_cg_record *)P(hist), j, S(stream));
+    });
+    /* the same rules on host memory (csrc/cpu/cpu_cg.cpp, the entry points of <libhpnn/cg.h>) */
+    m.def("cg_host_init", [](uptr state, double a_init, unsigned int n, unsigned int cap) {
+        hpnn_cg_host_init((hpnn_cg_state *)P(state), a_init, n, cap);
+    });
+    m.def("cg_host_accumulate", [](int f64, uptr g, uptr slab, int Sn, long sstride, long n, int first, double scale) {
+        hpnn_cg_host_accumulate(f64, P(g), P(slab), Sn, sstride, n, first, scale);
+    });
+    m.def("cg_host_dots", [](int f64, uptr g, uptr gprev, uptr d, long n, uptr out) {
+        hpnn_cg_host_dots(f64, P(g), P(gprev), P(d), n, (double *)P(out));
+    });
+    m.def("cg_host_direction", [](uptr state) { hpnn_cg_host_direction((hpnn_cg_state *)P(state)); });
+    m.def("cg_host_begin", [](int f64, uptr w, uptr w0, uptr g, uptr gprev, uptr d, long n, double beta) {
+        hpnn_cg_host_begin(f64, P(w), P(w0), P(g), P(gprev), P(d), n, beta);
+    });
+    m.def("cg_host_trial", [](int f64, uptr w, uptr w0, uptr d, long n, double a) {
+        hpnn_cg_host_trial(f64, P(w), P(w0), P(d), n, a);
+    });
+    m.def("cg_host_file", [](uptr state, uptr hist, unsigned int j, double loss_sum, unsigned int hits) {
+        hpnn_cg_host_file((hpnn_cg_state *)P(state), (hpnn_cg_record *)P(hist), j, loss_sum, hits);
+    });
     m.def("mlp3_tile_grid", [](int Bp, int grid) { return hpnn_mlp3_tile_grid(Bp, grid); });
     m.def("mlp3_tile_trace", []() {
         std::vector<unsigned long long> v(1024 * 12);

@@ -22,6 +22,13 @@ NN_DTYPE = {"f64": 0, "f32": 1, "bf16": 2}
 NN_DEVICE = {"auto": 0, "cpu": 1, "gpu": 2}
 NN_SHUFFLE = {"once": 0, "epoch": 1}
 NN_KEEP_BEST = {"off": 0, "loss": 1, "acc": 2}
+CG_FAILED, CG_RESTART, CG_VERTEX, CG_TOOK7 = 1, 2, 4, 8  # flags of a CG record (include/libhpnn/cg.h)
+
+
+class CgRecord(ctypes.Structure):
+    """hpnn_cg_record"""
+    _fields_ = [("f0", ctypes.c_double), ("f1", ctypes.c_double), ("beta", ctypes.c_double),
+                ("alpha", ctypes.c_double), ("trial", ctypes.c_uint), ("flags", ctypes.c_uint)]
 
 
 def lib():
@@ -52,6 +59,7 @@ def lib():
             "nn_set_keep_best": (None, [vp, i]), "nn_return_keep_best": (i, [vp]),
             "nn_set_patience": (None, [vp, u]), "nn_return_patience": (u, [vp]),
             "nn_get_best": (i, [vp, ctypes.POINTER(u), ctypes.POINTER(d), ctypes.POINTER(u), ctypes.POINTER(u)]),
+            "nn_get_cg_history": (ctypes.POINTER(CgRecord), [vp, ctypes.POINTER(u)]),
             "nn_set_batch": (None, [vp, u]), "nn_set_epochs": (None, [vp, u]),
             "nn_set_learning_rate": (None, [vp, d]), "nn_set_momentum": (None, [vp, d]),
             "nn_set_seed": (None, [vp, u]), "nn_return_seed": (u, [vp]),
@@ -154,6 +162,16 @@ class Network:
             return None
         return {"epoch": ep.value, "loss": lo.value, "correct": co.value, "n": nn.value,
                 "accuracy": co.value / nn.value if nn.value else 0.0}
+
+    def cg_history(self):
+        """the [train] CG records of the last train() call, one dict per iteration (= epoch): f0 and
+        f1 (mean loss before / after), beta, alpha (the step taken), trial (j*, None when every
+        trial loss was a NaN), flags (CG_FAILED | CG_RESTART | CG_VERTEX | CG_TOOK7)"""
+        m = ctypes.c_uint()
+        r = self.L.nn_get_cg_history(self.ptr, ctypes.byref(m))
+        return [{"f0": r[i].f0, "f1": r[i].f1, "beta": r[i].beta, "alpha": r[i].alpha,
+                 "trial": None if r[i].trial == 0xffffffff else int(r[i].trial), "flags": int(r[i].flags)}
+                for i in range(m.value)]
 
     @property
     def validate(self):

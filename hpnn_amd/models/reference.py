@@ -86,3 +86,101 @@ def online_step(weights, x, t, net_type, lr, momentum=None, alpha=0.2):
             W += lr * G
     hs = forward(weights, X, net_type)
     return Ep - loss_per_sample(hs[-1], T, net_type)[0], hs[-1][0]
+
+
+# ----------------------------------------------------------------------------- [train] CG
+CG_TRIALS = 6
+CG_FAILED, CG_RESTART, CG_VERTEX, CG_TOOK7 = 1, 2, 4, 8
+
+
+def cg_loss(weights, X, T, net_type):
+    """mean loss (a Python float, summed in FP64) and argmax hits of the set"""
+    o = forward(weights, X, net_type)[-1]
+    hits = int((o.argmax(1) == T.argmax(1)).sum())
+    return float(loss_per_sample(o, T, net_type).double().sum()) / X.shape[0], hits
+
+
+def cg_gradient(weights, X, T, net_type, batch=None):
+    """the descent direction g = (1/n) sum delta (x) h, accumulated in chunks of `batch` rows"""
+    n = X.shape[0]
+    batch = batch or n
+    g = [torch.zeros_like(W) for W in weights]
+    for s in range(0, n, batch):
+        Xb, Tb = X[s:s + batch], T[s:s + batch]
+        hs = forward(weights, Xb, net_type)
+        d = deltas(weights, hs, Tb, net_type)
+        for l in range(len(weights)):
+            g[l] += d[l].t() @ (Xb if l == 0 else hs[l - 1])
+    return [x / n for x in g]
+
+
+def cg_state(weights, lr):
+    """the state of one CG call: the first a_init is lr, the first direction is g"""
+    return {"a_init": float(lr), "first": True, "gg_prev": 0.0, "d": [torch.zeros_like(W) for W in weights],
+            "g_prev": [torch.zeros_like(W) for W in weights]}
+
+
+def cg_iteration(weights, X, T, net_type, state, batch=None):
+    """One nonlinear conjugate-gradient iteration over the whole set, in place on `weights`
+    (include/libhpnn/cg.h, docs/DESIGN.md 3.2h; FP64 tensors = the oracle): Polak-Ribiere+
+    direction, six fixed trials a_init 2^(j-2), the parabola point as the seventh, all
+    forward-only.  Returns the record: f0, f1, beta, alpha, trial (None: every trial a NaN), flags,
+    hits, and phi (the seven trial losses) for the tests' preconditions."""
+    def dot(a, b):
+        return float(sum((x.double() * y.double()).sum() for x, y in zip(a, b)))
+
+    g = cg_gradient(weights, X, T, net_type, batch)
+    f0, hits = cg_loss(weights, X, T, net_type)
+    gg, gp, gd = dot(g, g), dot(g, state["g_prev"]), dot(g, state["d"])
+    beta, flags = 0.0, 0
+    if state["first"] or not state["gg_prev"] > 0.0:
+        flags = CG_RESTART
+    else:
+        beta = (gg - gp) / state["gg_prev"]
+        if not beta > 0.0:
+            beta = 0.0
+        if not gg + beta * gd > 0.0:
+            beta, flags = 0.0, CG_RESTART
+    d = [gi + beta * di if beta else gi.clone() for gi, di in zip(g, state["d"])]
+    state["d"], state["g_prev"], state["gg_prev"] = d, g, gg
+    W0 = [W.clone() for W in weights]
+
+    def phi(a):
+        for W, w0, di in zip(weights, W0, d):
+            W.copy_(w0 + a * di if a else w0)
+        return cg_loss(weights, X, T, net_type)[0]
+
+    a_init = state["a_init"]
+    steps = [a_init * 2.0 ** (j - 2) for j in range(CG_TRIALS)]
+    phis = [phi(a) for a in steps]
+    js = None
+    for j, p in enumerate(phis):
+        if p == p and (js is None or p < phis[js]):
+            js = j
+    a7 = 0.0
+    if js is None or not phis[js] < f0:
+        flags |= CG_FAILED
+    else:
+        b, fb = steps[js], phis[js]
+        a7 = b
+        if js + 1 < CG_TRIALS:
+            a, fa = (steps[js - 1], phis[js - 1]) if js else (0.0, f0)
+            c, fc = steps[js + 1], phis[js + 1]
+            p, q = (b - a) * (fb - fc), (b - c) * (fb - fa)
+            den = p - q
+            if den != 0.0 and den == den:
+                x = b - 0.5 * ((b - a) * p - (b - c) * q) / den
+                if a < x < c:
+                    a7, flags = x, flags | CG_VERTEX
+    f7 = phi(a7)
+    if flags & CG_FAILED:
+        astar, f1 = 0.0, f0
+        state["a_init"], state["first"] = a_init / 16.0, True
+    else:
+        astar, f1 = steps[js], phis[js]
+        if f7 < f1:
+            astar, f1, flags = a7, f7, flags | CG_TOOK7
+        state["a_init"], state["first"] = astar, False
+    phi(astar)
+    return {"f0": f0, "f1": f1, "beta": beta, "alpha": astar, "trial": js, "flags": flags, "hits": hits,
+            "phi": phis + [f7]}

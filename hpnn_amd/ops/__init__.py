@@ -523,6 +523,213 @@ def snapshot_if(segs, take):
         raise RuntimeError(f"snapshot_if failed (rc={rc})")
 
 
+# --------------------------------------------------------------------------- [train] CG
+CG_TRIALS, CG_PARABOLA, CG_FINAL = 6, 6, 7  # HPNN_CG_TRIALS / _PARABOLA / _FINAL (include/libhpnn/cg.h)
+CG_NONE = 0xffffffff
+CG_FAILED, CG_RESTART, CG_VERTEX, CG_TOOK7 = 1, 2, 4, 8
+_CG_D = ("gg", "gp", "gd", "gg_prev", "beta", "a_init")  # float64 words 0..5 of a CG state
+_CG_U = ("hits0", "first", "jstar", "flags", "cursor", "cap", "n")  # int32 words 44..50
+
+
+def cg_state(a_init, n, cap, device="cpu"):
+    """a fresh hpnn_cg_state as [26] float64: gg, gp, gd, gg_prev, beta, a_init, a[8], phi[8]
+    (phi[7] = f0), then the int32 words hits0, first, jstar, flags, cursor, cap, n, pad"""
+    st = torch.zeros(26, dtype=torch.float64)
+    native().cg_host_init(st.data_ptr(), float(a_init), int(n), int(cap))
+    return st.to(device)
+
+
+def read_cg_state(state):
+    """the CG state as a dict (synchronises)"""
+    s = state.cpu()
+    u = s.view(torch.int32)
+    out = {k: float(s[i]) for i, k in enumerate(_CG_D)}
+    out["a"] = [float(x) for x in s[6:14]]
+    out["phi"] = [float(x) for x in s[14:22]]
+    out.update({k: int(u[44 + i]) & 0xffffffff for i, k in enumerate(_CG_U)})
+    return out
+
+
+def write_cg_state(state, **kw):
+    """set fields of a CG state (names of read_cg_state; a / phi as 8-lists); returns the state"""
+    s = state.cpu().clone()
+    u = s.view(torch.int32)
+    for k, v in kw.items():
+        if k in _CG_D:
+            s[_CG_D.index(k)] = v
+        elif k in ("a", "phi"):
+            o = 6 if k == "a" else 14
+            s[o:o + 8] = torch.tensor(v, dtype=torch.float64)
+        else:
+            v = int(v) & 0xffffffff
+            u[44 + _CG_U.index(k)] = v - (1 << 32) if v >= 1 << 31 else v
+    state.copy_(s)
+    return state
+
+
+def cg_history(cap, device="cpu"):
+    """a zeroed history of cap hpnn_cg_record rows as [cap, 5] float64: f0, f1, beta, alpha, then
+    the int32 words trial and flags"""
+    return torch.zeros(max(int(cap), 1), 5, dtype=torch.float64, device=device)
+
+
+def read_cg_history(hist, count):
+    h = hist.cpu()
+    out = []
+    for i in range(int(count)):
+        w = h[i, 4:5].view(torch.int32)
+        t = int(w[0]) & 0xffffffff
+        out.append({"f0": float(h[i, 0]), "f1": float(h[i, 1]), "beta": float(h[i, 2]), "alpha": float(h[i, 3]),
+                    "trial": None if t == CG_NONE else t, "flags": int(w[1]) & 0xffffffff})
+    return out
+
+
+class CgTable:
+    """the segment table of the cg_* ops: one segment per layer, a dict of flat (element stride 1)
+    tensors of one dtype (float64 / float32) under the keys w, w0, g, gprev, d -- only those the
+    ops called need be given -- and slab: [S, n] with any row stride.  At most 16 segments.
+    Device tensors: uploaded once (a [n, 9] int64 device tensor that keeps the tensors alive)."""
+
+    def __init__(self, segs):
+        self.segs = [dict(s) for s in segs]
+        if not 1 <= len(self.segs) <= 16:
+            raise ValueError("CgTable: 1..16 segments")
+        any_t = next(t for t in self.segs[0].values() if t is not None)
+        self.dtype, self.device = any_t.dtype, any_t.device
+        if self.dtype not in (torch.float64, torch.float32):
+            raise ValueError("CgTable: float64 or float32 tensors")
+        self.f64 = int(self.dtype == torch.float64)
+        rows = []
+        for s in self.segs:
+            n = next(t.numel() for k, t in s.items() if t is not None and k != "slab")
+            slab = s.get("slab")
+            for k, t in s.items():
+                if t is None:
+                    continue
+                if t.dtype != self.dtype or t.device != self.device or t.stride(-1) != 1:
+                    raise ValueError("CgTable: one dtype, one device, element stride 1")
+                if (k == "slab" and t.shape[-1] != n) or (k != "slab" and t.numel() != n):
+                    raise ValueError("CgTable: every tensor of a segment has its n elements")
+            s["n"] = n
+            rows.append(tuple(_ptr(s.get(k)) for k in ("w", "w0", "g", "gprev", "d", "slab")) +
+                        (slab.shape[0] if slab is not None else 0,
+                         (slab.stride(0) if slab.shape[0] > 1 else n) if slab is not None else 0, n))
+        self.dev = None
+        if self.device.type != "cpu":
+            self.dev = torch.zeros(len(rows), 9, dtype=torch.int64, device=self.device)
+            rc = native().cg_table(self.f64, self.dev.data_ptr(), rows, _stream())
+            if rc:
+                raise ValueError(f"cg_table refused the segments (rc={rc})")
+        self.rows = rows
+
+    def __len__(self):
+        return len(self.segs)
+
+
+def _cg_rc(rc, what):
+    if rc:
+        raise RuntimeError(f"{what} failed (rc={rc})")
+
+
+def cg_accumulate(table, first, scale=1.0):
+    """g = ((0 if first else g) + slab[0] + slab[1] + ...) * scale per segment, in slab order
+    (csrc/gpu/kernels_cg.hip); one capturable launch for the whole table.  CPU tensors: the host
+    entry point of include/libhpnn/cg.h."""
+    if table.dev is None:
+        for r in table.rows:
+            native().cg_host_accumulate(table.f64, r[2], r[5], r[6], r[7], r[8], int(bool(first)), float(scale))
+        return
+    _cg_rc(native().cg_accumulate(table.f64, table.dev.data_ptr(), len(table), int(bool(first)), float(scale),
+                                  _stream()), "cg_accumulate")
+
+
+def cg_dots(table, state, partials=None):
+    """state.gg, gp, gd = <g,g>, <g,g_prev>, <g,d> over every segment: FP64 sums of FP64 products
+    in a fixed order (bitwise reproducible); two capturable launches.  partials: [3 * 64] float64
+    scratch (allocated when not given)."""
+    if table.dev is None:
+        out = torch.zeros(3, dtype=torch.float64)
+        for r in table.rows:
+            native().cg_host_dots(table.f64, r[2], r[3], r[4], r[8], out.data_ptr())
+        state[0:3] = out
+        return state
+    if partials is None:
+        partials = torch.zeros(3 * native().CG_DOT_WGS, dtype=torch.float64, device=table.device)
+    _cg_rc(native().cg_dots(table.f64, table.dev.data_ptr(), len(table), partials.data_ptr(), state.data_ptr(),
+                            _stream()), "cg_dots")
+    return state
+
+
+def cg_direction(state):
+    """beta (Polak-Ribiere+, 0 on a restart), the restart flag and the six trial steps
+    a_init 2^(j-2) from the state's dot products: one capturable one-thread launch"""
+    if _cpu(state):
+        native().cg_host_direction(state.data_ptr())
+        return state
+    _cg_rc(native().cg_direction(state.data_ptr(), _stream()), "cg_direction")
+    return state
+
+
+def cg_begin(table, state):
+    """d = fma(beta, d, g) (beta = 0: d = g), g_prev = g, W0 = W per segment, beta read from the state"""
+    if table.dev is None:
+        beta = float(state[4])
+        for r in table.rows:
+            native().cg_host_begin(table.f64, r[0], r[1], r[2], r[3], r[4], r[8], beta)
+        return
+    _cg_rc(native().cg_begin(table.f64, table.dev.data_ptr(), len(table), state.data_ptr(), _stream()), "cg_begin")
+
+
+def cg_trial(table, state, j):
+    """W = fma(a[j], d, W0) per segment, one fma in the tensors' dtype, a[j] read from the state when
+    the launch runs; a[j] = 0 gives W0 bit for bit.  j = 6: the parabola point, j = 7: the final step."""
+    if not 0 <= int(j) <= CG_FINAL:
+        raise ValueError(f"cg_trial: j = {j}")
+    if table.dev is None:
+        a = float(state[6 + int(j)])
+        for r in table.rows:
+            native().cg_host_trial(table.f64, r[0], r[1], r[4], r[8], a)
+        return
+    _cg_rc(native().cg_trial(table.f64, table.dev.data_ptr(), len(table), state.data_ptr(), int(j), _stream()),
+           "cg_trial")
+
+
+def cg_loss(Z, T, slots, net_type, n_valid=None):
+    """the output layer forward only over the first n_valid rows of the logits Z [B, n_out]
+    (float64 / float32; net_type TYPE_ANN / TYPE_LNN / TYPE_SNN): the loss sum (float64, floats
+    2..3 of a slot) and the argmax hits (word 1) ADDED into the 64 stat slots [64, 16] float32,
+    bitwise reproducible (64 workgroups, one writer per slot, no atomics).  Device tensors only."""
+    if _cpu(Z):
+        raise NotImplementedError("cg_loss: device tensors only (the CPU oracle is csrc/cpu/cpu_cg.cpp)")
+    n_valid = Z.shape[0] if n_valid is None else int(n_valid)
+    if not 0 <= n_valid <= Z.shape[0] or T.shape[0] < n_valid or Z.dtype != T.dtype:
+        raise ValueError("cg_loss: n_valid rows of Z and T, one dtype")
+    _cg_rc(native().cg_loss(int(Z.dtype == torch.float64), Z.data_ptr(), Z.stride(0), T.data_ptr(), T.stride(0),
+                            slots.data_ptr(), n_valid, Z.shape[1], int(net_type), _stream()), "cg_loss")
+    return slots
+
+
+def cg_file(slots, state, hist, j):
+    """file the loss of trial j: the 64 stat slots summed in slot order (layout of validate_commit)
+    and zeroed, phi[j] = sum / n (j = 7: f0 and its hits); behind j = 5 the choice of j* and of the
+    seventh point, behind j = 6 the step a* and a record appended to hist (cg_history; may be
+    None).  One capturable 64-lane launch; CPU tensors: the same rule through cg.h."""
+    if not 0 <= int(j) <= CG_FINAL:
+        raise ValueError(f"cg_file: j = {j}")
+    if _cpu(slots):
+        loss, hits = 0.0, 0
+        dbl = slots[:, 2:4].contiguous().view(torch.float64).view(-1)
+        word = slots[:, 1].contiguous().view(torch.int32)
+        for i in range(slots.shape[0]):
+            loss += float(slots[i, 0].double()) + float(dbl[i])
+            hits += int(word[i]) & 0xffffffff
+        slots[:, :4] = 0
+        native().cg_host_file(state.data_ptr(), _ptr(hist), int(j), loss, hits & 0xffffffff)
+        return state
+    _cg_rc(native().cg_file(slots.data_ptr(), state.data_ptr(), _ptr(hist), int(j), _stream()), "cg_file")
+    return state
+
+
 WIDE2_K0 = (4096,)  # first-layer input widths of hpnn_wide2_front
 WIDE2_TILE = 128  # samples per tile (the batch must be a multiple)
 

@@ -11,6 +11,7 @@
 #ifndef LIBHPNN_H
 #define LIBHPNN_H
 #include <libhpnn/common.h>
+#include <libhpnn/cg.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -51,7 +52,9 @@ typedef enum {
 typedef enum {
     NN_TRAIN_BP = 0,
     NN_TRAIN_BPM = 1,
-    NN_TRAIN_CG = 2,   /* parsed, not implemented (as in the reference)  */
+    NN_TRAIN_CG = 2,   /* extension: nonlinear conjugate gradient, one iteration per epoch of
+                        * batched training, [dtype] f64 | f32 (<libhpnn/cg.h>; the reference
+                        * parses it and implements nothing) */
     NN_TRAIN_SPLX = 3, /* parsed, not implemented (as in the reference)  */
     NN_TRAIN_UKN = -1,
 } nn_train;
@@ -146,6 +149,10 @@ typedef struct {
     DOUBLE best_loss;
     UINT best_correct;
     UINT best_n;
+    /* -- [train] CG: the records of the last nn_train_kernel call, one per iteration
+     *    (nn_get_cg_history) -- */
+    UINT n_cg_history;
+    void *cg_history;
 } nn_def;
 
 #define _NN(a, b) nn_##a##_##b
@@ -309,6 +316,15 @@ void _NN(set, patience)(nn_def *conf, UINT passes);
 void _NN(get, patience)(nn_def *conf, UINT *passes);
 UINT _NN(return, patience)(nn_def *conf);
 BOOL _NN(get, best)(nn_def *conf, UINT *epoch, DOUBLE *loss, UINT *correct, UINT *n);
+/* [train] CG (batched mode, [dtype] f64 | f32, one device): every epoch is one nonlinear
+ * conjugate-gradient iteration over the whole sample set -- Polak-Ribiere+ direction, a line
+ * search of six fixed trials a_init 2^(j-2) and a parabola point, all forward-only
+ * (<libhpnn/cg.h>).  [batch] is the chunk the gradient is accumulated in, [lr] the first a_init
+ * of a call, [momentum] is unused.  The direction and a_init live for one call: a resumed run
+ * continues epochs_done and starts with a steepest-descent iteration.  nn_train_kernel prints
+ * "CG: epoch E loss=L beta=B alpha=A trial=j" per iteration; nn_get_cg_history returns the
+ * records of the last call (owned by conf; *n = their number, NULL when there is none) */
+const hpnn_cg_record *_NN(get, cg_history)(nn_def *conf, UINT *n);
 /* the [shuffle] epoch permutation (libhpnn/shuffle.h): out[i] = index, in the order drawn once
  * from [seed], of the sample at position i of epoch `epoch` (epochs completed before it) */
 void hpnn_epoch_perm(UINT n, UINT seed, UINT epoch, UINT *out);
