@@ -55,6 +55,8 @@ $(BUILD)/%.o: %.hip $(HDRS) $(HIPSTAMP)
 # the CG decisions (include/libhpnn/cg.h) are the same numbers on the host and on the device:
 # no FP contraction in their device unit either (CXXFLAGS has it off already)
 $(BUILD)/csrc/gpu/kernels_cg.o: HIPFLAGS += -ffp-contract=off
+# the Adam rule (include/libhpnn/adam.h) likewise: the same roundings on both sides
+$(BUILD)/csrc/gpu/kernels_adam.o: HIPFLAGS += -ffp-contract=off
 
 $(LIB): $(CORE_OBJ) $(HIP_OBJ)
 	@mkdir -p $(LIBDIR)

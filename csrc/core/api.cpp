@@ -60,6 +60,7 @@ extern "C" void _NN(init, conf)(nn_def *conf) {
     conf->epochs = 1;
     conf->lr = -1.0;
     conf->momentum = -1.0;
+    conf->beta1 = conf->beta2 = conf->epsilon = conf->decay = NAN; /* not set */
 }
 
 extern "C" void _NN(free, kernel)(nn_def *conf) {
@@ -167,6 +168,20 @@ extern "C" void _NN(set, learning_rate)(nn_def *c, DOUBLE lr) { c->lr = lr; }
 extern "C" DOUBLE _NN(return, learning_rate)(nn_def *c) { return c->lr; }
 extern "C" void _NN(set, momentum)(nn_def *c, DOUBLE a) { c->momentum = a; }
 extern "C" DOUBLE _NN(return, momentum)(nn_def *c) { return c->momentum; }
+extern "C" void _NN(set, adam)(nn_def *c, DOUBLE beta1, DOUBLE beta2, DOUBLE epsilon, DOUBLE decay) {
+    if (!c) return;
+    c->beta1 = beta1;
+    c->beta2 = beta2;
+    c->epsilon = epsilon;
+    c->decay = decay;
+}
+extern "C" void _NN(get, adam)(nn_def *c, DOUBLE *beta1, DOUBLE *beta2, DOUBLE *epsilon, DOUBLE *decay) {
+    if (!c) return;
+    if (beta1) *beta1 = c->beta1 == c->beta1 ? c->beta1 : HPNN_ADAM_BETA1;
+    if (beta2) *beta2 = c->beta2 == c->beta2 ? c->beta2 : HPNN_ADAM_BETA2;
+    if (epsilon) *epsilon = c->epsilon == c->epsilon ? c->epsilon : HPNN_ADAM_EPS;
+    if (decay) *decay = c->decay == c->decay ? c->decay : 0.0;
+}
 extern "C" UINT _NN(return, last_pass)(void) { return g_last_pass; }
 extern "C" UINT _NN(return, last_total)(void) { return g_last_total; }
 
@@ -260,6 +275,7 @@ extern "C" nn_def *_NN(load, conf)(const CHAR *filename) {
             for (auto &ch : u) ch = (char)toupper(ch);
             if (!u.empty() && u[0] == 'B') conf->train = (u.size() > 2 && u[2] == 'M') ? NN_TRAIN_BPM : NN_TRAIN_BP;
             else if (!u.empty() && u[0] == 'C') conf->train = NN_TRAIN_CG;
+            else if (!u.empty() && u[0] == 'A') conf->train = NN_TRAIN_ADAM;
             else if (!u.empty() && u[0] == 'S') conf->train = NN_TRAIN_SPLX;
             else conf->train = NN_TRAIN_UKN;
         } else if (is("sample_dir") || is("samples")) {
@@ -316,6 +332,18 @@ extern "C" nn_def *_NN(load, conf)(const CHAR *filename) {
             conf->lr = strtod(v.c_str(), NULL);
         } else if (is("momentum")) {
             conf->momentum = strtod(v.c_str(), NULL);
+        } else if (is("beta1") || is("beta2") || is("epsilon") || is("decay")) {
+            /* [train] ADAM; no earlier key is a prefix of these ([batch] is not one of [beta1]) */
+            char *end = NULL;
+            const DOUBLE x = strtod(v.c_str(), &end);
+            const bool beta = key[0] == 'b';
+            const bool bad = v.empty() || end == v.c_str() || x != x ||
+                             (beta ? (x < 0.0 || x >= 1.0) : key[0] == 'e' ? !(x > 0.0) : x < 0.0);
+            if (bad)
+                CONF_FAIL("[%s] value: %s (%s)\n", key.c_str(), v.c_str(),
+                          beta ? "0 <= beta < 1" : key[0] == 'e' ? "> 0" : ">= 0");
+            (beta ? (key.compare(0, 5, "beta1") == 0 ? conf->beta1 : conf->beta2)
+                  : key[0] == 'e' ? conf->epsilon : conf->decay) = x;
         }
     }
     fclose(fp);
@@ -351,7 +379,7 @@ fail:
 extern "C" void _NN(dump, conf)(nn_def *conf, FILE *fp) {
     if (!conf) return;
     static const char *tn[] = {"ANN", "LNN", "SNN"};
-    static const char *trn[] = {"BP", "BPM", "CG", "SPLX"};
+    static const char *trn[] = {"BP", "BPM", "CG", "SPLX", "ADAM"};
     _OUT(fp, "# NN configuration (libhpnn-mi355x)\n");
     _OUT(fp, "[name] %s\n", conf->name ? conf->name : "noname");
     _OUT(fp, "[type] %s\n", (conf->type >= 0 && conf->type <= 2) ? tn[conf->type] : "UKN");
@@ -365,7 +393,7 @@ extern "C" void _NN(dump, conf)(nn_def *conf, FILE *fp) {
         for (UINT i = 0; i < k->n_hiddens; i++) _OUT(fp, " %u", k->hiddens[i].n_neurons);
         _OUT(fp, "\n[outputs] %u\n", k->n_outputs);
     }
-    _OUT(fp, "[train] %s\n", (conf->train >= 0 && conf->train <= 3) ? trn[conf->train] : "UKN");
+    _OUT(fp, "[train] %s\n", (conf->train >= 0 && conf->train <= 4) ? trn[conf->train] : "UKN");
     if (conf->samples) _OUT(fp, "[sample_dir] %s\n", conf->samples);
     if (conf->tests) _OUT(fp, "[test_dir] %s\n", conf->tests);
     if (conf->mode == NN_MODE_BATCHED) {
@@ -380,6 +408,10 @@ extern "C" void _NN(dump, conf)(nn_def *conf, FILE *fp) {
     if (conf->patience) _OUT(fp, "[patience] %u\n", conf->patience);
     if (conf->lr > 0) _OUT(fp, "[lr] %.17g\n", conf->lr);
     if (conf->momentum >= 0) _OUT(fp, "[momentum] %.17g\n", conf->momentum);
+    if (conf->beta1 == conf->beta1) _OUT(fp, "[beta1] %.17g\n", conf->beta1);
+    if (conf->beta2 == conf->beta2) _OUT(fp, "[beta2] %.17g\n", conf->beta2);
+    if (conf->epsilon == conf->epsilon) _OUT(fp, "[epsilon] %.17g\n", conf->epsilon);
+    if (conf->decay == conf->decay) _OUT(fp, "[decay] %.17g\n", conf->decay);
 }
 
 /* ------------------------------------------------------------------ */
@@ -543,6 +575,7 @@ static bool use_gpu(const nn_def *conf) {
 
 static DOUBLE default_lr(const nn_def *conf, bool gpu) {
     if (conf->lr > 0) return conf->lr;
+    if (conf->train == NN_TRAIN_ADAM) return ADAM_LEARN_RATE;
     if (gpu || conf->mode == NN_MODE_BATCHED) return GPU_LEARN_RATE;
     if (conf->type == NN_TYPE_ANN) return conf->train == NN_TRAIN_BPM ? BPM_LEARN_RATE : BP_LEARN_RATE;
     return GPU_LEARN_RATE;
@@ -556,7 +589,8 @@ static DOUBLE default_alpha(const nn_def *conf) { return conf->momentum >= 0 ? c
 extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
     if (!conf || !conf->kernel || !conf->samples || conf->type == NN_TYPE_UKN) return FALSE;
     kernel_ann *k = KERN(conf);
-    if (conf->train != NN_TRAIN_BP && conf->train != NN_TRAIN_BPM && conf->train != NN_TRAIN_CG) {
+    if (conf->train != NN_TRAIN_BP && conf->train != NN_TRAIN_BPM && conf->train != NN_TRAIN_CG &&
+        conf->train != NN_TRAIN_ADAM) {
         NN_ERROR(stdout, "unimplemented training type!\n");
         return FALSE;
     }
@@ -572,6 +606,22 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
                              "use [dtype] f32 or f64\n");
             return FALSE;
         }
+    }
+    DOUBLE beta1 = 0.0, beta2 = 0.0, epsilon = 0.0, decay = 0.0;
+    if (conf->train == NN_TRAIN_ADAM) {
+        /* the moments are those of a minibatch sequence: there is none in online mode */
+        if (conf->mode != NN_MODE_BATCHED) {
+            NN_ERROR(stderr, "[train] ADAM needs [mode] batched (its moments run over minibatch steps); "
+                             "online mode trains with BP or BPM\n");
+            return FALSE;
+        }
+        _NN(get, adam)(conf, &beta1, &beta2, &epsilon, &decay);
+        if (!hpnn_adam_valid(0.0, beta1, beta2, epsilon, decay)) {
+            NN_ERROR(stderr, "[train] ADAM: beta1 %g, beta2 %g, epsilon %g, decay %g are out of range "
+                             "(0 <= beta < 1, epsilon > 0, decay >= 0)\n", beta1, beta2, epsilon, decay);
+            return FALSE;
+        }
+        if (conf->momentum >= 0) NN_OUT(stdout, "[train] ADAM: [momentum] is unused (the moments decay with [beta1], [beta2])\n");
     }
     HpnnTraceRange tr("nn_train_kernel");
     HpnnSamples src;
@@ -638,6 +688,10 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
         o.alpha = conf->train == NN_TRAIN_BPM ? alpha : 0.0;
         o.seed = conf->seed;
         o.resume = conf->resume && k->dw != NULL;
+        o.beta1 = beta1;
+        o.beta2 = beta2;
+        o.eps = epsilon;
+        o.decay = decay;
         o.epoch0 = conf->epochs_done;
         o.shuffle = conf->shuffle == NN_SHUFFLE_EPOCH ? 1 : 0;
         o.validate = conf->validate;

@@ -54,6 +54,9 @@ extern "C" kernel_ann *ann_kernel_allocate(UINT n_inputs, UINT n_hiddens, const 
     k->tmp_cpu = (DOUBLE *)calloc(mx, sizeof(DOUBLE));
     k->dw = NULL;
     k->gpu = NULL;
+    k->dv = NULL;
+    k->adam_t = 0;
+    k->adam_p1 = k->adam_p2 = 1.0;
     return k;
 }
 
@@ -64,6 +67,7 @@ extern "C" void ann_kernel_free(kernel_ann *k) {
     if (!k) return;
     if (k->gpu && hpnn_gpu_model_destroy_hook) hpnn_gpu_model_destroy_hook(k);
     ann_momentum_free(k);
+    ann_adam_free(k);
     for (UINT i = 0; i < k->n_hiddens; i++) {
         free(k->hiddens[i].weights);
         free(k->hiddens[i].vec);

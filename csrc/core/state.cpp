@@ -13,10 +13,12 @@
  *   char magic[8] = "HPNNSTA1"
  *   u32 type, train, L (weight layers), has_momentum
  *   u32 dims[L + 1]             n_in, h_1 .. h_{L-1}, n_out
- *   u32 seed, epochs_done, reserved[2]
+ *   u32 seed, epochs_done, has_adam, reserved
  *   u64 samples_seen
  *   f64 W_l (N_l x M_l row-major), l = 0 .. L-1
- *   f64 dW_l (same shapes)      when has_momentum
+ *   f64 dW_l (same shapes)      when has_momentum ([train] ADAM: the first moment)
+ *   f64 V_l (same shapes)       when has_adam: the second moment, then
+ *   u64 t, f64 p1, f64 p2       the steps taken and the running products beta1^t, beta2^t
  *   u64 FNV-1a checksum of every byte above
  */
 #include <libhpnn/ann.h>
@@ -75,12 +77,14 @@ extern "C" BOOL _NN(dump, state)(nn_def *conf, const CHAR *filename) {
     w.u32((UINT)conf->type);
     w.u32((UINT)conf->train);
     w.u32(L);
+    /* a BP / BPM file is the same bytes whatever an earlier ADAM call left in the kernel */
+    const bool adam = conf->train == NN_TRAIN_ADAM && k->dw && k->dv;
     w.u32(k->dw ? 1u : 0u);
     w.u32(k->n_inputs);
     for (UINT l = 0; l < L; l++) w.u32(layer_at(k, l)->n_neurons);
     w.u32(conf->seed);
     w.u32(conf->epochs_done);
-    w.u32(0);
+    w.u32(adam ? 1u : 0u);
     w.u32(0);
     w.put(&conf->samples_seen, 8);
     for (UINT l = 0; l < L; l++) {
@@ -92,6 +96,15 @@ extern "C" BOOL _NN(dump, state)(nn_def *conf, const CHAR *filename) {
             const layer_ann *ly = layer_at(k, l);
             w.put(k->dw[l], sizeof(DOUBLE) * ly->n_neurons * ly->n_inputs);
         }
+    if (adam) {
+        for (UINT l = 0; l < L; l++) {
+            const layer_ann *ly = layer_at(k, l);
+            w.put(k->dv[l], sizeof(DOUBLE) * ly->n_neurons * ly->n_inputs);
+        }
+        w.put(&k->adam_t, 8);
+        w.put(&k->adam_p1, 8);
+        w.put(&k->adam_p2, 8);
+    }
     const UINT64 h = hpnn_fnv1a(w.buf.data(), w.buf.size(), HPNN_FNV_SEED);
     w.put(&h, 8);
     /* write to a temporary name, then rename: a crash mid-write never leaves a torn state */
@@ -148,11 +161,17 @@ extern "C" BOOL _NN(load, state)(nn_def *conf, const CHAR *filename) {
         return FALSE;
     }
     const UINT seed = r.u32(), epochs = r.u32();
+    const UINT has_adam = r.u32();
     r.u32();
-    r.u32();
+    if (has_adam > 1 || (has_adam && !has_mom)) {
+        NN_ERROR(stderr, "state file %s: bad Adam flag\n", filename);
+        return FALSE;
+    }
     UINT64 seen = 0;
     r.get(&seen, 8);
-    std::vector<std::vector<DOUBLE>> W(L), V(L);
+    std::vector<std::vector<DOUBLE>> W(L), V(L), A(L);
+    UINT64 at = 0;
+    DOUBLE ap1 = 1.0, ap2 = 1.0;
     for (UINT l = 0; l < L; l++) {
         const layer_ann *ly = layer_at(k, l);
         W[l].resize((size_t)ly->n_neurons * ly->n_inputs);
@@ -163,22 +182,48 @@ extern "C" BOOL _NN(load, state)(nn_def *conf, const CHAR *filename) {
             V[l].resize(W[l].size());
             r.get(V[l].data(), V[l].size() * 8);
         }
+    if (has_adam) {
+        for (UINT l = 0; l < L; l++) {
+            A[l].resize(W[l].size());
+            r.get(A[l].data(), A[l].size() * 8);
+        }
+        r.get(&at, 8);
+        r.get(&ap1, 8);
+        r.get(&ap2, 8);
+    }
     if (!r.ok || r.off != buf.size() - 8) {
         NN_ERROR(stderr, "state file %s: bad size\n", filename);
         return FALSE;
     }
     for (UINT l = 0; l < L; l++) memcpy(layer_at(k, l)->weights, W[l].data(), W[l].size() * 8);
-    if (has_mom) {
+    const bool want_adam = conf->train == NN_TRAIN_ADAM;
+    ann_adam_free(k);
+    if (has_adam && !want_adam) {
+        NN_WARN(stderr, "state file %s holds Adam moments but [train] is not ADAM: the moments are ignored\n",
+                filename);
+    } else if (has_mom && !has_adam && want_adam) {
+        NN_WARN(stderr, "state file %s holds a BPM momentum but [train] is ADAM: the moments start at zero\n",
+                filename);
+    }
+    const bool take_mom = has_mom && (has_adam == (want_adam ? 1u : 0u));
+    if (take_mom) {
         ann_momentum_init(k);
         for (UINT l = 0; l < L; l++) memcpy(k->dw[l], V[l].data(), V[l].size() * 8);
+    }
+    if (take_mom && has_adam) {
+        ann_adam_init(k);
+        for (UINT l = 0; l < L; l++) memcpy(k->dv[l], A[l].data(), A[l].size() * 8);
+        k->adam_t = at;
+        k->adam_p1 = ap1;
+        k->adam_p2 = ap2;
     }
     hpnn_gpu_mark_host_dirty(k);
     conf->seed = seed;
     conf->epochs_done = epochs;
     conf->samples_seen = seen;
-    conf->resume = has_mom ? TRUE : FALSE;
+    conf->resume = take_mom ? TRUE : FALSE;
     NN_OUT(stdout, "state %s loaded: %u epochs done, %llu samples seen%s\n", filename, epochs,
-           (unsigned long long)seen, has_mom ? ", momentum restored" : "");
+           (unsigned long long)seen, take_mom ? (has_adam ? ", Adam moments restored" : ", momentum restored") : "");
     return TRUE;
 }
 

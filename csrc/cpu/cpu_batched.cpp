@@ -185,6 +185,24 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
         ann_momentum_init(k);
         if (!keep) ann_raz_momentum(k);
     }
+    /* [train] ADAM: the moments in k->dw (first) and k->dv (second), the running state in the
+     * kernel; zero unless the call resumes a loaded state */
+    const bool adam = o->train == NN_TRAIN_ADAM;
+    hpnn_adam_state ast;
+    hpnn_adam_state_init(&ast, o->lr, o->beta1, o->beta2, o->eps, o->decay);
+    if (adam) {
+        if (!hpnn_adam_valid(o->lr, o->beta1, o->beta2, o->eps, o->decay)) {
+            NN_ERROR(stderr, "[train] ADAM: needs 0 <= beta1, beta2 < 1, epsilon > 0, decay >= 0\n");
+            return FALSE;
+        }
+        const bool keep = o->resume && k->dw && k->dv;
+        if (!keep) ann_adam_free(k);
+        ann_adam_init(k);
+        if (!keep) ann_raz_momentum(k);
+        ast.t = k->adam_t;
+        ast.p1 = k->adam_p1;
+        ast.p2 = k->adam_p2;
+    }
     const UINT B = o->batch ? o->batch : 1;
     /* [shuffle] epoch: epoch e trains on a permuted copy, position i = sample src(i) of
      * <libhpnn/shuffle.h> for (n, seed, epochs completed); one batch per epoch: nothing to do */
@@ -213,7 +231,8 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
     const bool keep = validate && o->keep_best != 0;
     const UINT L = k->n_hiddens + 1;
     auto layer = [&](UINT l) { return l + 1 < L ? &k->hiddens[l] : &k->output; };
-    std::vector<std::vector<DOUBLE>> bestW, bestV;
+    std::vector<std::vector<DOUBLE>> bestW, bestV, bestA;
+    hpnn_adam_state best_ast = ast;
     bool have_best = false, stop = false;
     DOUBLE best_sum = 0.0;
     UINT best_hits = 0, best_index = 0, stale = 0, epochs_run = 0;
@@ -243,8 +262,9 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
         }
         for (UINT s = 0; s < n && !cg; s += B) {
             UINT b = (n - s < B) ? n - s : B;
-            last = hpnn_cpu_batched_step(k, o->type, Xe + (size_t)s * k->n_inputs, Te + (size_t)s * k->n_outputs, b,
-                                         o->lr, mom, o->alpha, &hits);
+            const DOUBLE *xb = Xe + (size_t)s * k->n_inputs, *tb = Te + (size_t)s * k->n_outputs;
+            last = adam ? hpnn_cpu_adam_step(k, o->type, xb, tb, b, &ast, &hits)
+                        : hpnn_cpu_batched_step(k, o->type, xb, tb, b, o->lr, mom, o->alpha, &hits);
             acc += last;
             nb++;
             samples += b;
@@ -267,11 +287,14 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
                 best_index = (UINT)val.size() - 1;
                 stale = 0;
                 bestW.resize(L);
-                bestV.resize(mom ? L : 0);
+                bestV.resize(mom || adam ? L : 0);
+                bestA.resize(adam ? L : 0);
+                best_ast = ast;
                 for (UINT l = 0; l < L; l++) {
                     const size_t nw = (size_t)layer(l)->n_neurons * layer(l)->n_inputs;
                     bestW[l].assign(layer(l)->weights, layer(l)->weights + nw);
-                    if (mom) bestV[l].assign(k->dw[l], k->dw[l] + nw);
+                    if (mom || adam) bestV[l].assign(k->dw[l], k->dw[l] + nw);
+                    if (adam) bestA[l].assign(k->dv[l], k->dv[l] + nw);
                 }
             } else if (keep) {
                 stale++;
@@ -321,7 +344,13 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
     /* [keep_best]: the kernel as it was after the best pass's epoch */
     for (UINT l = 0; have_best && l < L; l++) {
         memcpy(layer(l)->weights, bestW[l].data(), bestW[l].size() * sizeof(DOUBLE));
-        if (mom) memcpy(k->dw[l], bestV[l].data(), bestV[l].size() * sizeof(DOUBLE));
+        if (mom || adam) memcpy(k->dw[l], bestV[l].data(), bestV[l].size() * sizeof(DOUBLE));
+        if (adam) memcpy(k->dv[l], bestA[l].data(), bestA[l].size() * sizeof(DOUBLE));
+    }
+    if (adam && have_best) {
+        k->adam_t = best_ast.t;
+        k->adam_p1 = best_ast.p1;
+        k->adam_p2 = best_ast.p2;
     }
     /* the momentum stays in k->dw: nn_dump_state saves it for an exact resume */
     return TRUE;

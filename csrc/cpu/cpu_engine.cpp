@@ -190,6 +190,29 @@ extern "C" void ann_momentum_free(kernel_ann *k) {
     k->dw = NULL;
 }
 
+extern "C" BOOL ann_adam_init(kernel_ann *k) {
+    if (!k || !ann_momentum_init(k)) return FALSE;
+    if (k->dv) return TRUE;
+    k->dv = (DOUBLE **)calloc(k->n_hiddens + 1, sizeof(DOUBLE *));
+    for (UINT l = 0; l < k->n_hiddens; l++)
+        k->dv[l] = (DOUBLE *)calloc((size_t)k->hiddens[l].n_neurons * k->hiddens[l].n_inputs, sizeof(DOUBLE));
+    k->dv[k->n_hiddens] = (DOUBLE *)calloc((size_t)k->output.n_neurons * k->output.n_inputs, sizeof(DOUBLE));
+    k->adam_t = 0;
+    k->adam_p1 = k->adam_p2 = 1.0;
+    return TRUE;
+}
+
+extern "C" void ann_adam_free(kernel_ann *k) {
+    if (!k) return;
+    if (k->dv) {
+        for (UINT l = 0; l <= k->n_hiddens; l++) free(k->dv[l]);
+        free(k->dv);
+    }
+    k->dv = NULL;
+    k->adam_t = 0;
+    k->adam_p1 = k->adam_p2 = 1.0;
+}
+
 static void argmax_target(const DOUBLE *o, const DOUBLE *t, UINT n, UINT *max_p, UINT *p_trg) {
     DOUBLE probe = -1.0;
     *max_p = 0;

@@ -44,6 +44,21 @@ extern "C" BOOL hpnn_gpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
         }
         return train_single(k, X, T, n, o, st);
     }
+    if (o->train == NN_TRAIN_ADAM) {
+        /* [train] ADAM exists on one device only: its moments and its step count live beside one
+         * device's masters */
+        if (o->tp) {
+            NN_ERROR(stderr, "[train] ADAM is not supported by tensor-parallel batched training; use one GPU "
+                             "([parallel] dp, 1 GPU) or [train] BP / BPM\n");
+            return FALSE;
+        }
+        if (lbr >= 2 || hpnn_boot_world() > 1 || o->n_gpu > 1 || (fr && fr[0] == '1') || getenv("HPNN_DP_FORCE")) {
+            NN_ERROR(stderr, "[train] ADAM is not supported by data-parallel batched training; use one GPU or "
+                             "[train] BP / BPM\n");
+            return FALSE;
+        }
+        return train_single(k, X, T, n, o, st);
+    }
     if (o->tp) return hpnn_gpu_train_tp(k, X, T, n, o, st);
     if (lbr >= 2) return train_dp(k, X, T, n, o, st, lbr, true);
     /* one process per GPU under a launcher (torchrun --no-python bin/train_nn ...);

@@ -73,6 +73,18 @@ struct Batched {
     static constexpr hpnn_comm_dtype comm_dt = HPNN_DT_F32;
     static const char *name() { return "bf16"; }
     static constexpr bool has_cg = false; /* [train] CG: FP64 / FP32 only (its losses need their precision) */
+    /* [train] ADAM: the plan's optimizer (BPlan::set_adam, before init): V32 is the first moment,
+     * A32 the second, the device state one more buffer of the plan */
+    static constexpr bool has_adam = true;
+    bool adam = false;
+    BOOL set_adam(const hpnn_adam_state &a) {
+        adam = p.set_adam(a.lr, a.beta1, a.beta2, a.eps, a.decay) == 0;
+        return adam ? TRUE : FALSE;
+    }
+    /* the plan's step ignores lr and alpha under ADAM */
+    BOOL step_adam(const XSet &xs, long row, const float *T, int ldt, int n_valid) {
+        return step(xs, row, T, ldt, n_valid, 0.f, 0.f, false);
+    }
     static constexpr size_t ACC_BYTES = HPNN_STAT_SLOTS * HPNN_STAT_STRIDE * 4;
     static int reduce_sum(grad_t *buf, int G, size_t count, hipStream_t st) {
         return hpnn_reduce_slabs(buf, G, (long)count, (long)count, buf, st);
@@ -135,6 +147,7 @@ struct Batched {
             if (!pad_f32(p.W32[l], ly->weights, ly, l)) return FALSE;
         }
         if (p.cast_weights(s)) return FALSE;
+        if (adam && hpnn_adam_preload(s)) return FALSE;
         acc = p.stats;
         gflat = p.gflat;
         memcpy(goff, p.goff, sizeof goff);
@@ -327,13 +340,16 @@ struct Batched {
     std::vector<std::pair<const void *, size_t>> masters() const {
         std::vector<std::pair<const void *, size_t>> v;
         for (int l = 0; l < L; l++)
-            for (const float *b : {p.W32[l], p.V32[l]})
+            for (const float *b : {p.W32[l], p.V32[l], p.A32[l]})
                 if (b) v.push_back({b, (size_t)p.Np[l] * p.Kp[l] * 4});
+        /* [train] ADAM: the state (t, p1, p2 and the coefficients) is one more segment */
+        if (adam) v.push_back({p.adam_dev, sizeof(hpnn_adam_state)});
         return v;
     }
     BOOL download_from(kernel_ann *k, void *const *src) {
         HIPCHK(hipStreamSynchronize(s));
         if (p.V32[0]) ann_momentum_init(k);
+        if (adam) ann_adam_init(k);
         for (int l = 0, i = 0; l < L; l++) {
             layer_ann *ly = layer_of(k, l);
             if (!unpad(ly->weights, src ? (const float *)src[i] : p.W32[l], ly, l)) return FALSE;
@@ -341,6 +357,16 @@ struct Batched {
             if (!p.V32[l]) continue;
             if (!unpad(k->dw[l], src ? (const float *)src[i] : p.V32[l], ly, l)) return FALSE;
             i++;
+            if (!p.A32[l]) continue;
+            if (!unpad(k->dv[l], src ? (const float *)src[i] : p.A32[l], ly, l)) return FALSE;
+            i++;
+        }
+        if (adam) {
+            hpnn_adam_state st;
+            HIPCHK(hipMemcpy(&st, src ? src[3 * L] : (const void *)p.adam_dev, sizeof st, hipMemcpyDeviceToHost));
+            k->adam_t = st.t;
+            k->adam_p1 = st.p1;
+            k->adam_p2 = st.p2;
         }
         return TRUE;
     }
@@ -351,23 +377,29 @@ struct Batched {
         out.clear();
         HIPCHK(hipStreamSynchronize(s));
         for (int l = 0; l < L; l++)
-            for (float *b : {p.W32[l], p.V32[l]}) {
+            for (float *b : {p.W32[l], p.V32[l], p.A32[l]}) {
                 if (!b) continue;
                 const size_t n = (size_t)p.Np[l] * p.Kp[l] * 4, o = out.size();
                 out.resize(o + n);
                 HIPCHK(hipMemcpy(out.data() + o, b, n, hipMemcpyDeviceToHost));
             }
+        if (adam) {
+            const size_t o = out.size();
+            out.resize(o + sizeof(hpnn_adam_state));
+            HIPCHK(hipMemcpy(out.data() + o, p.adam_dev, sizeof(hpnn_adam_state), hipMemcpyDeviceToHost));
+        }
         return TRUE;
     }
     BOOL set_state(const char *in) {
         size_t o = 0;
         for (int l = 0; l < L; l++)
-            for (float *b : {p.W32[l], p.V32[l]}) {
+            for (float *b : {p.W32[l], p.V32[l], p.A32[l]}) {
                 if (!b) continue;
                 const size_t n = (size_t)p.Np[l] * p.Kp[l] * 4;
                 HIPCHK(hipMemcpy(b, in + o, n, hipMemcpyHostToDevice));
                 o += n;
             }
+        if (adam) HIPCHK(hipMemcpy(p.adam_dev, in + o, sizeof(hpnn_adam_state), hipMemcpyHostToDevice));
         return p.cast_weights(s) == 0 && hipStreamSynchronize(s) == hipSuccess;
     }
 
@@ -376,6 +408,21 @@ struct Batched {
         if (!k->dw) return TRUE;
         for (int l = 0; l < L; l++)
             if (p.V32[l] && !pad_f32(p.V32[l], k->dw[l], layer_of((kernel_ann *)k, l), l)) return FALSE;
+        return TRUE;
+    }
+    /* exact resume under ADAM: both moments (the padding stays zero) and t, p1, p2 */
+    BOOL upload_moments(const kernel_ann *k) {
+        if (!adam || !k->dw || !k->dv) return TRUE;
+        if (!upload_momentum(k)) return FALSE;
+        for (int l = 0; l < L; l++)
+            if (!pad_f32(p.A32[l], k->dv[l], layer_of((kernel_ann *)k, l), l)) return FALSE;
+        hpnn_adam_state st;
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipMemcpy(&st, p.adam_dev, sizeof st, hipMemcpyDeviceToHost));
+        st.t = k->adam_t;
+        st.p1 = k->adam_p1;
+        st.p2 = k->adam_p2;
+        HIPCHK(hipMemcpy(p.adam_dev, &st, sizeof st, hipMemcpyHostToDevice));
         return TRUE;
     }
 };
@@ -520,6 +567,68 @@ struct BatchedFP {
         return TRUE;
     }
 
+    /* [train] ADAM (kernels_adam.hip, docs/DESIGN.md 3.2i): V[l] is the first moment, A2[l] the
+     * second, both zeroed; the segment table and the device state -- allocated by init_adam only
+     * (init was given momentum = true, so V exists) */
+    static constexpr bool has_adam = true;
+    T *A2[16] = {0};
+    DevBuf<hpnn_adam_seg> adam_table;
+    DevBuf<hpnn_adam_state> adam_state;
+    bool adam = false, adam_req = false;
+    hpnn_adam_state adam_cfg;
+    BOOL set_adam(const hpnn_adam_state &a) { /* before init (given momentum = true): it ends in init_adam */
+        adam_cfg = a;
+        adam_req = true;
+        return TRUE;
+    }
+    BOOL init_adam(const hpnn_adam_state &st0) {
+        std::vector<hpnn_adam_seg> h(L);
+        for (int l = 0; l < L; l++) {
+            const size_t nw = (size_t)N[l] * M[l];
+            if (!V[l]) return FALSE;
+            HIPCHK(hpnn_dev_malloc(&A2[l], nw * sizeof(T)));
+            HIPCHK(hipMemsetAsync(A2[l], 0, nw * sizeof(T), s));
+            h[l] = {W[l], V[l], A2[l], slab[l], S[l], 0, 0, 0, (long)nw, (unsigned long long)nw};
+        }
+        HIPCHK(adam_table.alloc(L));
+        HIPCHK(adam_state.alloc(1));
+        HIPCHK(hipMemcpyAsync(adam_state.get(), &st0, sizeof st0, hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (hpnn_adam_table(F64, adam_table.get(), h.data(), L, s)) {
+            NN_ERROR(stderr, "[train] ADAM: the segment table was refused (alignment or too many layers)\n");
+            return FALSE;
+        }
+        adam = true;
+        return hpnn_adam_preload(s) == 0;
+    }
+    /* backprop -> advance -> one update launch over every layer */
+    BOOL step_adam(const XSet &xs, long row, const T *Tt, int ldt, int n_valid) {
+        if (!backprop(at(xs, row), Tt, ldt, n_valid)) return FALSE;
+        if (hpnn_adam_advance_dev(adam_state.get(), s) ||
+            hpnn_adam_fp(F64, adam_table.get(), L, 1.0 / (double)n_valid, adam_state.get(), s))
+            return FALSE;
+        return hpnn_debug_check("batched Adam step (fp)") == 0;
+    }
+    /* exact resume: the moments k->dw, k->dv (host FP64) -> V, A2; t, p1, p2 -> the device state */
+    BOOL upload_moments(const kernel_ann *k) {
+        if (!adam || !k->dw || !k->dv) return TRUE;
+        if (!upload_momentum(k)) return FALSE;
+        for (int l = 0; l < L; l++) {
+            const size_t nw = (size_t)N[l] * M[l];
+            std::vector<T> tmp(nw);
+            for (size_t i = 0; i < nw; i++) tmp[i] = (T)k->dv[l][i];
+            HIPCHK(hipMemcpyAsync(A2[l], tmp.data(), nw * sizeof(T), hipMemcpyHostToDevice, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        hpnn_adam_state st;
+        HIPCHK(hipMemcpy(&st, adam_state.get(), sizeof st, hipMemcpyDeviceToHost));
+        st.t = k->adam_t;
+        st.p1 = k->adam_p1;
+        st.p2 = k->adam_p2;
+        HIPCHK(hipMemcpy(adam_state.get(), &st, sizeof st, hipMemcpyHostToDevice));
+        return TRUE;
+    }
+
     BOOL evaluate(const XSet &vs, const T *Tt, int ldt, int nv) {
         for (long row = 0; row < nv; row += Bp) {
             const int rows = (int)std::min((long)Bp, nv - row);
@@ -537,6 +646,7 @@ struct BatchedFP {
         for (int l = 0; l < 16; l++) {
             hpnn_dev_free(W[l]);
             hpnn_dev_free(V[l]);
+            hpnn_dev_free(A2[l]);
             hpnn_dev_free(slab[l]);
             hpnn_dev_free(H[l]);
             hpnn_dev_free(D[l]);
@@ -578,7 +688,7 @@ struct BatchedFP {
         HIPCHK(hpnn_dev_malloc(&Z, (size_t)Bp * N[L - 1] * sizeof(T)));
         HIPCHK(hpnn_dev_malloc(&acc, ACC_BYTES));
         HIPCHK(hipMemsetAsync(acc, 0, ACC_BYTES, s));
-        return TRUE;
+        return adam_req ? init_adam(adam_cfg) : TRUE;
     }
 
     BOOL forward(const void *X, int rows) {
@@ -700,17 +810,20 @@ struct BatchedFP {
     void detach_dpx() {}
 
     BOOL download(kernel_ann *k) { return download_from(k, nullptr); }
-    /* [keep_best]: as Batched::masters / download_from (unpadded, any shape) */
+    /* [keep_best]: as Batched::masters / download_from (unpadded, any shape); with ADAM the second
+     * moment follows the first, and the device state is one more segment behind the last layer */
     std::vector<std::pair<const void *, size_t>> masters() const {
         std::vector<std::pair<const void *, size_t>> v;
         for (int l = 0; l < L; l++)
-            for (const T *b : {W[l], V[l]})
+            for (const T *b : {W[l], V[l], A2[l]})
                 if (b) v.push_back({b, (size_t)N[l] * M[l] * sizeof(T)});
+        if (adam) v.push_back({adam_state.get(), sizeof(hpnn_adam_state)});
         return v;
     }
     BOOL download_from(kernel_ann *k, void *const *src) {
         HIPCHK(hipStreamSynchronize(s));
         if (V[0]) ann_momentum_init(k);
+        if (adam) ann_adam_init(k);
         for (int l = 0, j = 0; l < L; l++) {
             layer_ann *ly = layer_of(k, l);
             const size_t nw = (size_t)N[l] * M[l];
@@ -722,6 +835,17 @@ struct BatchedFP {
             HIPCHK(hipMemcpy(tmp.data(), src ? (const T *)src[j] : V[l], nw * sizeof(T), hipMemcpyDeviceToHost));
             j++;
             for (size_t i = 0; i < nw; i++) k->dw[l][i] = (DOUBLE)tmp[i];
+            if (!A2[l]) continue;
+            HIPCHK(hipMemcpy(tmp.data(), src ? (const T *)src[j] : A2[l], nw * sizeof(T), hipMemcpyDeviceToHost));
+            j++;
+            for (size_t i = 0; i < nw; i++) k->dv[l][i] = (DOUBLE)tmp[i];
+        }
+        if (adam) {
+            hpnn_adam_state st;
+            HIPCHK(hipMemcpy(&st, src ? src[3 * L] : (const void *)adam_state.get(), sizeof st, hipMemcpyDeviceToHost));
+            k->adam_t = st.t;
+            k->adam_p1 = st.p1;
+            k->adam_p2 = st.p2;
         }
         return TRUE;
     }
@@ -730,23 +854,29 @@ struct BatchedFP {
         out.clear();
         HIPCHK(hipStreamSynchronize(s));
         for (int l = 0; l < L; l++)
-            for (T *b : {W[l], V[l]}) {
+            for (T *b : {W[l], V[l], A2[l]}) {
                 if (!b) continue;
                 const size_t n = (size_t)N[l] * M[l] * sizeof(T), o = out.size();
                 out.resize(o + n);
                 HIPCHK(hipMemcpy(out.data() + o, b, n, hipMemcpyDeviceToHost));
             }
+        if (adam) {
+            const size_t o = out.size();
+            out.resize(o + sizeof(hpnn_adam_state));
+            HIPCHK(hipMemcpy(out.data() + o, adam_state.get(), sizeof(hpnn_adam_state), hipMemcpyDeviceToHost));
+        }
         return TRUE;
     }
     BOOL set_state(const char *in) {
         size_t o = 0;
         for (int l = 0; l < L; l++)
-            for (T *b : {W[l], V[l]}) {
+            for (T *b : {W[l], V[l], A2[l]}) {
                 if (!b) continue;
                 const size_t n = (size_t)N[l] * M[l] * sizeof(T);
                 HIPCHK(hipMemcpy(b, in + o, n, hipMemcpyHostToDevice));
                 o += n;
             }
+        if (adam) HIPCHK(hipMemcpy(adam_state.get(), in + o, sizeof(hpnn_adam_state), hipMemcpyHostToDevice));
         return TRUE;
     }
 

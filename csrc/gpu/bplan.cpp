@@ -81,6 +81,14 @@ int BPlan::pick_splits(int Np, int Kp, int Bp) {
     return s < 1 ? 1 : s;
 }
 
+int BPlan::set_adam(double lr, double beta1, double beta2, double eps, double decay) {
+    if (!hpnn_adam_valid(lr, beta1, beta2, eps, decay)) return -1;
+    hpnn_adam_state_init(&adam0, lr, beta1, beta2, eps, decay);
+    adam = true;
+    g0_fused = tn_update = tn8_side = false;
+    return 0;
+}
+
 int BPlan::configure(const int *sizes, int n_layers, int net_type, int batch_size, bool momentum_, int fused,
                      const int *splits, int mid_grid_req, bool device, std::string *err) {
     auto fail = [&](int code, const std::string &m) {
@@ -93,7 +101,7 @@ int BPlan::configure(const int *sizes, int n_layers, int net_type, int batch_siz
     L = n_layers;
     type = net_type;
     batch = batch_size;
-    momentum = momentum_;
+    momentum = momentum_ || adam; /* the first moment lives in V32 */
     on_device = device;
     n_out = sizes[L];
     for (int l = 0; l < L; l++) {
@@ -163,12 +171,14 @@ int BPlan::configure(const int *sizes, int n_layers, int net_type, int batch_siz
     for (int l = 0; l < L; l++) {
         add("W32", l, BD_F32, {Np[l], Kp[l]}, true);
         if (momentum) add("V32", l, BD_F32, {Np[l], Kp[l]}, true);
+        if (adam) add("A32", l, BD_F32, {Np[l], Kp[l]}, true);
         add("Wb", l, BD_BF16, {Np[l], Kp[l]}, true);
         add("Wt", l, BD_BF16, {Kp[l], Np[l]}, true);
         add("slab", l, BD_F32, {S[l], Np[l], Kp[l]}, false);
         if (l < L - 1) add("H", l, BD_BF16, {Bp, Np[l]}, false);
         add("D", l, BD_BF16, {Bp, Np[l]}, false);
     }
+    if (adam) add("adam", -1, BD_F32, {(long)(sizeof(hpnn_adam_state) / 4)}, true);
     add("gflat", -1, BD_F32, {(long)goff[L]}, true);
     add("Z", -1, BD_F32, {Bp, Np[L - 1]}, false);
     add("stats", -1, BD_F32, {HPNN_STAT_SLOTS, HPNN_STAT_STRIDE}, true);
@@ -203,12 +213,14 @@ void BPlan::name_pointers() {
     for (int l = 0; l < L; l++) {
         W32[l] = (float *)buf("W32", l);
         V32[l] = (float *)buf("V32", l);
+        A32[l] = (float *)buf("A32", l);
         Wb[l] = buf("Wb", l);
         Wt[l] = buf("Wt", l);
         slab[l] = (float *)buf("slab", l);
         H[l] = buf("H", l);
         D[l] = buf("D", l);
     }
+    adam_dev = (hpnn_adam_state *)buf("adam");
     gflat = (float *)buf("gflat");
     Z = (float *)buf("Z");
     stats = (float *)buf("stats");
@@ -231,6 +243,8 @@ int BPlan::allocate(hipStream_t s) {
         if (specs[i].zero && hipMemsetAsync(ptr_[i], 0, specs[i].bytes(), s) != hipSuccess) return -7;
     }
     name_pointers();
+    /* adam0 is a member: it outlives the copy */
+    if (adam && hipMemcpyAsync(adam_dev, &adam0, sizeof adam0, hipMemcpyHostToDevice, s) != hipSuccess) return -7;
     return 0;
 }
 
@@ -325,13 +339,35 @@ int BPlan::grad_layer(int l, const XIn &x, bool reduce, hipStream_t s) {
     return r;
 }
 
+int BPlan::apply_optimizer(const hpnn_upd_layer *u, int n, float lr, float alpha, float scale, hipStream_t s) {
+    if (!adam) return hpnn_sgd_update_multi(u, n, lr, alpha, scale, momentum ? 1 : 0, s);
+    if (!adam_dev) return -1;
+    int r = hpnn_adam_advance_dev(adam_dev, s);
+    adam_launches++;
+    for (int i0 = 0; !r && i0 < n; i0 += HPNN_UPD_MAX) {
+        hpnn_adam_upd_layer a[HPNN_UPD_MAX];
+        const int cnt = n - i0 < HPNN_UPD_MAX ? n - i0 : HPNN_UPD_MAX;
+        for (int i = 0; i < cnt; i++) {
+            int l = 0;
+            while (l < L && W32[l] != u[i0 + i].W32) l++;
+            if (l == L) return -1;
+            a[i].u = u[i0 + i];
+            a[i].A32 = A32[l];
+        }
+        r = hpnn_adam_update_multi(a, cnt, scale, adam_dev, s);
+        adam_launches++;
+    }
+    return r;
+}
+
 int BPlan::update_layer(int l, float lr, float alpha, float scale, bool from_g, hipStream_t s) {
+    if (adam) return -1; /* one advance per step: the whole net goes through apply_optimizer */
     const float *G = from_g ? gflat + goff[l] : slab[l];
     const int Sn = from_g ? 1 : S[l];
     const long gs = from_g ? 0 : (long)Np[l] * Kp[l];
     if (l == 0 && W0f) {
         hpnn_upd_layer u = {W32[0], V32[0], G, gs, Wb[0], Wt[0], W0f, Sn, Np[0], Kp[0]};
-        return hpnn_sgd_update_multi(&u, 1, lr, alpha, scale, momentum ? 1 : 0, s);
+        return apply_optimizer(&u, 1, lr, alpha, scale, s);
     }
     return hpnn_sgd_update(W32[l], V32[l], G, Sn, gs, Wb[l], Wt[l], Np[l], Kp[l], lr, alpha, scale, momentum ? 1 : 0,
                            s);
@@ -425,6 +461,15 @@ bool BPlan::tn_update_ok(int l) const {
 /* from the last layer to the first: gradient + step per layer (the deltas were all computed
  * with the pre-update weights already) */
 int BPlan::grad_and_update_layers(const XIn &x, float lr, float alpha, float scale, hipStream_t s) {
+    if (adam) { /* every gradient into its slabs, then the one update over all layers */
+        hpnn_upd_layer u[16];
+        for (int l = L - 1; l >= 0; l--) {
+            const int r = grad_layer(l, x, false, s);
+            if (r) return r;
+            u[l] = {W32[l], V32[l], slab[l], (long)Np[l] * Kp[l], Wb[l], Wt[l], l == 0 ? W0f : nullptr, S[l], Np[l], Kp[l]};
+        }
+        return apply_optimizer(u, L, lr, alpha, scale, s);
+    }
     /* a two-layer net (RRUFF): layer 1's gradient + step ride in layer 0's fused launch as its
      * side job (bitwise the separate gemm_tn + update launches; HPNN_TN8_SIDE=0: off) */
     if (L == 2 && tn8_side && tncnt && g0_fused && S[0] > 1 && !W0f) {
@@ -478,7 +523,7 @@ int BPlan::step(const XIn &x, const int *labels, const float *T, int ldt, int n_
             {W32[0], V32[0], slab[0], (long)Np[0] * Kp[0], Wb[0], Wt[0], W0f, S[0], Np[0], Kp[0]},
             {W32[1], V32[1], midtmp, slab_f, Wb[1], Wt[1], nullptr, mid_groups, Np[1], Kp[1]},
             {W32[2], V32[2], midtmp + n1, slab_f, Wb[2], Wt[2], nullptr, mid_groups, Np[2], Kp[2]}};
-        return hpnn_sgd_update_multi(u, 3, lr, alpha, scale, momentum ? 1 : 0, s);
+        return apply_optimizer(u, 3, lr, alpha, scale, s);
     }
     case 'w':
         /* one launch up to the deltas, then per-layer gradient + step (one multi-layer update
@@ -492,7 +537,7 @@ int BPlan::step(const XIn &x, const int *labels, const float *T, int ldt, int n_
             if ((r = backward_layer(l, s))) return r;
         /* every delta above used the pre-update weights: all gradients, then ONE update launch
          * for the layers whose step did not already run in the gradient GEMM's epilogue */
-        hpnn_upd_layer u[HPNN_UPD_MAX];
+        hpnn_upd_layer u[16];
         int nu = 0;
         for (int l = 0; l < L; l++) {
             const void *Hin = l ? H[l - 1] : x.x;
@@ -500,12 +545,12 @@ int BPlan::step(const XIn &x, const int *labels, const float *T, int ldt, int n_
                                                         Wb[l], Wt[l], lr, alpha, scale, momentum ? 1 : 0, s) == 0)
                 continue;
             if ((r = grad_layer(l, x, false, s))) return r;
-            if (L <= HPNN_UPD_MAX)
+            if (adam || L <= HPNN_UPD_MAX)
                 u[nu++] = {W32[l], V32[l], slab[l], (long)Np[l] * Kp[l], Wb[l], Wt[l], nullptr, S[l], Np[l], Kp[l]};
             else if ((r = update_layer(l, lr, alpha, scale, false, s)))
                 return r;
         }
-        return nu ? hpnn_sgd_update_multi(u, nu, lr, alpha, scale, momentum ? 1 : 0, s) : 0;
+        return nu ? apply_optimizer(u, nu, lr, alpha, scale, s) : 0;
     }
     }
 }
@@ -648,7 +693,7 @@ int BPlan::grads_slabs(const XIn &x, const int *labels, const float *T, int ldt,
 }
 
 int BPlan::update_flat(const float *G, float lr, float alpha, float scale, hipStream_t s) {
-    if (L > HPNN_UPD_MAX) {
+    if (L > HPNN_UPD_MAX && !adam) {
         for (int l = 0; l < L; l++) {
             int r = hpnn_sgd_update(W32[l], V32[l], G + goff[l], 1, 0, Wb[l], Wt[l], Np[l], Kp[l], lr, alpha, scale,
                                     momentum ? 1 : 0, s);
@@ -656,10 +701,10 @@ int BPlan::update_flat(const float *G, float lr, float alpha, float scale, hipSt
         }
         return 0;
     }
-    hpnn_upd_layer u[HPNN_UPD_MAX];
+    hpnn_upd_layer u[16];
     for (int l = 0; l < L; l++)
         u[l] = {W32[l], V32[l], G + goff[l], 0, Wb[l], Wt[l], l == 0 ? W0f : nullptr, 1, Np[l], Kp[l]};
-    return hpnn_sgd_update_multi(u, L, lr, alpha, scale, momentum ? 1 : 0, s);
+    return apply_optimizer(u, L, lr, alpha, scale, s);
 }
 
 int BPlan::evaluate(const XIn &x, const int *labels, const float *T, int ldt, int n_valid, float *slots, int *guess,

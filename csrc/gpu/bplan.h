@@ -91,12 +91,24 @@ class BPlan {
     /* two-layer nets: layer 1's gradient + step as the side job of layer 0's fused TN launch */
     bool tn8_side = [] { const char *e = getenv("HPNN_TN8_SIDE"); return !(e && e[0] == '0'); }();
     long side_launches = 0; /* launches issued with that side job (tests) */
+    /* [train] ADAM (set_adam): the optimizer of every step; V32 is then the first moment, A32
+     * the second, "adam" the device hpnn_adam_state the update reads when it runs */
+    bool adam = false;
+    hpnn_adam_state adam0;  /* the state a fresh plan starts from (allocate uploads it) */
+    long adam_launches = 0; /* launches of kernels_adam.hip issued by this plan (tests) */
     /* per-layer: the delta GEMM reads W (NN form, hpnn_gemm_nn_bf16) instead of W^T, which is
      * then not kept current (the sharded data-parallel step sets it: no transpose per update) */
     bool nn_bwd[16] = {false};
     size_t goff[17] = {0};
     std::vector<BufSpec> specs;
 
+    /* [train] ADAM, before configure: Adam / AdamW (<libhpnn/adam.h>) takes the place of BP / BPM.
+     * Forces the moments on (V32, plus the specs "A32" per layer and "adam", the state) and turns
+     * off the three places where a BP / BPM step is fused into a gradient launch (g0_fused,
+     * tn_update, tn8_side), so every mode runs its unfused sequence and ends in the advance plus
+     * ONE hpnn_adam_update_multi over all layers.  step() / update_flat() then ignore their lr and
+     * alpha; update_layer() is refused (one advance per step).  -1: coefficients out of range. */
+    int set_adam(double lr, double beta1, double beta2, double eps, double decay);
     /* fused: -1 auto (the fastest eligible mode), 0 per-layer only, or 't' / 'x' / 'm' / 'w'
      * (an error when not eligible); splits: per-layer split-K override (null / 0 = pick);
      * mid_grid_req: block slabs of mode 'm'; on_device = false: a host-only configuration
@@ -188,7 +200,8 @@ class BPlan {
     int read_stats(double *loss, unsigned int *hits, hipStream_t s);
 
     /* named pointers (valid after allocate / bind) */
-    float *W32[16] = {0}, *V32[16] = {0}, *slab[16] = {0};
+    float *W32[16] = {0}, *V32[16] = {0}, *A32[16] = {0}, *slab[16] = {0};
+    hpnn_adam_state *adam_dev = nullptr;
     void *Wb[16] = {0}, *Wt[16] = {0}, *H[16] = {0}, *D[16] = {0};
     float *Z = nullptr, *stats = nullptr, *vstats = nullptr, *gflat = nullptr, *midslab = nullptr, *midtmp = nullptr;
     void *W0f = nullptr;
@@ -205,6 +218,9 @@ class BPlan {
     std::vector<void *> ptr_;
     bool owns_ = false;
     unsigned long long *digest_ = nullptr; /* device word of weights_digest */
+    /* the one place a step's optimizer is applied to layers whose gradients are in memory:
+     * hpnn_sgd_update_multi, or under ADAM the advance plus hpnn_adam_update_multi */
+    int apply_optimizer(const hpnn_upd_layer *u, int n, float lr, float alpha, float scale, hipStream_t s);
     int grad_and_update_layers(const XIn &x, float lr, float alpha, float scale, hipStream_t s);
     int g0_reduce(const XIn &x, hipStream_t s);
     int g0_fused_step(const XIn &x, float lr, float alpha, float scale, hipStream_t s, float *gout = nullptr,

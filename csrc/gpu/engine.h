@@ -15,6 +15,7 @@
 #define HPNN_GPU_ENGINE_H
 #include <libhpnn/ann.h>
 #include <libhpnn/cg.h>
+#include <libhpnn/adam.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -66,6 +67,9 @@ typedef struct {
      * improved.  Both need validate > 0 (single-device engines). */
     UINT keep_best;
     UINT patience;
+    /* [train] ADAM: the coefficients (lr is the step size, alpha is unused); resume: start from
+     * the moments k->dw, k->dv and k->adam_t, adam_p1, adam_p2 */
+    DOUBLE beta1, beta2, eps, decay;
 } hpnn_batched_opts;
 
 /* one validation pass: the absolute epoch it followed, the mean loss per sample and the argmax
@@ -151,6 +155,19 @@ void hpnn_cg_host_direction(hpnn_cg_state *s);
 void hpnn_cg_host_begin(int f64, const void *w, void *w0, const void *g, void *gprev, void *d, long n, double beta);
 void hpnn_cg_host_trial(int f64, void *w, const void *w0, const void *d, long n, double a);
 void hpnn_cg_host_file(hpnn_cg_state *s, hpnn_cg_record *hist, unsigned int j, double loss_sum, unsigned int hits);
+
+/* ---- [train] ADAM on the host (the FP64 oracle and the CPU form of hpnn_amd.ops.adam_*): the
+ * rule of <libhpnn/adam.h> on host memory; f64 selects double, else float ---- */
+void hpnn_adam_host_init(hpnn_adam_state *s, double lr, double beta1, double beta2, double eps, double decay);
+void hpnn_adam_host_advance(hpnn_adam_state *s);
+/* g = (G[0] + G[1] + ... + G[S-1]) * scale, slabs gstride elements apart, in slab order; then the
+ * rule on W, M (first moment), V (second moment) with the coefficients the last advance derived */
+void hpnn_adam_host_update(int f64, void *W, void *M, void *V, const void *G, int S, long gstride, long n,
+                           double scale, const hpnn_adam_state *s);
+/* one minibatch Adam step on the CPU (FP64; k->dw, k->dv allocated: ann_adam_init): advances s,
+ * mirrors t, p1, p2 into the kernel; returns the mean loss before the update */
+DOUBLE hpnn_cpu_adam_step(kernel_ann *k, nn_type type, const DOUBLE *X, const DOUBLE *T, UINT b, hpnn_adam_state *s,
+                          UINT *hits /* may be NULL: += argmax hits */);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,7 @@
 #define HPNN_GPU_KERNELS_H
 #include <hip/hip_runtime_api.h>
 #include <libhpnn/cg.h>
+#include <libhpnn/adam.h>
 #include <libhpnn/xar.h>
 
 #ifdef __cplusplus
@@ -416,6 +417,43 @@ int hpnn_cg_loss(int f64, const void *Z, int ldz, const void *T, int ldt, float 
 int hpnn_cg_file(float *slots, hpnn_cg_state *state, hpnn_cg_record *hist, int j, hipStream_t stream);
 /* loads the unit's code object (an empty launch and a synchronise) before a capture */
 int hpnn_cg_preload(hipStream_t stream);
+/* ---- Adam trainer (kernels_adam.hip; [train] ADAM, rule in <libhpnn/adam.h>) ----
+ * Every launch is capturable, allocates nothing and reads the state (the bias corrections of the
+ * step) from DEVICE memory when it runs.  f64 selects double, else float.  A segment is one
+ * layer: the weights, the two moments, n elements each, and the S gradient slabs gstride
+ * elements apart.  hpnn_adam_table checks a host table (-1: refused, nothing written), fills
+ * first_block / blocks (the workgroups of the launch that own the segment) and copies it to the
+ * device (synchronises: setup).  Return: 0 launched, -1 refused, -5 launch error. */
+typedef struct {
+    void *w, *m, *v;
+    const void *g;
+    int S;
+    int blocks;      /* filled by hpnn_adam_table */
+    int first_block; /* filled by hpnn_adam_table */
+    int pad;
+    long gstride;
+    unsigned long long n;
+} hpnn_adam_seg;
+#define HPNN_ADAM_MAX_SEGS 16
+int hpnn_adam_table(int f64, hpnn_adam_seg *segs, const hpnn_adam_seg *host_segs, int n_segs, hipStream_t stream);
+/* one thread: hpnn_adam_advance on the device state */
+int hpnn_adam_advance_dev(hpnn_adam_state *state, hipStream_t stream);
+/* every segment in one launch: g = (slab[0] + ... + slab[S-1]) * scale in slab order, then the
+ * rule of adam.h in T with the coefficients the last advance left in *state */
+int hpnn_adam_fp(int f64, const hpnn_adam_seg *segs, int n_segs, double scale, const hpnn_adam_state *state,
+                 hipStream_t stream);
+/* the BF16 plan's update, every layer (n <= HPNN_UPD_MAX) in one launch: the layer descriptor
+ * of hpnn_sgd_update_multi (V32 = the first moment) plus the second moment A32.  g = scale * the
+ * S slabs summed in the kernel's one fixed order (kernels_adam.hip), the rule of adam.h in FP32,
+ * then BF16 W, W^T and Wf exactly where hpnn_sgd_update_multi writes them */
+typedef struct {
+    hpnn_upd_layer u;
+    float *A32;
+} hpnn_adam_upd_layer;
+int hpnn_adam_update_multi(const hpnn_adam_upd_layer *layers, int n, float scale, const hpnn_adam_state *state,
+                           hipStream_t stream);
+/* loads the unit's code object (an empty launch and a synchronise) before a capture */
+int hpnn_adam_preload(hipStream_t stream);
 /* profiling (HPNN_TILE_TRACE=1): per-workgroup s_memtime stamps [1024][12] */
 int hpnn_mlp3_tile_trace(unsigned long long *out);
 /* HPNN_G0_TRACE=1 phase stamps of the fused G0 launch: out[512][8] */

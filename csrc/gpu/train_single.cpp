@@ -29,11 +29,28 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
                          "use [dtype] f32 or f64\n");
         return FALSE;
     }
+    const bool adam = o->train == NN_TRAIN_ADAM;
+    if (adam && !hpnn_adam_valid(o->lr, o->beta1, o->beta2, o->eps, o->decay)) {
+        NN_ERROR(stderr, "[train] ADAM: needs 0 <= beta1, beta2 < 1, epsilon > 0, decay >= 0\n");
+        return FALSE;
+    }
     const int n_in = (int)k->n_inputs, n_out = (int)k->n_outputs;
     Net net;
-    if (!net.init(k, B, o->type, mom, s, B % 32 == 0)) return FALSE;
+    /* [train] ADAM: the moments beside the masters and the device state the update launches read
+     * when they run; zero and t = 0 unless the call resumes a loaded state */
+    if (adam) {
+        hpnn_adam_state ast;
+        hpnn_adam_state_init(&ast, o->lr, o->beta1, o->beta2, o->eps, o->decay);
+        if (!net.set_adam(ast)) return FALSE;
+    }
+    if (!net.init(k, B, o->type, mom || adam, s, B % 32 == 0)) return FALSE;
     NN_OUT(stdout, "batched GPU training: %s, %d samples per step\n", Net::name(), B);
     if (mom && o->resume && !net.upload_momentum(k)) return FALSE;
+    if (adam) {
+        if (o->resume && k->dv && !net.upload_moments(k)) return FALSE;
+        NN_OUT(stdout, "batched GPU training: Adam, beta1 %g beta2 %g epsilon %g decay %g\n", o->beta1, o->beta2,
+               o->eps, o->decay);
+    }
     const int n_batches = (int)((n + B - 1) / B);
     int rows_p = (n_batches - 1) * B + net.Bp; /* last batch reads Bp rows */
     ResidentSet<TT> tr;
@@ -139,6 +156,10 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
         for (int b = 0; b < n_batches; b++) {
             int start, nv, total;
             hpnn_dp_shard(b, B, (int)n, 0, B, &start, &nv, &total);
+            if (adam) {
+                if (!net.step_adam(xs, start, Td + (size_t)start * n_out, n_out, nv)) return false;
+                continue;
+            }
             if (!net.step(xs, start, Td + (size_t)start * n_out, n_out, nv, o->lr, o->alpha, mom)) return false;
         }
         return true;

@@ -51,10 +51,19 @@ XIn xin(uptr x, uptr xg, int u8, float scale) {
 void bind_plan(py::module_ &m) {
     py::class_<BPlan>(m, "BPlan")
         .def(py::init([](std::vector<int> sizes, int type, int batch, bool momentum, int fused,
-                         std::vector<int> splits, int mid_grid, bool device) {
+                         std::vector<int> splits, int mid_grid, bool device, py::object adam) {
                  auto *p = new BPlan();
                  std::string err;
                  if (sizes.size() < 2) throw std::runtime_error("BPlan: at least two layer sizes");
+                 if (!adam.is_none()) { /* (lr, beta1, beta2, eps, decay): BPlan::set_adam before configure */
+                     py::tuple a = adam.cast<py::tuple>();
+                     if (py::len(a) != 5 || p->set_adam(a[0].cast<double>(), a[1].cast<double>(), a[2].cast<double>(),
+                                                        a[3].cast<double>(), a[4].cast<double>())) {
+                         delete p;
+                         throw std::invalid_argument("BPlan: adam = (lr, 0 <= beta1 < 1, 0 <= beta2 < 1, eps > 0, "
+                                                     "decay >= 0)");
+                     }
+                 }
                  std::vector<int> sp(sizes.size(), 0);
                  for (size_t i = 0; i < splits.size() && i < sp.size(); i++) sp[i] = splits[i];
                  const int rc = p->configure(sizes.data(), (int)sizes.size() - 1, type, batch, momentum, fused,
@@ -66,7 +75,8 @@ void bind_plan(py::module_ &m) {
                  return p;
              }),
              py::arg("sizes"), py::arg("type"), py::arg("batch"), py::arg("momentum"), py::arg("fused") = -1,
-             py::arg("splits") = std::vector<int>(), py::arg("mid_grid") = 512, py::arg("device") = true)
+             py::arg("splits") = std::vector<int>(), py::arg("mid_grid") = 512, py::arg("device") = true,
+             py::arg("adam") = py::none())
         .def("config",
              [](const BPlan &p) {
                  py::dict d;
@@ -197,6 +207,8 @@ void bind_plan(py::module_ &m) {
         .def_readwrite("tn_update", &BPlan::tn_update)
         .def_readwrite("tn8_side", &BPlan::tn8_side)
         .def_readwrite("side_launches", &BPlan::side_launches)
+        .def_readonly("adam", &BPlan::adam)
+        .def_readwrite("adam_launches", &BPlan::adam_launches)
         .def_property_readonly("nn_bwd", [](const BPlan &p) { return std::vector<bool>(p.nn_bwd, p.nn_bwd + 16); })
         .def("tn_update_ok", &BPlan::tn_update_ok)
         .def("predict", [](BPlan &p, uptr X, int n_valid, uptr O, int ldo, uptr s) {
@@ -555,6 +567,34 @@ PYBIND11_MODULE(_native, m) {
     m.def("cg_host_file", [](uptr state, uptr hist, unsigned int j, double loss_sum, unsigned int hits) {
         hpnn_cg_host_file((hpnn_cg_state *)P(state), (hpnn_cg_record *)P(hist), j, loss_sum, hits);
     });
+    /* [train] ADAM (csrc/gpu/kernels_adam.hip; the host forms: csrc/cpu/cpu_adam.cpp) */
+    m.attr("ADAM_STATE_BYTES") = (int)sizeof(hpnn_adam_state);
+    m.attr("ADAM_SEG_BYTES") = (int)sizeof(hpnn_adam_seg);
+    m.def("adam_table", [](int f64, uptr segs,
+                           const std::vector<std::tuple<uptr, uptr, uptr, uptr, int, long, unsigned long long>> &host,
+                           uptr stream) {
+        std::vector<hpnn_adam_seg> h;
+        for (const auto &t : host)
+            h.push_back({P(std::get<0>(t)), P(std::get<1>(t)), P(std::get<2>(t)), P(std::get<3>(t)), std::get<4>(t), 0, 0,
+                         0, std::get<5>(t), std::get<6>(t)});
+        return hpnn_adam_table(f64, (hpnn_adam_seg *)P(segs), h.data(), (int)h.size(), S(stream));
+    });
+    m.def("adam_preload", [](uptr stream) { return hpnn_adam_preload(S(stream)); });
+    m.def("adam_advance", [](uptr state, uptr stream) {
+        return hpnn_adam_advance_dev((hpnn_adam_state *)P(state), S(stream));
+    });
+    m.def("adam_fp", [](int f64, uptr segs, int n_segs, double scale, uptr state, uptr stream) {
+        return hpnn_adam_fp(f64, (const hpnn_adam_seg *)P(segs), n_segs, scale, (const hpnn_adam_state *)P(state),
+                            S(stream));
+    });
+    m.def("adam_host_init", [](uptr state, double lr, double beta1, double beta2, double eps, double decay) {
+        hpnn_adam_host_init((hpnn_adam_state *)P(state), lr, beta1, beta2, eps, decay);
+    });
+    m.def("adam_host_advance", [](uptr state) { hpnn_adam_host_advance((hpnn_adam_state *)P(state)); });
+    m.def("adam_host_update", [](int f64, uptr W, uptr M, uptr V, uptr G, int Sn, long gstride, long n, double scale,
+                                 uptr state) {
+        hpnn_adam_host_update(f64, P(W), P(M), P(V), P(G), Sn, gstride, n, scale, (const hpnn_adam_state *)P(state));
+    });
     m.def("mlp3_tile_grid", [](int Bp, int grid) { return hpnn_mlp3_tile_grid(Bp, grid); });
     m.def("mlp3_tile_trace", []() {
         std::vector<unsigned long long> v(1024 * 12);
@@ -614,6 +654,31 @@ PYBIND11_MODULE(_native, m) {
             check(hpnn_sgd_update_multi(L, n, lr, alpha, scale, momentum, S(stream)), "sgd_update_multi");
         },
         "layers: [(W32, V32, G, gstride, Wbf, Wt, Wf, S, N, K)] device addresses (0 = none)");
+    m.def(
+        "adam_update_multi",
+        [](py::list layers, float scale, uptr state, uptr stream) {
+            hpnn_adam_upd_layer L[HPNN_UPD_MAX];
+            const int n = (int)py::len(layers);
+            if (n < 1 || n > HPNN_UPD_MAX) throw std::runtime_error("adam_update_multi: 1..8 layers");
+            for (int i = 0; i < n; i++) {
+                py::tuple t = layers[i].cast<py::tuple>();
+                if (py::len(t) != 11) throw std::runtime_error("adam_update_multi: layer tuple of 11");
+                L[i].u.W32 = (float *)P(t[0].cast<uptr>());
+                L[i].u.V32 = (float *)P(t[1].cast<uptr>());
+                L[i].A32 = (float *)P(t[2].cast<uptr>());
+                L[i].u.G = (const float *)P(t[3].cast<uptr>());
+                L[i].u.gstride = t[4].cast<long>();
+                L[i].u.Wbf = P(t[5].cast<uptr>());
+                L[i].u.Wt = P(t[6].cast<uptr>());
+                L[i].u.Wf = P(t[7].cast<uptr>());
+                L[i].u.S = t[8].cast<int>();
+                L[i].u.N = t[9].cast<int>();
+                L[i].u.K = t[10].cast<int>();
+            }
+            check(hpnn_adam_update_multi(L, n, scale, (const hpnn_adam_state *)P(state), S(stream)),
+                  "adam_update_multi");
+        },
+        "layers: [(W32, V32, A32, G, gstride, Wbf, Wt, Wf, S, N, K)] device addresses (Wf: 0 = none)");
     /* ---- communication layer (include/libhpnn/comm.h) ---- */
     m.def("comm_available", []() { return hpnn_comm_available(); });
     m.def("comm_unique_id", []() {

@@ -16,7 +16,7 @@ _LIB = None
 _LIBC = None
 
 NN_TYPE = {"ANN": 0, "LNN": 1, "SNN": 2}
-NN_TRAIN = {"BP": 0, "BPM": 1, "CG": 2, "SPLX": 3}
+NN_TRAIN = {"BP": 0, "BPM": 1, "CG": 2, "SPLX": 3, "ADAM": 4}
 NN_MODE = {"online": 0, "batched": 1}
 NN_DTYPE = {"f64": 0, "f32": 1, "bf16": 2}
 NN_DEVICE = {"auto": 0, "cpu": 1, "gpu": 2}
@@ -63,6 +63,9 @@ def lib():
             "nn_set_batch": (None, [vp, u]), "nn_set_epochs": (None, [vp, u]),
             "nn_set_learning_rate": (None, [vp, d]), "nn_set_momentum": (None, [vp, d]),
             "nn_set_seed": (None, [vp, u]), "nn_return_seed": (u, [vp]),
+            "nn_set_train": (None, [vp, i]), "nn_return_batch": (u, [vp]),
+            "nn_set_adam": (None, [vp, d, d, d, d]),
+            "nn_get_adam": (None, [vp, ctypes.POINTER(d), ctypes.POINTER(d), ctypes.POINTER(d), ctypes.POINTER(d)]),
             "nn_return_last_pass": (u, []), "nn_return_last_total": (u, []),
             "nn_return_version": (cp, []), "nn_return_type": (i, [vp]), "nn_return_train": (i, [vp]),
             "nn_dump_state": (i, [vp, cp]), "nn_load_state": (i, [vp, cp]), "nn_return_epochs_done": (u, [vp]),
@@ -119,7 +122,7 @@ class Network:
 
     # configuration
     def set(self, mode=None, dtype=None, device=None, batch=None, epochs=None, lr=None, momentum=None, seed=None,
-            shuffle=None, validate=None, keep_best=None, patience=None):
+            shuffle=None, validate=None, keep_best=None, patience=None, adam=None):
         if mode is not None:
             self.L.nn_set_mode(self.ptr, NN_MODE[mode])
         if dtype is not None:
@@ -144,7 +147,21 @@ class Network:
             self.L.nn_set_keep_best(self.ptr, NN_KEEP_BEST[keep_best or "off"])
         if patience is not None:  # P: stop after P validation passes without improvement (0 = never)
             self.L.nn_set_patience(self.ptr, int(patience))
+        if adam is not None:  # dict(beta1=, beta2=, epsilon=, decay=) of [train] ADAM; a missing key keeps its value
+            cur = self.adam
+            unknown = set(adam) - set(cur)
+            if unknown:
+                raise ValueError(f"adam: unknown keys {sorted(unknown)} (beta1, beta2, epsilon, decay)")
+            cur.update({k: float(v) for k, v in adam.items()})
+            self.L.nn_set_adam(self.ptr, cur["beta1"], cur["beta2"], cur["epsilon"], cur["decay"])
         return self
+
+    @property
+    def adam(self):
+        """the [train] ADAM coefficients a training call would use: beta1, beta2, epsilon, decay"""
+        v = [ctypes.c_double() for _ in range(4)]
+        self.L.nn_get_adam(self.ptr, *[ctypes.byref(x) for x in v])
+        return dict(zip(("beta1", "beta2", "epsilon", "decay"), (x.value for x in v)))
 
     @property
     def keep_best(self):

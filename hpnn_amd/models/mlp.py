@@ -6,6 +6,7 @@ Math (reference SURVEY 2.4; ann.c / snn.c):
   ANN output  o = f(z),                             delta_L = (t - o) f'(o)
   hidden      delta_l = (W_{l+1}^T delta_{l+1}) * f'(h_l),  f'(y) = -0.5 (y^2 - 1)
   update      BP : W += lr * G ;  BPM: dW += lr * G; W += dW; dW *= alpha
+              Adam (optimizer="adam"): include/libhpnn/adam.h on W32 / V32 (= m) / A32 (= v)
   with G = mean over the minibatch of delta_l (x) h_{l-1} (batched mode, see
   csrc/cpu/cpu_batched.cpp for the FP64 oracle of exactly these semantics).
 
@@ -78,10 +79,14 @@ class MLP:
     batch: per-step (per-GPU) minibatch (padded by the plan: to 128, 256 on the tile path).
     fused: None / True = the fastest structure the plan finds (True: error if none),
     False = per-layer kernels, or one of "t", "x", "mid", "w" (bplan.h).
+    optimizer: "sgd" (BP, or BPM with momentum=True) | "adam" with lr, betas, eps, decay (AdamW when
+    decay > 0): the plan then keeps the moments V32 (first) and A32 (second) and the state
+    `adam_state` ([11] float64, ops.read_adam_state), and train_step ignores its lr / alpha.
     """
 
     def __init__(self, sizes, net_type="SNN", batch=256, device="cuda", momentum=False, weights=None, seed=10958,
-                 init="reference", splits=None, fused=None, mid_grid=512):
+                 init="reference", splits=None, fused=None, mid_grid=512, optimizer="sgd", lr=0.001,
+                 betas=(0.9, 0.999), eps=1e-8, decay=0.0):
         self.sizes = list(sizes)
         self.L = len(sizes) - 1
         self.type = TYPES[net_type] if isinstance(net_type, str) else int(net_type)
@@ -89,11 +94,15 @@ class MLP:
         self.device = torch.device(device)
         self.batch = batch
         self.momentum = momentum
+        if optimizer not in ("sgd", "adam"):
+            raise ValueError(f"optimizer {optimizer!r} (sgd | adam)")
+        self.adam = optimizer == "adam"
+        adam_cfg = (float(lr), float(betas[0]), float(betas[1]), float(eps), float(decay)) if self.adam else None
         on_gpu = self.device.type == "cuda"
         req = -1 if fused is None or fused is True else (0 if fused is False else ord({"mid": "m"}.get(fused, fused)))
         try:
             self.plan = native().BPlan(self.sizes, self.type, int(batch), bool(momentum), req, list(splits or []),
-                                       int(mid_grid), on_gpu)
+                                       int(mid_grid), on_gpu, adam_cfg)
         except ValueError as e:
             raise ValueError(f"fused={fused!r}: {e}") from None
         cfg = self.plan.config()
@@ -115,6 +124,11 @@ class MLP:
         b = self.buf
         self.W32 = [b[("W32", l)] for l in range(self.L)]
         self.V32 = [b.get(("V32", l)) for l in range(self.L)]
+        self.A32 = [b.get(("A32", l)) for l in range(self.L)]
+        self.adam_state = None
+        if self.adam:  # the plan's "adam" buffer is the hpnn_adam_state itself
+            self.adam_state = b[("adam", -1)].view(torch.float64)
+            self.adam_state.copy_(ops.adam_state(*adam_cfg))
         self.Wb = [b[("Wb", l)] for l in range(self.L)]
         self.Wt = [b[("Wt", l)] for l in range(self.L)]
         self.slab = [b[("slab", l)] for l in range(self.L)]
@@ -347,6 +361,9 @@ class MLP:
             ops.reduce_slabs(self.slab[l], self.G[l])
 
     def update_layer(self, l, lr, alpha, scale, from_G=False):
+        if self.adam:
+            raise RuntimeError("update_layer: Adam advances once per step and updates every layer in one launch "
+                               "(train_step / update_all)")
         if self._gpu:
             self.plan.update_layer(l, float(lr), float(alpha), float(scale), bool(from_G), _stream())
             return
@@ -359,8 +376,18 @@ class MLP:
         if self._gpu:
             self.plan.update_flat(self.grad_flat.data_ptr(), float(lr), float(alpha), float(scale), _stream())
             return
+        if self.adam:
+            self._adam_update(scale, from_G=True)
+            return
         for l in range(self.L):
             self.update_layer(l, lr, alpha, scale, from_G=True)
+
+    def _adam_update(self, scale, from_G=False):
+        """CPU emulation of the plan's optimizer under Adam: the advance, then every layer"""
+        ops.adam_advance(self.adam_state)
+        ops.adam_update_multi([(self.W32[l], self.V32[l], self.A32[l], self.G[l] if from_G else self.slab[l],
+                                self.Wb[l], self.Wt[l], self.W0f if l == 0 else None) for l in range(self.L)],
+                              self.adam_state, scale)
 
     def front(self, X, labels=None, T=None, n_valid=None):
         """fused modes: X -> the deltas (+ the [G1 | G2] block slabs), one launch"""
@@ -404,7 +431,8 @@ class MLP:
         return self.plan.grads_slabs(*self._x(X), *self._tgt(labels, T), n_valid, _stream(), d, sel, alt)
 
     def train_step(self, X, labels=None, T=None, n_valid=None, lr=0.01, alpha=0.2):
-        """One minibatch fwd + bwd + update on the current stream (no host sync)."""
+        """One minibatch fwd + bwd + update on the current stream (no host sync).  Under Adam lr
+        and alpha are ignored: the step size is the state's lr."""
         n_valid = self.Bp if n_valid is None else int(n_valid)
         if self._gpu:
             self.plan.step(*self._x(X), *self._tgt(labels, T), n_valid, float(lr), float(alpha), _stream())
@@ -416,7 +444,10 @@ class MLP:
             if l > 0:
                 self.backward_layer(l)  # pre-update W_l^T, before layer l's step below
             self.grad_layer(l, X)
-            self.update_layer(l, lr, alpha, scale)
+            if not self.adam:
+                self.update_layer(l, lr, alpha, scale)
+        if self.adam:
+            self._adam_update(scale)
 
     def predict(self, X, n_valid=None):
         """network outputs [n_valid, n_out] (fp32)."""
@@ -488,7 +519,8 @@ class MLP:
 
     # ------------------------------------------------------------------ keep the best pass
     def _masters(self):
-        return [t for l in range(self.L) for t in (self.W32[l], self.V32[l]) if t is not None]
+        m = [t for l in range(self.L) for t in (self.W32[l], self.V32[l], self.A32[l]) if t is not None]
+        return m + ([self.adam_state.view(torch.float32)] if self.adam else [])
 
     def keep_best(self, metric="loss", patience=0):
         """allocate the best state and the snapshot of the FP32 masters (and the momentum) for

@@ -50,13 +50,58 @@ def deltas(weights, hs, T, net_type):
     return d
 
 
-def batched_step(weights, X, T, net_type, lr, momentum=None, alpha=0.2):
+def adam_new_state(lr=0.001, beta1=0.9, beta2=0.999, eps=1e-8, decay=0.0):
+    """the state of adam_step: the coefficients, t = 0 and the running products p1 = p2 = 1"""
+    return {"lr": float(lr), "beta1": float(beta1), "beta2": float(beta2), "eps": float(eps), "decay": float(decay),
+            "t": 0, "p1": 1.0, "p2": 1.0}
+
+
+def adam_step(W, M, V, G, state, advance=True):
+    """One Adam / AdamW step of include/libhpnn/adam.h in place on the tensors (or lists of
+    tensors) W, M (first moment), V (second moment) of one dtype (float64 / float32), G the
+    ascent direction the project's BP adds to W: torch.optim.Adam / AdamW with maximize=True.
+    Written independently of the C form: the state advances first (t += 1, p1 *= beta1,
+    p2 *= beta2, unless advance=False: the caller did), then with c1 = lr / (1 - p1),
+    s2 = sqrt(1 - p2) rounded to the tensors' dtype
+        m = beta1 m + (1 - beta1) g,  v = beta2 v + ((1 - beta2) g) g,
+        w = w - lr decay w  (decay != 0),  w = w + c1 (m / (sqrt(v) / s2 + eps))."""
+    import math
+    if advance:
+        state["t"] += 1
+        state["p1"] *= state["beta1"]
+        state["p2"] *= state["beta2"]
+    c1 = state["lr"] / (1.0 - state["p1"])
+    s2 = math.sqrt(1.0 - state["p2"])
+    wd = state["lr"] * state["decay"]
+    many = isinstance(W, (list, tuple))
+    for w, m, v, g in zip(*((W, M, V, G) if many else ([W], [M], [V], [G]))):
+        dt = w.dtype
+        c = lambda x: torch.tensor(x, dtype=torch.float64).to(dt)  # noqa: E731  (one rounding to T)
+        g = g.to(dt)
+        m.copy_(c(state["beta1"]) * m + c(1.0 - state["beta1"]) * g)
+        v.copy_(c(state["beta2"]) * v + (c(1.0 - state["beta2"]) * g) * g)
+        if state["decay"] != 0.0:
+            w.copy_(w - c(wd) * w)
+        # a full tensor as the divisor: PyTorch turns a division by a scalar into a product with its
+        # reciprocal, which is another rounding than the rule's
+        # and the square root through FP64 (correctly rounded to T; PyTorch's vectorised FP32 sqrt
+        # is not on every CPU)
+        root = torch.sqrt(v.double()).to(dt)
+        w.copy_(w + c(c1) * (m / (root / torch.full_like(v, s2) + c(state["eps"]))))
+
+
+def batched_step(weights, X, T, net_type, lr, momentum=None, alpha=0.2, adam=None):
     """In-place minibatch step; returns the mean loss before the update.
-    momentum: list of dW tensors (BPM) or None (BP)."""
+    momentum: list of dW tensors (BPM) or None (BP).  adam: (M, V, state) -- lists of moment
+    tensors and an adam_new_state dict -- selects adam_step (lr, alpha are then unused)."""
     hs = forward(weights, X, net_type)
     loss = loss_per_sample(hs[-1], T, net_type).mean()
     d = deltas(weights, hs, T, net_type)
     B = X.shape[0]
+    if adam is not None:
+        G = [d[l].t() @ (X if l == 0 else hs[l - 1]) / B for l in range(len(weights))]
+        adam_step(weights, adam[0], adam[1], G, adam[2])
+        return loss
     for l, W in enumerate(weights):
         hin = X if l == 0 else hs[l - 1]
         G = d[l].t() @ hin / B

@@ -1114,3 +1114,144 @@ def _cpu_mlp3_mid(H1, W1, W1t, W2, W2t, D1, gslab, n_out, net_type, labels, T, t
     gslab[0, :G1.numel()] = G1.reshape(-1)
     gslab[0, G1.numel():] = G2.reshape(-1)
     return D1
+
+
+# --------------------------------------------------------------------------- [train] ADAM
+_ADAM_D = ("lr", "beta1", "beta2", "eps", "decay", "t", "p1", "p2", "c1", "s2", "wd")  # words of hpnn_adam_state
+
+
+def adam_state(lr=0.001, beta1=0.9, beta2=0.999, eps=1e-8, decay=0.0, device="cpu"):
+    """a fresh hpnn_adam_state (include/libhpnn/adam.h) as [11] float64: lr, beta1, beta2, eps,
+    decay, t (a uint64 word, 0), p1 = p2 = 1, then c1, s2, wd as the last advance derived them"""
+    if not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0 and eps > 0.0 and decay >= 0.0):
+        raise ValueError("adam_state: 0 <= beta < 1, eps > 0, decay >= 0")
+    st = torch.zeros(11, dtype=torch.float64)
+    native().adam_host_init(st.data_ptr(), float(lr), float(beta1), float(beta2), float(eps), float(decay))
+    return st.to(device)
+
+
+def read_adam_state(state):
+    """the Adam state as a dict (synchronises); t is an int"""
+    s = state.cpu()
+    out = {k: float(s[i]) for i, k in enumerate(_ADAM_D)}
+    out["t"] = int(s[5:6].view(torch.int64)[0])
+    return out
+
+
+def write_adam_state(state, **kw):
+    """set fields of an Adam state (names of read_adam_state); returns the state"""
+    s = state.cpu().clone()
+    for k, v in kw.items():
+        if k == "t":
+            s[5:6].view(torch.int64)[0] = int(v)
+        else:
+            s[_ADAM_D.index(k)] = float(v)
+    state.copy_(s)
+    return state
+
+
+def adam_advance(state):
+    """t += 1, p1 *= beta1, p2 *= beta2, then c1 = lr / (1 - p1), s2 = sqrt(1 - p2), wd = lr decay:
+    one capturable one-thread launch (csrc/gpu/kernels_adam.hip); CPU tensors: the host form"""
+    if _cpu(state):
+        native().adam_host_advance(state.data_ptr())
+        return state
+    _cg_rc(native().adam_advance(state.data_ptr(), _stream()), "adam_advance")
+    return state
+
+
+class AdamTable:
+    """the segment table of adam_update_fp: one segment per layer, a dict of flat (element stride
+    1) tensors w, m, v of one dtype (float64 / float32) with n elements each and slab: [S, n] with
+    any row stride >= n.  At most 16 segments.  Device tensors: uploaded once (a [n, 8] int64
+    device tensor; the table keeps the tensors alive)."""
+
+    def __init__(self, segs):
+        self.segs = [dict(s) for s in segs]
+        if not 1 <= len(self.segs) <= 16:
+            raise ValueError("AdamTable: 1..16 segments")
+        w0 = self.segs[0]["w"]
+        self.dtype, self.device = w0.dtype, w0.device
+        if self.dtype not in (torch.float64, torch.float32):
+            raise ValueError("AdamTable: float64 or float32 tensors")
+        self.f64 = int(self.dtype == torch.float64)
+        rows = []
+        for s in self.segs:
+            n, slab = s["w"].numel(), s["slab"]
+            for k in ("w", "m", "v", "slab"):
+                t = s[k]
+                if t.dtype != self.dtype or t.device != self.device or t.stride(-1) != 1:
+                    raise ValueError("AdamTable: one dtype, one device, element stride 1")
+                if (k == "slab" and (t.dim() != 2 or t.shape[1] != n)) or (k != "slab" and t.numel() != n):
+                    raise ValueError("AdamTable: every tensor of a segment has its n elements")
+            if n == 0 or slab.shape[0] < 1 or (slab.shape[0] > 1 and slab.stride(0) < n):
+                raise ValueError("AdamTable: n >= 1, S >= 1, slab row stride >= n")
+            rows.append((_ptr(s["w"]), _ptr(s["m"]), _ptr(s["v"]), _ptr(slab), slab.shape[0],
+                         slab.stride(0) if slab.shape[0] > 1 else n, n))
+        self.dev = None
+        if self.device.type != "cpu":
+            self.dev = torch.zeros(len(rows), 8, dtype=torch.int64, device=self.device)
+            rc = native().adam_table(self.f64, self.dev.data_ptr(), rows, _stream())
+            if rc:
+                raise ValueError(f"adam_table refused the segments (rc={rc})")
+        self.rows = rows
+
+    def __len__(self):
+        return len(self.segs)
+
+
+def adam_update_fp(table, state, scale=1.0):
+    """per segment g = (slab[0] + ... + slab[S-1]) * scale in slab order, then the Adam rule of
+    include/libhpnn/adam.h on w, m, v in the tensors' dtype with the coefficients the last
+    adam_advance left in the state, read when the launch runs: one capturable launch for the whole
+    table (csrc/gpu/kernels_adam.hip).  CPU tensors: the host entry point."""
+    if table.dev is None:
+        for r in table.rows:
+            native().adam_host_update(table.f64, r[0], r[1], r[2], r[3], r[4], r[5], r[6], float(scale),
+                                      state.data_ptr())
+        return
+    _cg_rc(native().adam_fp(table.f64, table.dev.data_ptr(), len(table), float(scale), state.data_ptr(), _stream()),
+           "adam_update_fp")
+
+
+def adam_slab_sum(G):
+    """the slab sum of adam_update_multi in the kernel's one fixed order (kernels_adam.hip): p_w =
+    the slabs w, w + 8, ... added in that order to 0, then ((p_0 + p_1) + ...) + p_7; FP32"""
+    if G.dim() == 2:
+        G = G.unsqueeze(0)
+    parts = []
+    for w in range(8):
+        p = torch.zeros_like(G[0])
+        for s in range(w, G.shape[0], 8):
+            p = p + G[s]
+        parts.append(p)
+    g = parts[0]
+    for w in range(1, 8):
+        g = g + parts[w]
+    return g
+
+
+def adam_update_multi(layers, state, scale=1.0):
+    """All layers' Adam steps in one launch (the BF16 plan's update, csrc/gpu/kernels_adam.hip).
+    layers: list of (W32, V32, A32, G, Wbf, Wt, Wf) with the FP32 masters W32, first moment V32 and
+    second moment A32 [N, K], G [S, N, K] (or a strided view) or [N, K]; Wf may be None.  The
+    coefficients are those the last adam_advance left in the state, read when the launch runs.
+    CPU tensors: the slabs summed in the kernel's order, then the host entry point of
+    include/libhpnn/adam.h and the BF16 copies of the emulation."""
+    if _cpu(layers[0][0]):
+        for W32, V32, A32, G, Wbf, Wt, Wf in layers:
+            g = adam_slab_sum(G.float()).contiguous()
+            if not (W32.is_contiguous() and V32.is_contiguous() and A32.is_contiguous()):
+                raise ValueError("adam_update_multi: contiguous W32, V32, A32")
+            native().adam_host_update(0, W32.data_ptr(), V32.data_ptr(), A32.data_ptr(), g.data_ptr(), 1, 0,
+                                      W32.numel(), float(scale), state.data_ptr())
+            cast_weights(W32, Wbf, Wt, Wf)
+        return
+    desc = []
+    for W32, V32, A32, G, Wbf, Wt, Wf in layers:
+        N, K = W32.shape
+        S = G.shape[0] if G.dim() == 3 else 1
+        gstride = G.stride(0) if G.dim() == 3 else 0
+        desc.append((W32.data_ptr(), V32.data_ptr(), A32.data_ptr(), G.data_ptr(), gstride, Wbf.data_ptr(),
+                     Wt.data_ptr(), _ptr(Wf), S, N, K))
+    native().adam_update_multi(desc, float(scale), state.data_ptr(), _stream())

@@ -48,6 +48,9 @@ class DataParallel:
     BF16RS_MIN_BYTES = 4 << 20
 
     def __init__(self, model, group=None, bucket_bytes=256 * 1024, comm="auto", grad_comm="auto"):
+        if getattr(model, "adam", False):
+            raise ValueError("DataParallel: optimizer='adam' trains on one device only (its moments and step "
+                             "count live beside one device's masters); use one GPU or optimizer='sgd'")
         self.m = model
         self.group = group
         self.active = dist.is_initialized()

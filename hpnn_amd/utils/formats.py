@@ -73,7 +73,7 @@ def read_conf(path):
     out = {}
     with open(path) as f:
         for ln in f:
-            m = re.match(r"\s*\[([a-z_]+)[^\]]*\]\s*(.*)", ln)
+            m = re.match(r"\s*\[([a-z_]+[12]?)[^\]]*\]\s*(.*)", ln)
             if not m:
                 continue
             k, v = m.group(1), m.group(2).split("#")[0].strip()

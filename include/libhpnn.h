@@ -12,6 +12,7 @@
 #define LIBHPNN_H
 #include <libhpnn/common.h>
 #include <libhpnn/cg.h>
+#include <libhpnn/adam.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -56,6 +57,8 @@ typedef enum {
                         * batched training, [dtype] f64 | f32 (<libhpnn/cg.h>; the reference
                         * parses it and implements nothing) */
     NN_TRAIN_SPLX = 3, /* parsed, not implemented (as in the reference)  */
+    NN_TRAIN_ADAM = 4, /* extension: Adam / AdamW on one device in batched training, every [dtype]
+                        * (<libhpnn/adam.h>) */
     NN_TRAIN_UKN = -1,
 } nn_train;
 
@@ -72,6 +75,8 @@ typedef enum {
  * reference (cuda_ann.cu:2094, cuda_snn.cu:1918, snn.c:799) */
 #define GPU_LEARN_RATE 0.01
 #define BPM_MOMENTUM 0.2
+/* [train] ADAM with [lr] unset */
+#define ADAM_LEARN_RATE 0.001
 
 /* ---- extensions: execution mode and precision ---- */
 typedef enum {
@@ -153,6 +158,8 @@ typedef struct {
      *    (nn_get_cg_history) -- */
     UINT n_cg_history;
     void *cg_history;
+    /* -- [train] ADAM: [beta1], [beta2], [epsilon], [decay]; a NaN: not set (0.9, 0.999, 1e-8, 0) -- */
+    DOUBLE beta1, beta2, epsilon, decay;
 } nn_def;
 
 #define _NN(a, b) nn_##a##_##b
@@ -325,6 +332,15 @@ BOOL _NN(get, best)(nn_def *conf, UINT *epoch, DOUBLE *loss, UINT *correct, UINT
  * "CG: epoch E loss=L beta=B alpha=A trial=j" per iteration; nn_get_cg_history returns the
  * records of the last call (owned by conf; *n = their number, NULL when there is none) */
 const hpnn_cg_record *_NN(get, cg_history)(nn_def *conf, UINT *n);
+/* [train] ADAM (batched mode, one device): W += c1 m / (sqrt(v) / s2 + eps) with the moments
+ * m, v of the mean gradient and the bias corrections of <libhpnn/adam.h>; decay > 0 is the
+ * decoupled weight decay of AdamW.  [lr] defaults to ADAM_LEARN_RATE, [momentum] is unused.  A NaN
+ * argument of nn_set_adam unsets that key (its default); nn_get_adam returns the values a
+ * training call would use (any pointer may be NULL).  0 <= beta < 1, epsilon > 0 and
+ * decay >= 0 are checked by nn_train_kernel.  The moments and the step count persist through
+ * the state file (nn_dump_state / nn_load_state), not across two calls in one process */
+void _NN(set, adam)(nn_def *conf, DOUBLE beta1, DOUBLE beta2, DOUBLE epsilon, DOUBLE decay);
+void _NN(get, adam)(nn_def *conf, DOUBLE *beta1, DOUBLE *beta2, DOUBLE *epsilon, DOUBLE *decay);
 /* the [shuffle] epoch permutation (libhpnn/shuffle.h): out[i] = index, in the order drawn once
  * from [seed], of the sample at position i of epoch `epoch` (epochs completed before it) */
 void hpnn_epoch_perm(UINT n, UINT seed, UINT epoch, UINT *out);

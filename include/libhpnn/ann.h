@@ -35,6 +35,11 @@ typedef struct {
     UINT max_index;    /* max(n_in, n_out, h_i)                */
     DOUBLE *tmp_cpu;   /* scratch, max_index                   */
     void *gpu;         /* device state (hpnn_gpu_model*)        */
+    /* [train] ADAM: dw is the first moment; the second moment (NULL if none), the steps taken
+     * and the running products beta1^t, beta2^t */
+    DOUBLE **dv;
+    UINT64 adam_t;
+    DOUBLE adam_p1, adam_p2;
 } kernel_ann;
 
 /* allocation / I/O (reference ann.c:113-879) */
@@ -64,6 +69,10 @@ DOUBLE hpnn_cpu_train_step(kernel_ann *kernel, nn_type type, const DOUBLE *train
 BOOL ann_momentum_init(kernel_ann *kernel);
 void ann_raz_momentum(kernel_ann *kernel);
 void ann_momentum_free(kernel_ann *kernel);
+/* [train] ADAM: allocates dw and dv (zeroed) where missing; free releases dv and resets the step
+ * count (dw is the momentum's) */
+BOOL ann_adam_init(kernel_ann *kernel);
+void ann_adam_free(kernel_ann *kernel);
 
 /* per-sample convergence driver (reference ann.c:2281-2467, snn.c:1417-1595)
  * returns the last dEp; *n_iter and *ok report the loop outcome */
