@@ -144,8 +144,9 @@ __device__ __forceinline__ void output_snn_onehot(const f32x4 (&z)[2], int lab, 
         }
         if constexpr (STORE) *(bf16x4 *)wr_ptr<R>(imgD3, lo, r0, ot * 16) = dv;
     }
-    /* lanes that do not hold the label contribute 0 */
-    float l = (z_lab > -INFINITY && valid) ? t_hi * __logf(o_lab + TINY) : 0.f;
+    /* lanes that do not hold the label contribute 0; so does an output that underflowed to
+     * 0 (the rule of output_layer and of hpnn_output_delta: a term counts only if o > 0) */
+    float l = (z_lab > -INFINITY && valid && o_lab > 0.f) ? t_hi * __logf(o_lab + TINY) : 0.f;
     l = rows_sum(l);
     const unsigned int hit = (valid && z_lab > -INFINITY && z_lab >= zmax) ? 1u : 0u;
     if (valid) {

@@ -393,10 +393,14 @@ def mlp3_eval(Xg, K0, W0, W0f, W1, W2, n_out, net_type, labels=None, T=None, t_h
         H2 = bipolar(H1.float() @ W1.float().t()).bfloat16()
         Z = H2.float() @ W2.float().t()
         D3 = torch.empty(Bp, W2.shape[0], dtype=torch.bfloat16)
-        _cpu_output_delta(Z, n_out, net_type, D3, labels, T, t_hi, t_lo, n_valid, None, loss_acc, correct)
-        if guess is not None:
+        _cpu_output_delta(Z, n_out, net_type, D3, labels, T, t_hi, t_lo, n_valid, None, loss_acc, correct,
+                          front=True)
+        if guess is not None:  # the lowest index of the largest logit
+            z = Z[:n_valid, :n_out]
+            col = torch.arange(n_out).expand_as(z)
+            low = torch.where(z == z.max(1, keepdim=True).values, col, torch.full_like(col, n_out)).min(1).values
             guess.fill_(-1)
-            guess[:n_valid] = Z[:n_valid, :n_out].argmax(1).to(torch.int32)
+            guess[:n_valid] = low.to(torch.int32)
         return guess
     native().mlp3_eval(Xg.data_ptr(), int(u8), float(xscale), K0, W0f.data_ptr(), W1.data_ptr(), W2.data_ptr(),
                        _ptr(labels), _ptr(T), T.stride(0) if T is not None else 0, float(t_hi), float(t_lo),
@@ -768,7 +772,8 @@ def wide2_front(X, W0, W1, W1t, H0, D2, D1, ws, n_out, net_type, labels=None, T=
         h = bipolar(X[:, :K0].float() @ W0.float().t()).bfloat16()
         H0.copy_(h)
         Z = h.float() @ W1.float().t()
-        _cpu_output_delta(Z, n_out, net_type, D2, labels, T, t_hi, t_lo, n_valid, None, loss_acc, correct)
+        _cpu_output_delta(Z, n_out, net_type, D2, labels, T, t_hi, t_lo, n_valid, None, loss_acc, correct,
+                          front=True)
         D1.copy_(((D2.float() @ W1.float()) * dbipolar(h.float())).bfloat16())
         return D1
     native().wide2_front(X.data_ptr(), X.stride(0), K0, W0.data_ptr(), W1.data_ptr(), W1t.data_ptr(), _ptr(labels),
@@ -1078,7 +1083,11 @@ def ref_output(Z, n_out, net_type, T):
     return o, d, loss
 
 
-def _cpu_output_delta(Z, n_out, net_type, D, labels, T, t_hi, t_lo, n_valid, O, loss_acc, correct):
+def _cpu_output_delta(Z, n_out, net_type, D, labels, T, t_hi, t_lo, n_valid, O, loss_acc, correct, front=False):
+    """front: the hit rule of the fused fronts (csrc/gpu/mlp3_common.h, kernels_mlp3.hip,
+    kernels_wide.hip): a row is a hit when the logit of its label -- dense targets: of its first
+    largest target -- is >= the row's largest logit, so a tie counts.  Otherwise the rule of
+    hpnn_output_delta: the argmax of the outputs is the argmax of the targets."""
     B = Z.shape[0]
     if T is None:
         T = torch.full((B, n_out), t_lo, dtype=torch.float32)
@@ -1090,7 +1099,13 @@ def _cpu_output_delta(Z, n_out, net_type, D, labels, T, t_hi, t_lo, n_valid, O, 
         O[:, :n_out] = o
     if loss_acc is not None:
         loss_acc += loss[:n_valid].sum()
-    if correct is not None:
+    if correct is not None and front:
+        Tv, z = T[:n_valid, :n_out].float(), Z[:n_valid, :n_out].float()
+        col = torch.arange(n_out).expand_as(Tv)
+        tcol = torch.where(Tv == Tv.max(1, keepdim=True).values, col, torch.full_like(col, n_out)).min(1).values
+        hits = (z.gather(1, tcol[:, None])[:, 0] >= z.max(1).values).sum().to(torch.int32)
+        correct.view(torch.int32).add_(hits)
+    elif correct is not None:
         hits = (o[:n_valid].argmax(1) == T[:n_valid, :n_out].argmax(1)).sum().to(torch.int32)
         correct.view(torch.int32).add_(hits)
     # (GPU kernels spread these over 64 slots of 16 floats; slot 0 is used here)
@@ -1105,7 +1120,7 @@ def _cpu_mlp3_mid(H1, W1, W1t, W2, W2t, D1, gslab, n_out, net_type, labels, T, t
     D1 = D1 if D1 is not None else torch.empty_like(H1)
     Z = (H2.float() @ W2.float().t())
     D3 = torch.zeros(Bp, W2.shape[0], dtype=torch.bfloat16)
-    _cpu_output_delta(Z, n_out, net_type, D3, labels, T, t_hi, t_lo, n_valid, None, loss_acc, correct)
+    _cpu_output_delta(Z, n_out, net_type, D3, labels, T, t_hi, t_lo, n_valid, None, loss_acc, correct, front=True)
     D2 = ((D3.float() @ W2.float()) * dbipolar(H2.float())).bfloat16()
     D1.copy_(((D2.float() @ W1.float()) * dbipolar(H1.float())).bfloat16())
     G1 = D2.float().t() @ H1.float()
