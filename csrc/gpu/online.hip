@@ -47,6 +47,19 @@ __device__ __forceinline__ void gst(double *p, size_t i, double v) { ((glb_d *)p
 __device__ __forceinline__ double act(double x) { return 2.0 / (1.0 + exp(-1.0 * x)) - 1.0; }
 __device__ __forceinline__ double dact(double y) { return -0.5 * (y * y - 1.0); }
 
+/* Ep - Ep' from two ROUNDED errors.  The SNN error ends in s * (-1 / N); left to the compiler, that
+ * product and this difference contract into fma(-s, 1 / N, Ep), which keeps the product unrounded
+ * and leaves Ep's own rounding error (1e-19) where the reference's dEp is exactly 0 on weights
+ * that did not move.  err_scale / err_drop keep the two roundings apart. */
+__device__ __forceinline__ double err_scale(double s, int type, int N) {
+#pragma clang fp contract(off)
+    return type == 2 ? s * (-1.0 / (double)N) : 0.5 * s;
+}
+__device__ __forceinline__ double err_drop(double Ep, double Epr) {
+#pragma clang fp contract(off)
+    return Ep - Epr;
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -111,7 +124,7 @@ __device__ double error_of(const hpnn_online_args &a, const double *o, double *r
         }
     }
     const double s = block_sum(part, red);
-    return a.type == 2 ? s * (-1.0 / (double)N) : 0.5 * s;
+    return err_scale(s, a.type, N);
 }
 
 template <bool LDS>
@@ -299,7 +312,7 @@ __global__ __launch_bounds__(NTH) void online_kernel(hpnn_online_args a) {
         }
         if (a.type == 2) softmax_out(v.h[nxt][L - 1], n_out, red);
         const double Epr = error_of(a, v.h[nxt][L - 1], red);
-        dEp = Ep - Epr;
+        dEp = err_drop(Ep, Epr);
         Ep = Epr;
         cur = nxt;
         int max_p, p_trg;
@@ -467,7 +480,7 @@ __device__ double c_error(const hpnn_online_args &a, P o, P t, double *red) {
         }
     }
     const double s = cblock_sum(part, red);
-    return a.type == 2 ? s * (-1.0 / (double)N) : 0.5 * s;
+    return err_scale(s, a.type, N);
 }
 
 template <class P>
@@ -670,7 +683,7 @@ __global__ __launch_bounds__(CNT) void online_coop_kernel(hpnn_online_args a) {
         }
         if (a.type == 2) c_softmax(h[nxt][L - 1], n_out, red);
         const double Epr = c_error(a, h[nxt][L - 1], tt, red);
-        dEp = Ep - Epr;
+        dEp = err_drop(Ep, Epr);
         Ep = Epr;
         cur = nxt;
         int max_p, p_trg;
@@ -746,7 +759,7 @@ extern "C" long hpnn_online_coop_xch_bytes(const hpnn_online_args *a, int grid) 
 
 /* n_slots > 1: the caller zeroes ctl once, before any slot is launched */
 extern "C" int hpnn_online_coop_launch(const hpnn_online_args *a, int grid, hipStream_t stream) {
-    if (grid < 1 || grid > COOP_MAX_GRID || !a->xch || !a->ctl) return -1;
+    if (a->L < 1 || a->L > 16 || grid < 1 || grid > COOP_MAX_GRID || !a->xch || !a->ctl) return -1;
     long lds = a->n_in + a->N[a->L - 1];
     for (int l = 0; l < a->L; l++) lds += 3L * a->N[l];
     const unsigned bytes = (unsigned)(lds * 8);

@@ -595,6 +595,72 @@ PYBIND11_MODULE(_native, m) {
                                  uptr state) {
         hpnn_adam_host_update(f64, P(W), P(M), P(V), P(G), Sn, gstride, n, scale, (const hpnn_adam_state *)P(state));
     });
+    /* ---- online (batch-1) FP64 engine (csrc/gpu/online.hip), one launch ---- */
+    m.attr("ONLINE_CTL_BYTES") = (int)HPNN_ONLINE_CTL_BYTES;
+    /* the host-side sizing helpers only read L, n_in and N[] */
+    auto online_shape = [](const std::vector<int> &sizes) {
+        if (sizes.size() < 2) throw std::invalid_argument("online: at least two layer sizes");
+        hpnn_online_args a = {};
+        a.L = (int)sizes.size() - 1;
+        a.n_in = sizes[0];
+        for (int l = 0; l < a.L && l < 16; l++) a.M[l] = sizes[l], a.N[l] = sizes[l + 1];
+        return a;
+    };
+    m.def("online_vec_bytes", [online_shape](std::vector<int> sizes) {
+        if (sizes.size() > 17) throw std::invalid_argument("online_vec_bytes: at most 16 layers");
+        const hpnn_online_args a = online_shape(sizes);
+        return hpnn_online_vec_bytes(&a);
+    });
+    m.def("online_coop_grid", [online_shape](std::vector<int> sizes) {
+        const hpnn_online_args a = online_shape(sizes); /* L > 16: the helper answers 0 before reading N[] */
+        return hpnn_online_coop_grid(&a);
+    });
+    m.def("online_coop_grid_slots", [online_shape](std::vector<int> sizes, int n_slots, int per_device_cap) {
+        const hpnn_online_args a = online_shape(sizes);
+        return hpnn_online_coop_grid_slots(&a, n_slots, per_device_cap);
+    });
+    m.def("online_coop_xch_bytes", [online_shape](std::vector<int> sizes, int grid) {
+        if (sizes.size() > 17) throw std::invalid_argument("online_coop_xch_bytes: at most 16 layers");
+        const hpnn_online_args a = online_shape(sizes);
+        return hpnn_online_coop_xch_bytes(&a, grid);
+    });
+    m.def("online_coop_status", [](uptr ctl) {
+        hpnn_online_args a = {};
+        a.ctl = (unsigned int *)P(ctl);
+        return hpnn_online_coop_status(&a);
+    });
+    /* one sample through one launch of the named kernel: "lds" / "global" (online_kernel<true/false>)
+     * or "coop" (online_coop_kernel<false> on `grid` workgroups).  Returns the launcher's code
+     * unchanged: 0, -1 (L or grid out of range), -2 (the vectors do not fit in LDS), -5 (launch) */
+    m.def(
+        "online_sample",
+        [online_shape](std::vector<int> sizes, std::vector<uptr> W, std::vector<uptr> dW, uptr x, uptr t, uptr out,
+                       uptr result, uptr scratch, int type, int momentum, double lr, double alpha, double delta,
+                       int min_iter, int max_iter, int forward_only, const std::string &variant, int grid, uptr xch,
+                       uptr ctl, int n_slots, uptr stream) {
+            if (n_slots > 1) throw std::invalid_argument("online_sample: the device-spanning form is not bound");
+            hpnn_online_args a = online_shape(sizes);
+            if (W.size() != (size_t)a.L || dW.size() != (size_t)a.L)
+                throw std::invalid_argument("online_sample: one W and one dW pointer per layer");
+            for (int l = 0; l < a.L && l < 16; l++) a.W[l] = (double *)P(W[l]), a.dW[l] = (double *)P(dW[l]);
+            a.type = type, a.momentum = momentum;
+            a.lr = lr, a.alpha = alpha, a.delta = delta;
+            a.min_iter = min_iter, a.max_iter = max_iter;
+            a.x = (const double *)P(x), a.t = (const double *)P(t);
+            a.out = (double *)P(out), a.result = (double *)P(result), a.scratch = (double *)P(scratch);
+            a.forward_only = forward_only;
+            a.xch = (double *)P(xch), a.ctl = (unsigned int *)P(ctl);
+            a.dev_slot = 0, a.n_slots = 1;
+            if (variant == "coop") return hpnn_online_coop_launch(&a, grid, S(stream));
+            if (variant != "lds" && variant != "global")
+                throw std::invalid_argument("online_sample: variant is lds, global or coop");
+            a.use_lds = variant == "lds";
+            return hpnn_online_launch(&a, S(stream));
+        },
+        py::arg("sizes"), py::arg("W"), py::arg("dW"), py::arg("x"), py::arg("t"), py::arg("out"), py::arg("result"),
+        py::arg("scratch"), py::arg("type"), py::arg("momentum"), py::arg("lr"), py::arg("alpha"), py::arg("delta"),
+        py::arg("min_iter"), py::arg("max_iter"), py::arg("forward_only"), py::arg("variant"), py::arg("grid") = 0,
+        py::arg("xch") = 0, py::arg("ctl") = 0, py::arg("n_slots") = 1, py::arg("stream") = 0);
     m.def("mlp3_tile_grid", [](int Bp, int grid) { return hpnn_mlp3_tile_grid(Bp, grid); });
     m.def("mlp3_tile_trace", []() {
         std::vector<unsigned long long> v(1024 * 12);

@@ -1270,3 +1270,67 @@ def adam_update_multi(layers, state, scale=1.0):
         desc.append((W32.data_ptr(), V32.data_ptr(), A32.data_ptr(), G.data_ptr(), gstride, Wbf.data_ptr(),
                      Wt.data_ptr(), _ptr(Wf), S, N, K))
     native().adam_update_multi(desc, float(scale), state.data_ptr(), _stream())
+
+
+# --------------------------------------------------------------------------- online FP64 engine
+ONLINE_VARIANTS = ("lds", "global", "coop")
+
+
+def online_sizes(W):
+    """[n_in, N_0, ..] of a list of [N, M] weight tensors"""
+    return [int(W[0].shape[1])] + [int(w.shape[0]) for w in W]
+
+
+def online_coop_grid(sizes):
+    """the grid the engine gives the cooperative online kernel for this net (0: single workgroup)"""
+    return native().online_coop_grid([int(s) for s in sizes])
+
+
+def online_sample(W, dW, x, t, net_type, variant="lds", momentum=False, lr=0.0, alpha=0.0, delta=1e-6, min_iter=0,
+                  max_iter=0, forward_only=False, grid=None, check=True):
+    """One sample through ONE launch of an online kernel of csrc/gpu/online.hip: the reference's
+    "iterate this sample until it converges" loop on the device.  W / dW: lists of FP64 device
+    tensors [N, M], updated in place (dW: the momenta of BPM; read and written only when momentum).
+    variant: "lds" / "global" (the single-workgroup kernel with its vectors in LDS / in global
+    scratch) or "coop" (the cooperative kernel on `grid` workgroups; None: the engine's choice).
+    Launches on the current stream and synchronises.  Returns (out, dEp, init_err, iters, ok,
+    first_ok); forward_only: (out, None, init_err, None, None, None).  check=False returns the
+    launcher's code instead of raising when it refuses (then nothing was launched)."""
+    n = native()
+    sizes = online_sizes(W)
+    dev = x.device
+    for a, b, m in zip(W, dW, sizes):
+        if not (a.is_cuda and b.is_cuda and a.dtype == b.dtype == torch.float64 and a.is_contiguous()
+                and b.is_contiguous() and a.shape == b.shape and a.shape[1] == m):
+            raise ValueError("online_sample: W / dW are contiguous FP64 device tensors [N, M], chained")
+    if not (x.dtype == t.dtype == torch.float64 and x.numel() == sizes[0] and t.numel() == sizes[-1]):
+        raise ValueError("online_sample: x [n_in], t [n_out] FP64")
+    if variant not in ONLINE_VARIANTS:
+        raise ValueError("online_sample: variant is one of %s" % (ONLINE_VARIANTS,))
+    x, t = x.contiguous(), t.contiguous()
+    out = torch.zeros(sizes[-1], dtype=torch.float64, device=dev)
+    result = torch.zeros(8, dtype=torch.float64, device=dev)
+    fits = len(W) <= 16
+    scratch = torch.zeros(max(n.online_vec_bytes(sizes) // 8, 1) if fits else 1, dtype=torch.float64, device=dev)
+    xch = ctl = None
+    if variant == "coop":
+        if grid is None:
+            grid = n.online_coop_grid(sizes)
+        xb = n.online_coop_xch_bytes(sizes, max(int(grid), 1)) if fits else 8
+        xch = torch.zeros(max(xb // 8, 1), dtype=torch.float64, device=dev)
+        ctl = torch.zeros(n.ONLINE_CTL_BYTES // 4, dtype=torch.int32, device=dev)
+    rc = n.online_sample(sizes, [w.data_ptr() for w in W], [v.data_ptr() for v in dW], x.data_ptr(), t.data_ptr(),
+                         out.data_ptr(), result.data_ptr(), scratch.data_ptr(), int(net_type), int(bool(momentum)),
+                         float(lr), float(alpha), float(delta), int(min_iter), int(max_iter), int(bool(forward_only)),
+                         variant, int(grid or 0), _ptr(xch), _ptr(ctl), 1, _stream())
+    torch.cuda.current_stream().synchronize()
+    if rc != 0:
+        if check:
+            raise RuntimeError("online_sample: the %s launcher refused (rc=%d)" % (variant, rc))
+        return rc
+    if variant == "coop" and n.online_coop_status(ctl.data_ptr()) != 0:
+        raise RuntimeError("online_sample: a grid barrier of the cooperative kernel timed out")
+    r = result.cpu()
+    if forward_only:
+        return out, None, float(r[1]), None, None, None
+    return out, float(r[0]), float(r[1]), int(r[2]), int(r[3]), int(r[4])
