@@ -57,6 +57,8 @@ $(BUILD)/%.o: %.hip $(HDRS) $(HIPSTAMP)
 $(BUILD)/csrc/gpu/kernels_cg.o: HIPFLAGS += -ffp-contract=off
 # the Adam rule (include/libhpnn/adam.h) likewise: the same roundings on both sides
 $(BUILD)/csrc/gpu/kernels_adam.o: HIPFLAGS += -ffp-contract=off
+# the learning-rate schedules (include/libhpnn/lrsched.h) and the scheduled step likewise
+$(BUILD)/csrc/gpu/kernels_lrsched.o: HIPFLAGS += -ffp-contract=off
 
 $(LIB): $(CORE_OBJ) $(HIP_OBJ)
 	@mkdir -p $(LIBDIR)

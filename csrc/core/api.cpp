@@ -61,6 +61,8 @@ extern "C" void _NN(init, conf)(nn_def *conf) {
     conf->lr = -1.0;
     conf->momentum = -1.0;
     conf->beta1 = conf->beta2 = conf->epsilon = conf->decay = NAN; /* not set */
+    conf->lr_schedule = NN_LR_NONE;
+    conf->lr_gamma = conf->lr_end = conf->lr_min = NAN; /* not set */
 }
 
 extern "C" void _NN(free, kernel)(nn_def *conf) {
@@ -82,6 +84,9 @@ extern "C" void _NN(deinit, conf)(nn_def *conf) {
     free(conf->cg_history);
     conf->cg_history = NULL;
     conf->n_cg_history = 0;
+    free(conf->lr_history);
+    conf->lr_history = NULL;
+    conf->n_lr_history = 0;
     conf->name = conf->f_kernel = conf->samples = conf->tests = NULL;
 }
 
@@ -181,6 +186,35 @@ extern "C" void _NN(get, adam)(nn_def *c, DOUBLE *beta1, DOUBLE *beta2, DOUBLE *
     if (beta2) *beta2 = c->beta2 == c->beta2 ? c->beta2 : HPNN_ADAM_BETA2;
     if (epsilon) *epsilon = c->epsilon == c->epsilon ? c->epsilon : HPNN_ADAM_EPS;
     if (decay) *decay = c->decay == c->decay ? c->decay : 0.0;
+}
+extern "C" void _NN(set, lr_schedule)(nn_def *c, nn_lr_schedule kind, DOUBLE gamma, UINT period, UINT span,
+                                      DOUBLE lr_end, DOUBLE lr_min, UINT patience, UINT warmup) {
+    if (!c) return;
+    c->lr_schedule = (kind >= NN_LR_CONSTANT && kind <= NN_LR_PLATEAU) ? kind : NN_LR_NONE;
+    c->lr_gamma = gamma;
+    c->lr_period = period;
+    c->lr_span = span;
+    c->lr_end = lr_end;
+    c->lr_min = lr_min;
+    c->lr_patience = patience;
+    c->warmup = warmup;
+}
+extern "C" void _NN(get, lr_schedule)(nn_def *c, nn_lr_schedule *kind, DOUBLE *gamma, UINT *period, UINT *span,
+                                      DOUBLE *lr_end, DOUBLE *lr_min, UINT *patience, UINT *warmup) {
+    if (!c) return;
+    /* [warmup] alone schedules a constant rate */
+    if (kind) *kind = (c->lr_schedule == NN_LR_NONE && c->warmup) ? NN_LR_CONSTANT : c->lr_schedule;
+    if (gamma) *gamma = c->lr_gamma == c->lr_gamma ? c->lr_gamma : HPNN_LR_GAMMA;
+    if (period) *period = c->lr_period ? c->lr_period : HPNN_LR_PERIOD;
+    if (span) *span = c->lr_span;
+    if (lr_end) *lr_end = c->lr_end == c->lr_end ? c->lr_end : 0.0;
+    if (lr_min) *lr_min = c->lr_min == c->lr_min ? c->lr_min : 0.0;
+    if (patience) *patience = c->lr_patience ? c->lr_patience : HPNN_LR_PATIENCE;
+    if (warmup) *warmup = c->warmup;
+}
+extern "C" const DOUBLE *_NN(get, lr_history)(nn_def *c, UINT *n) {
+    if (n) *n = c && c->lr_history ? c->n_lr_history : 0;
+    return c ? c->lr_history : NULL;
 }
 extern "C" UINT _NN(return, last_pass)(void) { return g_last_pass; }
 extern "C" UINT _NN(return, last_total)(void) { return g_last_total; }
@@ -328,6 +362,31 @@ extern "C" nn_def *_NN(load, conf)(const CHAR *filename) {
             std::string u = v;
             for (auto &ch : u) ch = (char)tolower(ch);
             conf->parallel = u == "tp" ? NN_PARALLEL_TP : NN_PARALLEL_DP;
+        } else if (is("lr_schedule")) {
+            std::string u = v;
+            for (auto &ch : u) ch = (char)tolower(ch);
+            if (u == "constant") conf->lr_schedule = NN_LR_CONSTANT;
+            else if (u == "step") conf->lr_schedule = NN_LR_STEP;
+            else if (u == "linear") conf->lr_schedule = NN_LR_LINEAR;
+            else if (u == "plateau") conf->lr_schedule = NN_LR_PLATEAU;
+            else CONF_FAIL("[lr_schedule] unknown: %s (constant | step | linear | plateau)\n", v.c_str());
+        } else if (is("lr_gamma") || is("lr_end") || is("lr_min")) {
+            /* checked before [lr]: the keys are matched by prefix */
+            char *end = NULL;
+            const DOUBLE x = strtod(v.c_str(), &end);
+            const bool gam = key[3] == 'g', fin = x - x == 0.0;
+            if (v.empty() || end == v.c_str() || !fin || (gam ? !(x > 0.0 && x <= 1.0) : key[3] == 'm' && x < 0.0))
+                CONF_FAIL("[%s] value: %s (%s)\n", key.c_str(), v.c_str(),
+                          gam ? "0 < gamma <= 1" : key[3] == 'm' ? ">= 0" : "a finite rate");
+            (gam ? conf->lr_gamma : key[3] == 'm' ? conf->lr_min : conf->lr_end) = x;
+        } else if (is("lr_period") || is("lr_span") || is("lr_patience") || is("warmup")) {
+            char *end = NULL;
+            const unsigned long x = strtoul(v.c_str(), &end, 10);
+            const bool wu = key[0] == 'w';
+            if (v.empty() || !isdigit((unsigned char)v[0]) || (!wu && x == 0) || x > 0xffffffffUL)
+                CONF_FAIL("[%s] value: %s (epochs%s)\n", key.c_str(), v.c_str(), wu ? ", >= 0" : ", >= 1");
+            (wu ? conf->warmup : key[4] == 'e' ? conf->lr_period : key[3] == 's' ? conf->lr_span : conf->lr_patience) =
+                (UINT)x;
         } else if (is("lr")) {
             conf->lr = strtod(v.c_str(), NULL);
         } else if (is("momentum")) {
@@ -412,6 +471,16 @@ extern "C" void _NN(dump, conf)(nn_def *conf, FILE *fp) {
     if (conf->beta2 == conf->beta2) _OUT(fp, "[beta2] %.17g\n", conf->beta2);
     if (conf->epsilon == conf->epsilon) _OUT(fp, "[epsilon] %.17g\n", conf->epsilon);
     if (conf->decay == conf->decay) _OUT(fp, "[decay] %.17g\n", conf->decay);
+    static const char *lrn[] = {"constant", "step", "linear", "plateau"};
+    if (conf->lr_schedule >= NN_LR_CONSTANT && conf->lr_schedule <= NN_LR_PLATEAU)
+        _OUT(fp, "[lr_schedule] %s\n", lrn[conf->lr_schedule]);
+    if (conf->lr_gamma == conf->lr_gamma) _OUT(fp, "[lr_gamma] %.17g\n", conf->lr_gamma);
+    if (conf->lr_period) _OUT(fp, "[lr_period] %u\n", conf->lr_period);
+    if (conf->lr_span) _OUT(fp, "[lr_span] %u\n", conf->lr_span);
+    if (conf->lr_end == conf->lr_end) _OUT(fp, "[lr_end] %.17g\n", conf->lr_end);
+    if (conf->lr_min == conf->lr_min) _OUT(fp, "[lr_min] %.17g\n", conf->lr_min);
+    if (conf->lr_patience) _OUT(fp, "[lr_patience] %u\n", conf->lr_patience);
+    if (conf->warmup) _OUT(fp, "[warmup] %u\n", conf->warmup);
 }
 
 /* ------------------------------------------------------------------ */
@@ -623,6 +692,23 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
         }
         if (conf->momentum >= 0) NN_OUT(stdout, "[train] ADAM: [momentum] is unused (the moments decay with [beta1], [beta2])\n");
     }
+    /* [lr_schedule]: the keys as a training call uses them; the state itself is filled below, once
+     * the rate and the progress are known */
+    nn_lr_schedule lr_kind = NN_LR_NONE;
+    DOUBLE lr_gamma = 0.0, lr_end = 0.0, lr_min = 0.0;
+    UINT lr_period = 0, lr_span = 0, lr_patience = 0, lr_warmup = 0;
+    _NN(get, lr_schedule)(conf, &lr_kind, &lr_gamma, &lr_period, &lr_span, &lr_end, &lr_min, &lr_patience, &lr_warmup);
+    if (lr_kind != NN_LR_NONE && conf->mode == NN_MODE_BATCHED) {
+        if (conf->train == NN_TRAIN_CG) {
+            NN_ERROR(stderr, "[lr_schedule] is not supported by [train] CG (the line search chooses its own step); "
+                             "use [train] BP, BPM or ADAM\n");
+            return FALSE;
+        }
+        if (lr_kind == NN_LR_PLATEAU && !conf->validate) {
+            NN_ERROR(stderr, "[lr_schedule] plateau needs [validate] N: there is no validation loss to watch\n");
+            return FALSE;
+        }
+    }
     HpnnTraceRange tr("nn_train_kernel");
     HpnnSamples src;
     if (!src.open(conf->samples)) {
@@ -653,6 +739,9 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
         free(conf->cg_history);
         conf->cg_history = NULL;
         conf->n_cg_history = 0;
+        free(conf->lr_history);
+        conf->lr_history = NULL;
+        conf->n_lr_history = 0;
         if (conf->keep_best && !conf->validate) {
             NN_ERROR(stderr, "[keep_best] needs [validate] N: there is no validation pass to keep the best of\n");
             return FALSE;
@@ -700,6 +789,29 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
         o.nv = nv;
         o.keep_best = (UINT)conf->keep_best;
         o.patience = conf->patience;
+        if (lr_kind != NN_LR_NONE) {
+            o.sched = 1;
+            hpnn_lr_state_init(&o.lrs, (unsigned int)lr_kind, lr, lr_gamma, lr_period, lr_span, lr_end, lr_min,
+                               lr_patience, lr_warmup, conf->epochs_done);
+            if (!hpnn_lr_valid(&o.lrs)) {
+                NN_ERROR(stderr, "[lr_schedule]: needs finite [lr] and [lr_end], 0 < [lr_gamma] <= 1, [lr_period] >= 1, "
+                                 "[lr_min] >= 0, [lr_span] >= 1 for linear and [lr_patience] >= 1 for plateau\n");
+                return FALSE;
+            }
+            /* plateau continues from the running fields a state file left in the kernel */
+            if (lr_kind == NN_LR_PLATEAU && k->lr_loaded) {
+                o.lrs.scale = k->lr_scale;
+                o.lrs.best = k->lr_best;
+                o.lrs.stale = k->lr_stale;
+                o.lrs.cuts = k->lr_cuts;
+                o.lrs.valid = k->lr_valid;
+            }
+            static const char *lrn[] = {"constant", "step", "linear", "plateau"};
+            NN_OUT(stdout, "batched %s training: learning rate schedule %s, lr %g gamma %g period %u span %u end %g "
+                           "min %g patience %u warmup %u\n", gpu ? "GPU" : "CPU", lrn[lr_kind], lr, lr_gamma,
+                   lr_period, lr_span, lr_end, lr_min, lr_patience, lr_warmup);
+        }
+        k->lr_loaded = 0;
         UINT ng = 1;
         _NN(get, n_gpu)(&ng);
         o.n_gpu = ng ? ng : 1;
@@ -745,6 +857,23 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
                 hpnn_metrics_emit("cg", buf);
             }
         }
+        for (UINT i = 0; ok && i < st.n_lr; i++) {
+            NN_OUT(stdout, "LR: epoch %u lr=%.17g\n", o.epoch0 + i + 1, st.lr_hist[i]);
+            if (hpnn_metrics_active()) {
+                char buf[128];
+                snprintf(buf, sizeof buf, "\"engine\": \"%s\", \"epoch\": %u, \"lr\": %.17g", gpu ? "gpu" : "cpu",
+                         o.epoch0 + i + 1, st.lr_hist[i]);
+                hpnn_metrics_emit("lr", buf);
+            }
+        }
+        if (ok && o.sched) {
+            /* the schedule state of the returned kernel: nn_dump_state saves plateau's */
+            k->lr_scale = st.lrs.scale;
+            k->lr_best = st.lrs.best;
+            k->lr_stale = st.lrs.stale;
+            k->lr_cuts = st.lrs.cuts;
+            k->lr_valid = st.lrs.valid;
+        }
         for (UINT i = 0; ok && i < st.n_val; i++)
             NN_OUT(stdout, "VALIDATION: epoch %u loss=%.10f acc=%u/%u\n", st.val[i].epoch, st.val[i].loss,
                    st.val[i].correct, st.val[i].n);
@@ -779,9 +908,12 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
             conf->n_validation = st.n_val;
             conf->cg_history = st.cg;
             conf->n_cg_history = st.n_cg;
+            conf->lr_history = st.lr_hist;
+            conf->n_lr_history = st.n_lr;
         } else {
             free(st.val);
             free(st.cg);
+            free(st.lr_hist);
         }
         if (hpnn_metrics_active()) {
             char buf[384];
@@ -810,6 +942,11 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
         static bool warned_p = false;
         if (!warned_p) NN_WARN(stderr, "[patience] has no effect in online mode (ignored)\n");
         warned_p = true;
+    }
+    if (lr_kind != NN_LR_NONE) {
+        static bool warned_l = false; /* no epochs here to change the rate between */
+        if (!warned_l) NN_WARN(stderr, "[lr_schedule] has no effect in online mode (ignored)\n");
+        warned_l = true;
     }
     if (conf->shuffle == NN_SHUFFLE_EPOCH) {
         static bool warned = false; /* no epochs here: every sample is trained to convergence once */

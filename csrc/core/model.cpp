@@ -57,6 +57,9 @@ extern "C" kernel_ann *ann_kernel_allocate(UINT n_inputs, UINT n_hiddens, const 
     k->dv = NULL;
     k->adam_t = 0;
     k->adam_p1 = k->adam_p2 = 1.0;
+    k->lr_scale = 1.0;
+    k->lr_best = 0.0;
+    k->lr_stale = k->lr_cuts = k->lr_valid = k->lr_loaded = 0;
     return k;
 }
 

@@ -13,12 +13,14 @@
  *   char magic[8] = "HPNNSTA1"
  *   u32 type, train, L (weight layers), has_momentum
  *   u32 dims[L + 1]             n_in, h_1 .. h_{L-1}, n_out
- *   u32 seed, epochs_done, has_adam, reserved
+ *   u32 seed, epochs_done, has_adam, has_sched
  *   u64 samples_seen
  *   f64 W_l (N_l x M_l row-major), l = 0 .. L-1
  *   f64 dW_l (same shapes)      when has_momentum ([train] ADAM: the first moment)
  *   f64 V_l (same shapes)       when has_adam: the second moment, then
  *   u64 t, f64 p1, f64 p2       the steps taken and the running products beta1^t, beta2^t
+ *   f64 scale, f64 best,        when has_sched ([lr_schedule] plateau, <libhpnn/lrsched.h>): the
+ *   u32 stale, cuts, valid, 0   running fields of the schedule, 32 bytes
  *   u64 FNV-1a checksum of every byte above
  */
 #include <libhpnn/ann.h>
@@ -85,7 +87,9 @@ extern "C" BOOL _NN(dump, state)(nn_def *conf, const CHAR *filename) {
     w.u32(conf->seed);
     w.u32(conf->epochs_done);
     w.u32(adam ? 1u : 0u);
-    w.u32(0);
+    /* written for plateau only: every other file is the same bytes as without a schedule */
+    const bool sched = conf->lr_schedule == NN_LR_PLATEAU;
+    w.u32(sched ? 1u : 0u);
     w.put(&conf->samples_seen, 8);
     for (UINT l = 0; l < L; l++) {
         const layer_ann *ly = layer_at(k, l);
@@ -104,6 +108,14 @@ extern "C" BOOL _NN(dump, state)(nn_def *conf, const CHAR *filename) {
         w.put(&k->adam_t, 8);
         w.put(&k->adam_p1, 8);
         w.put(&k->adam_p2, 8);
+    }
+    if (sched) {
+        w.put(&k->lr_scale, 8);
+        w.put(&k->lr_best, 8);
+        w.u32(k->lr_stale);
+        w.u32(k->lr_cuts);
+        w.u32(k->lr_valid);
+        w.u32(0);
     }
     const UINT64 h = hpnn_fnv1a(w.buf.data(), w.buf.size(), HPNN_FNV_SEED);
     w.put(&h, 8);
@@ -162,9 +174,13 @@ extern "C" BOOL _NN(load, state)(nn_def *conf, const CHAR *filename) {
     }
     const UINT seed = r.u32(), epochs = r.u32();
     const UINT has_adam = r.u32();
-    r.u32();
+    const UINT has_sched = r.u32();
     if (has_adam > 1 || (has_adam && !has_mom)) {
         NN_ERROR(stderr, "state file %s: bad Adam flag\n", filename);
+        return FALSE;
+    }
+    if (has_sched > 1) {
+        NN_ERROR(stderr, "state file %s: bad schedule flag\n", filename);
         return FALSE;
     }
     UINT64 seen = 0;
@@ -190,6 +206,13 @@ extern "C" BOOL _NN(load, state)(nn_def *conf, const CHAR *filename) {
         r.get(&at, 8);
         r.get(&ap1, 8);
         r.get(&ap2, 8);
+    }
+    DOUBLE ls = 1.0, lb = 0.0;
+    UINT lw[4] = {0, 0, 0, 0};
+    if (has_sched) {
+        r.get(&ls, 8);
+        r.get(&lb, 8);
+        for (UINT &x : lw) x = r.u32();
     }
     if (!r.ok || r.off != buf.size() - 8) {
         NN_ERROR(stderr, "state file %s: bad size\n", filename);
@@ -217,6 +240,17 @@ extern "C" BOOL _NN(load, state)(nn_def *conf, const CHAR *filename) {
         k->adam_p1 = ap1;
         k->adam_p2 = ap2;
     }
+    /* [lr_schedule] plateau: the next batched call continues from these (nn_train_kernel) */
+    const bool want_sched = conf->lr_schedule == NN_LR_PLATEAU;
+    if (has_sched && !want_sched)
+        NN_WARN(stderr, "state file %s holds a plateau schedule but [lr_schedule] is not plateau: it is ignored\n",
+                filename);
+    k->lr_loaded = has_sched && want_sched ? 1u : 0u;
+    k->lr_scale = k->lr_loaded ? ls : 1.0;
+    k->lr_best = k->lr_loaded ? lb : 0.0;
+    k->lr_stale = k->lr_loaded ? lw[0] : 0u;
+    k->lr_cuts = k->lr_loaded ? lw[1] : 0u;
+    k->lr_valid = k->lr_loaded ? lw[2] : 0u;
     hpnn_gpu_mark_host_dirty(k);
     conf->seed = seed;
     conf->epochs_done = epochs;

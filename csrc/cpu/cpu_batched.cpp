@@ -188,6 +188,7 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
     /* [train] ADAM: the moments in k->dw (first) and k->dv (second), the running state in the
      * kernel; zero unless the call resumes a loaded state */
     const bool adam = o->train == NN_TRAIN_ADAM;
+    const bool cg = o->train == NN_TRAIN_CG;
     hpnn_adam_state ast;
     hpnn_adam_state_init(&ast, o->lr, o->beta1, o->beta2, o->eps, o->decay);
     if (adam) {
@@ -203,12 +204,22 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
         ast.p1 = k->adam_p1;
         ast.p2 = k->adam_p2;
     }
+    /* [lr_schedule]: the state of <libhpnn/lrsched.h>, advanced before the first step of every epoch
+     * and shown every validation loss (the oracle of kernels_lrsched.hip); the step size of an
+     * epoch is the state's lr */
+    const bool sched = o->sched != 0;
+    hpnn_lr_state lrs = o->lrs;
+    std::vector<DOUBLE> lrh;
+    if (sched && (cg || !hpnn_lr_valid(&lrs))) {
+        NN_ERROR(stderr, "[lr_schedule]: %s\n", cg ? "not supported by [train] CG (it chooses its own step)"
+                                                   : "the schedule's keys are out of range");
+        return FALSE;
+    }
     const UINT B = o->batch ? o->batch : 1;
     /* [shuffle] epoch: epoch e trains on a permuted copy, position i = sample src(i) of
      * <libhpnn/shuffle.h> for (n, seed, epochs completed); one batch per epoch: nothing to do */
     /* [train] CG: one epoch = one conjugate-gradient iteration over the whole set (cpu_cg.cpp);
      * the sample order only changes a summation order, so nothing is reshuffled */
-    const bool cg = o->train == NN_TRAIN_CG;
     const bool shuffle = o->shuffle && B < n && !cg;
     if (o->shuffle && cg) NN_OUT(stdout, "batched CPU training: CG sums over the whole set, no reshuffle\n");
     else if (o->shuffle && !shuffle) NN_OUT(stdout, "batched CPU training: one batch per epoch, no reshuffle\n");
@@ -233,6 +244,7 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
     auto layer = [&](UINT l) { return l + 1 < L ? &k->hiddens[l] : &k->output; };
     std::vector<std::vector<DOUBLE>> bestW, bestV, bestA;
     hpnn_adam_state best_ast = ast;
+    hpnn_lr_state best_lrs = lrs;
     bool have_best = false, stop = false;
     DOUBLE best_sum = 0.0;
     UINT best_hits = 0, best_index = 0, stale = 0, epochs_run = 0;
@@ -249,6 +261,12 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
                 memcpy(&Ts[(size_t)i * k->n_outputs], T + (size_t)perm[i] * k->n_outputs, sizeof(DOUBLE) * k->n_outputs);
             }
         }
+        if (sched) {
+            hpnn_lr_advance(&lrs);
+            lrh.push_back(lrs.lr);
+            if (adam) ast.lr = lrs.lr; /* the Adam advance of the next step derives c1 and wd from it */
+        }
+        const DOUBLE lr_e = sched ? lrs.lr : o->lr;
         if (cg) {
             cgs.iterate(k, o->type, X, T, n, B, [&](DOUBLE *sum, UINT *h) {
                 hpnn_validation_record r;
@@ -264,7 +282,7 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
             UINT b = (n - s < B) ? n - s : B;
             const DOUBLE *xb = Xe + (size_t)s * k->n_inputs, *tb = Te + (size_t)s * k->n_outputs;
             last = adam ? hpnn_cpu_adam_step(k, o->type, xb, tb, b, &ast, &hits)
-                        : hpnn_cpu_batched_step(k, o->type, xb, tb, b, o->lr, mom, o->alpha, &hits);
+                        : hpnn_cpu_batched_step(k, o->type, xb, tb, b, lr_e, mom, o->alpha, &hits);
             acc += last;
             nb++;
             samples += b;
@@ -280,6 +298,7 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
             cpu_validate(k, o->type, o->Xv, o->Tv, o->nv, &r, &sum);
             hpnn_metrics_validation("cpu", r.epoch, r.loss, r.correct, r.n);
             val.push_back(r);
+            if (sched) hpnn_lr_plateau(&lrs, sum); /* before the snapshot: the best state holds this pass */
             if (keep && hpnn_best_improves((int)o->keep_best, have_best, sum, r.correct, best_sum, best_hits)) {
                 have_best = true;
                 best_sum = sum;
@@ -290,6 +309,7 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
                 bestV.resize(mom || adam ? L : 0);
                 bestA.resize(adam ? L : 0);
                 best_ast = ast;
+                best_lrs = lrs;
                 for (UINT l = 0; l < L; l++) {
                     const size_t nw = (size_t)layer(l)->n_neurons * layer(l)->n_inputs;
                     bestW[l].assign(layer(l)->weights, layer(l)->weights + nw);
@@ -332,6 +352,14 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
             st->val = (hpnn_validation_record *)malloc(val.size() * sizeof(val[0]));
             if (!st->val) return FALSE;
             memcpy(st->val, val.data(), val.size() * sizeof(val[0]));
+        }
+        st->lrs = have_best ? best_lrs : lrs;
+        st->lr_hist = NULL;
+        st->n_lr = (UINT)lrh.size();
+        if (!lrh.empty()) {
+            st->lr_hist = (DOUBLE *)malloc(lrh.size() * sizeof(DOUBLE));
+            if (!st->lr_hist) return FALSE;
+            memcpy(st->lr_hist, lrh.data(), lrh.size() * sizeof(DOUBLE));
         }
         st->cg = NULL;
         st->n_cg = cg ? epochs_run : 0;

@@ -59,6 +59,19 @@ extern "C" BOOL hpnn_gpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
         }
         return train_single(k, X, T, n, o, st);
     }
+    if (o->sched) {
+        /* [lr_schedule] exists on one device only: the rate lives in one device's memory */
+        if (o->tp) {
+            NN_ERROR(stderr, "[lr_schedule] is not supported by tensor-parallel batched training; use one GPU "
+                             "([parallel] dp, 1 GPU)\n");
+            return FALSE;
+        }
+        if (lbr >= 2 || hpnn_boot_world() > 1 || o->n_gpu > 1 || (fr && fr[0] == '1') || getenv("HPNN_DP_FORCE")) {
+            NN_ERROR(stderr, "[lr_schedule] is not supported by data-parallel batched training; use one GPU\n");
+            return FALSE;
+        }
+        return train_single(k, X, T, n, o, st);
+    }
     if (o->tp) return hpnn_gpu_train_tp(k, X, T, n, o, st);
     if (lbr >= 2) return train_dp(k, X, T, n, o, st, lbr, true);
     /* one process per GPU under a launcher (torchrun --no-python bin/train_nn ...);

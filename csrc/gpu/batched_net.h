@@ -85,6 +85,22 @@ struct Batched {
     BOOL step_adam(const XSet &xs, long row, const float *T, int ldt, int n_valid) {
         return step(xs, row, T, ldt, n_valid, 0.f, 0.f, false);
     }
+    /* [lr_schedule]: the plan's BP / BPM step reads its rate from the device state (BPlan::
+     * set_schedule, before init; the buffer "lrs"); the driver launches the advance per epoch */
+    bool sched = false;
+    BOOL set_schedule(const hpnn_lr_state &l) {
+        sched = p.set_schedule(l) == 0;
+        return sched ? TRUE : FALSE;
+    }
+    hpnn_lr_state *lr_dev() const { return sched ? p.lrs_dev : nullptr; }
+    hpnn_adam_state *adam_dev() const { return adam ? p.adam_dev : nullptr; }
+    /* the schedule state of the live net, or of a [keep_best] snapshot (its last segment) */
+    BOOL read_schedule(void *const *src, hpnn_lr_state *out) {
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipMemcpy(out, src ? src[masters().size() - 1] : (const void *)p.lrs_dev, sizeof *out,
+                         hipMemcpyDeviceToHost));
+        return TRUE;
+    }
     static constexpr size_t ACC_BYTES = HPNN_STAT_SLOTS * HPNN_STAT_STRIDE * 4;
     static int reduce_sum(grad_t *buf, int G, size_t count, hipStream_t st) {
         return hpnn_reduce_slabs(buf, G, (long)count, (long)count, buf, st);
@@ -148,6 +164,7 @@ struct Batched {
         }
         if (p.cast_weights(s)) return FALSE;
         if (adam && hpnn_adam_preload(s)) return FALSE;
+        if (sched && hpnn_lrsched_preload(s)) return FALSE;
         acc = p.stats;
         gflat = p.gflat;
         memcpy(goff, p.goff, sizeof goff);
@@ -344,6 +361,8 @@ struct Batched {
                 if (b) v.push_back({b, (size_t)p.Np[l] * p.Kp[l] * 4});
         /* [train] ADAM: the state (t, p1, p2 and the coefficients) is one more segment */
         if (adam) v.push_back({p.adam_dev, sizeof(hpnn_adam_state)});
+        /* [lr_schedule]: the schedule state, always the last segment */
+        if (sched) v.push_back({p.lrs_dev, sizeof(hpnn_lr_state)});
         return v;
     }
     BOOL download_from(kernel_ann *k, void *const *src) {
@@ -629,6 +648,54 @@ struct BatchedFP {
         return TRUE;
     }
 
+    /* [lr_schedule] (kernels_lrsched.hip, docs/DESIGN.md 3.2j): the device state, and for BP / BPM
+     * the segment table of the one update launch that reads its rate from it -- allocated only
+     * when scheduled (init_schedule, at the end of init) */
+    DevBuf<hpnn_sched_seg> sched_table;
+    DevBuf<hpnn_lr_state> sched_state;
+    bool sched = false, sched_req = false;
+    hpnn_lr_state sched_cfg;
+    BOOL set_schedule(const hpnn_lr_state &l) { /* before init */
+        if (!hpnn_lr_valid(&l)) return FALSE;
+        sched_cfg = l;
+        sched_req = true;
+        return TRUE;
+    }
+    hpnn_lr_state *lr_dev() const { return sched ? sched_state.get() : nullptr; }
+    hpnn_adam_state *adam_dev() const { return adam ? adam_state.get() : nullptr; }
+    BOOL init_schedule(bool momentum) {
+        HIPCHK(sched_state.alloc(1));
+        HIPCHK(hipMemcpyAsync(sched_state.get(), &sched_cfg, sizeof sched_cfg, hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (!adam_req) {
+            std::vector<hpnn_sched_seg> h(L);
+            for (int l = 0; l < L; l++) {
+                const size_t nw = (size_t)N[l] * M[l];
+                h[l] = {W[l], momentum ? V[l] : nullptr, slab[l], S[l], 0, 0, 0, (long)nw, (unsigned long long)nw};
+            }
+            HIPCHK(sched_table.alloc(L));
+            if (hpnn_sgd_sched_table(F64, sched_table.get(), h.data(), L, momentum ? 1 : 0, s)) {
+                NN_ERROR(stderr, "[lr_schedule]: the segment table was refused (alignment or too many layers)\n");
+                return FALSE;
+            }
+        }
+        sched = true;
+        return hpnn_lrsched_preload(s) == 0;
+    }
+    /* backprop -> one update launch over every layer, the rate read from the device state */
+    BOOL step_sched(const XSet &xs, long row, const T *Tt, int ldt, int n_valid, double alpha, bool mom) {
+        if (!backprop(at(xs, row), Tt, ldt, n_valid)) return FALSE;
+        if (hpnn_sgd_sched_fp(F64, sched_table.get(), L, 1.0 / (double)n_valid, alpha, mom ? 1 : 0, sched_state.get(), s))
+            return FALSE;
+        return hpnn_debug_check("batched scheduled step (fp)") == 0;
+    }
+    BOOL read_schedule(void *const *src, hpnn_lr_state *out) {
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipMemcpy(out, src ? src[masters().size() - 1] : (const void *)sched_state.get(), sizeof *out,
+                         hipMemcpyDeviceToHost));
+        return TRUE;
+    }
+
     BOOL evaluate(const XSet &vs, const T *Tt, int ldt, int nv) {
         for (long row = 0; row < nv; row += Bp) {
             const int rows = (int)std::min((long)Bp, nv - row);
@@ -688,7 +755,8 @@ struct BatchedFP {
         HIPCHK(hpnn_dev_malloc(&Z, (size_t)Bp * N[L - 1] * sizeof(T)));
         HIPCHK(hpnn_dev_malloc(&acc, ACC_BYTES));
         HIPCHK(hipMemsetAsync(acc, 0, ACC_BYTES, s));
-        return adam_req ? init_adam(adam_cfg) : TRUE;
+        if (adam_req && !init_adam(adam_cfg)) return FALSE;
+        return sched_req ? init_schedule(momentum) : TRUE;
     }
 
     BOOL forward(const void *X, int rows) {
@@ -728,6 +796,7 @@ struct BatchedFP {
     }
 
     BOOL step(const XSet &xs, long row, const T *Tt, int ldt, int n_valid, double lr, double alpha, bool mom) {
+        if (sched) return step_sched(xs, row, Tt, ldt, n_valid, alpha, mom);
         if (!backprop(at(xs, row), Tt, ldt, n_valid)) return FALSE;
         const double scale = 1.0 / (double)n_valid;
         for (int l = 0; l < L; l++)
@@ -818,6 +887,8 @@ struct BatchedFP {
             for (const T *b : {W[l], V[l], A2[l]})
                 if (b) v.push_back({b, (size_t)N[l] * M[l] * sizeof(T)});
         if (adam) v.push_back({adam_state.get(), sizeof(hpnn_adam_state)});
+        /* [lr_schedule]: the schedule state, always the last segment */
+        if (sched) v.push_back({sched_state.get(), sizeof(hpnn_lr_state)});
         return v;
     }
     BOOL download_from(kernel_ann *k, void *const *src) {

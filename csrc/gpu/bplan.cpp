@@ -89,6 +89,20 @@ int BPlan::set_adam(double lr, double beta1, double beta2, double eps, double de
     return 0;
 }
 
+int BPlan::set_schedule(const hpnn_lr_state &st) {
+    if (!hpnn_lr_valid(&st)) return -1;
+    lrs0 = st;
+    sched = true;
+    g0_fused = tn_update = tn8_side = false;
+    return 0;
+}
+
+int BPlan::advance_schedule(double *hist, unsigned int *cursor, unsigned int cap, hipStream_t s) {
+    if (!sched || !lrs_dev) return -1;
+    sched_launches++;
+    return hpnn_lr_advance_dev(lrs_dev, adam ? adam_dev : nullptr, hist, cursor, cap, s);
+}
+
 int BPlan::configure(const int *sizes, int n_layers, int net_type, int batch_size, bool momentum_, int fused,
                      const int *splits, int mid_grid_req, bool device, std::string *err) {
     auto fail = [&](int code, const std::string &m) {
@@ -179,6 +193,7 @@ int BPlan::configure(const int *sizes, int n_layers, int net_type, int batch_siz
         add("D", l, BD_BF16, {Bp, Np[l]}, false);
     }
     if (adam) add("adam", -1, BD_F32, {(long)(sizeof(hpnn_adam_state) / 4)}, true);
+    if (sched) add("lrs", -1, BD_F32, {(long)(sizeof(hpnn_lr_state) / 4)}, true);
     add("gflat", -1, BD_F32, {(long)goff[L]}, true);
     add("Z", -1, BD_F32, {Bp, Np[L - 1]}, false);
     add("stats", -1, BD_F32, {HPNN_STAT_SLOTS, HPNN_STAT_STRIDE}, true);
@@ -221,6 +236,7 @@ void BPlan::name_pointers() {
         D[l] = buf("D", l);
     }
     adam_dev = (hpnn_adam_state *)buf("adam");
+    lrs_dev = (hpnn_lr_state *)buf("lrs");
     gflat = (float *)buf("gflat");
     Z = (float *)buf("Z");
     stats = (float *)buf("stats");
@@ -245,6 +261,7 @@ int BPlan::allocate(hipStream_t s) {
     name_pointers();
     /* adam0 is a member: it outlives the copy */
     if (adam && hipMemcpyAsync(adam_dev, &adam0, sizeof adam0, hipMemcpyHostToDevice, s) != hipSuccess) return -7;
+    if (sched && hipMemcpyAsync(lrs_dev, &lrs0, sizeof lrs0, hipMemcpyHostToDevice, s) != hipSuccess) return -7;
     return 0;
 }
 
@@ -340,6 +357,11 @@ int BPlan::grad_layer(int l, const XIn &x, bool reduce, hipStream_t s) {
 }
 
 int BPlan::apply_optimizer(const hpnn_upd_layer *u, int n, float lr, float alpha, float scale, hipStream_t s) {
+    if (!adam && sched) { /* BP / BPM with the device rate: one launch (groups past HPNN_UPD_MAX layers) */
+        if (!lrs_dev) return -1;
+        sched_launches += (n + HPNN_UPD_MAX - 1) / HPNN_UPD_MAX;
+        return hpnn_sgd_sched_multi(u, n, alpha, scale, momentum ? 1 : 0, lrs_dev, s);
+    }
     if (!adam) return hpnn_sgd_update_multi(u, n, lr, alpha, scale, momentum ? 1 : 0, s);
     if (!adam_dev) return -1;
     int r = hpnn_adam_advance_dev(adam_dev, s);
@@ -361,7 +383,7 @@ int BPlan::apply_optimizer(const hpnn_upd_layer *u, int n, float lr, float alpha
 }
 
 int BPlan::update_layer(int l, float lr, float alpha, float scale, bool from_g, hipStream_t s) {
-    if (adam) return -1; /* one advance per step: the whole net goes through apply_optimizer */
+    if (adam || sched) return -1; /* the whole net goes through apply_optimizer in one launch */
     const float *G = from_g ? gflat + goff[l] : slab[l];
     const int Sn = from_g ? 1 : S[l];
     const long gs = from_g ? 0 : (long)Np[l] * Kp[l];
@@ -461,7 +483,7 @@ bool BPlan::tn_update_ok(int l) const {
 /* from the last layer to the first: gradient + step per layer (the deltas were all computed
  * with the pre-update weights already) */
 int BPlan::grad_and_update_layers(const XIn &x, float lr, float alpha, float scale, hipStream_t s) {
-    if (adam) { /* every gradient into its slabs, then the one update over all layers */
+    if (adam || sched) { /* every gradient into its slabs, then the one update over all layers */
         hpnn_upd_layer u[16];
         for (int l = L - 1; l >= 0; l--) {
             const int r = grad_layer(l, x, false, s);
@@ -545,7 +567,7 @@ int BPlan::step(const XIn &x, const int *labels, const float *T, int ldt, int n_
                                                         Wb[l], Wt[l], lr, alpha, scale, momentum ? 1 : 0, s) == 0)
                 continue;
             if ((r = grad_layer(l, x, false, s))) return r;
-            if (adam || L <= HPNN_UPD_MAX)
+            if (adam || sched || L <= HPNN_UPD_MAX)
                 u[nu++] = {W32[l], V32[l], slab[l], (long)Np[l] * Kp[l], Wb[l], Wt[l], nullptr, S[l], Np[l], Kp[l]};
             else if ((r = update_layer(l, lr, alpha, scale, false, s)))
                 return r;
@@ -611,6 +633,7 @@ int BPlan::grads_local(const XIn &x, const int *labels, const float *T, int ldt,
 int BPlan::xchg_step(const XIn &x, const int *labels, const float *T, int ldt, int n_valid, float lr, float alpha,
                      float scale, const hpnn_xar_view &xv, hipStream_t s) {
     if (mode != 't' && mode != 'x' && mode != 'm') return -1;
+    if (sched) return -1; /* the fused epilogue takes its rate by value */
     if (!fm_input(x) || !g0cnt || !g0_fused || !hpnn_gemm_fm_direct_update_ok(Kp[0], Np[0], Kp[0], Bp, S[0]) ||
         S[0] * hpnn_g0_tiles(Np[0], Kp[0]) > HPNN_XAR_MAX_BLOCKS || (long)goff[L] > xv.half)
         return -1;
@@ -693,7 +716,7 @@ int BPlan::grads_slabs(const XIn &x, const int *labels, const float *T, int ldt,
 }
 
 int BPlan::update_flat(const float *G, float lr, float alpha, float scale, hipStream_t s) {
-    if (L > HPNN_UPD_MAX && !adam) {
+    if (L > HPNN_UPD_MAX && !adam && !sched) {
         for (int l = 0; l < L; l++) {
             int r = hpnn_sgd_update(W32[l], V32[l], G + goff[l], 1, 0, Wb[l], Wt[l], Np[l], Kp[l], lr, alpha, scale,
                                     momentum ? 1 : 0, s);

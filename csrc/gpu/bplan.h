@@ -96,6 +96,11 @@ class BPlan {
     bool adam = false;
     hpnn_adam_state adam0;  /* the state a fresh plan starts from (allocate uploads it) */
     long adam_launches = 0; /* launches of kernels_adam.hip issued by this plan (tests) */
+    /* [lr_schedule] (set_schedule): the BP / BPM step reads its rate from "lrs", the device
+     * hpnn_lr_state, when it runs; under ADAM the advance of the schedule stores it into "adam" */
+    bool sched = false;
+    hpnn_lr_state lrs0;      /* the state a fresh plan starts from (allocate uploads it) */
+    long sched_launches = 0; /* launches of kernels_lrsched.hip issued by this plan (tests) */
     /* per-layer: the delta GEMM reads W (NN form, hpnn_gemm_nn_bf16) instead of W^T, which is
      * then not kept current (the sharded data-parallel step sets it: no transpose per update) */
     bool nn_bwd[16] = {false};
@@ -109,6 +114,16 @@ class BPlan {
      * ONE hpnn_adam_update_multi over all layers.  step() / update_flat() then ignore their lr and
      * alpha; update_layer() is refused (one advance per step).  -1: coefficients out of range. */
     int set_adam(double lr, double beta1, double beta2, double eps, double decay);
+    /* [lr_schedule], before configure: adds the buffer spec "lrs" (the device hpnn_lr_state, which
+     * starts as st) and turns off the fused BP / BPM epilogues exactly as set_adam does, so every
+     * mode ends in ONE hpnn_sgd_sched_multi over all layers with the rate read from the device
+     * (<libhpnn/lrsched.h>, docs/DESIGN.md 3.2j).  step() / update_flat() then ignore their lr;
+     * update_layer() and xchg_step() are refused.  The caller launches advance_schedule() once
+     * per epoch, before its first step.  -1: hpnn_lr_valid fails. */
+    int set_schedule(const hpnn_lr_state &st);
+    /* one hpnn_lr_advance_dev on the plan's state (and its Adam state, if any); hist / cursor /
+     * cap: the device history of rates, may be null */
+    int advance_schedule(double *hist, unsigned int *cursor, unsigned int cap, hipStream_t s);
     /* fused: -1 auto (the fastest eligible mode), 0 per-layer only, or 't' / 'x' / 'm' / 'w'
      * (an error when not eligible); splits: per-layer split-K override (null / 0 = pick);
      * mid_grid_req: block slabs of mode 'm'; on_device = false: a host-only configuration
@@ -202,6 +217,7 @@ class BPlan {
     /* named pointers (valid after allocate / bind) */
     float *W32[16] = {0}, *V32[16] = {0}, *A32[16] = {0}, *slab[16] = {0};
     hpnn_adam_state *adam_dev = nullptr;
+    hpnn_lr_state *lrs_dev = nullptr;
     void *Wb[16] = {0}, *Wt[16] = {0}, *H[16] = {0}, *D[16] = {0};
     float *Z = nullptr, *stats = nullptr, *vstats = nullptr, *gflat = nullptr, *midslab = nullptr, *midtmp = nullptr;
     void *W0f = nullptr;

@@ -16,6 +16,7 @@
 #include <libhpnn/ann.h>
 #include <libhpnn/cg.h>
 #include <libhpnn/adam.h>
+#include <libhpnn/lrsched.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -70,6 +71,11 @@ typedef struct {
     /* [train] ADAM: the coefficients (lr is the step size, alpha is unused); resume: start from
      * the moments k->dw, k->dv and k->adam_t, adam_p1, adam_p2 */
     DOUBLE beta1, beta2, eps, decay;
+    /* [lr_schedule] (sched = 1; single-device engines and the CPU oracle): the state the call starts
+     * from -- lr0 = lr, epoch = epoch0, and under plateau the running fields of a loaded state file.
+     * The step size of every epoch is then the state's lr (<libhpnn/lrsched.h>), not `lr` */
+    UINT sched;
+    hpnn_lr_state lrs;
 } hpnn_batched_opts;
 
 /* one validation pass: the absolute epoch it followed, the mean loss per sample and the argmax
@@ -102,6 +108,12 @@ typedef struct {
      * malloc'ed by the engine (the caller frees cg) */
     hpnn_cg_record *cg;
     UINT n_cg;
+    /* [lr_schedule]: the rate of every epoch of the call up to the last one that counts (the
+     * stopping pass's epoch after an early stop), malloc'ed by the engine (the caller frees
+     * lr_hist), and the schedule state of the returned kernel (the best pass's under [keep_best]) */
+    DOUBLE *lr_hist;
+    UINT n_lr;
+    hpnn_lr_state lrs;
 } hpnn_batched_stats;
 
 /* the improvement rule of [keep_best] (one definition for every engine; the device form is
@@ -168,6 +180,20 @@ void hpnn_adam_host_update(int f64, void *W, void *M, void *V, const void *G, in
  * mirrors t, p1, p2 into the kernel; returns the mean loss before the update */
 DOUBLE hpnn_cpu_adam_step(kernel_ann *k, nn_type type, const DOUBLE *X, const DOUBLE *T, UINT b, hpnn_adam_state *s,
                           UINT *hits /* may be NULL: += argmax hits */);
+
+/* ---- [lr_schedule] on the host (the CPU form of hpnn_amd.ops.lr_* / sgd_sched_*): the rule of
+ * <libhpnn/lrsched.h> on host memory; f64 selects double, else float ---- */
+/* fills a fresh state (scale 1, nothing judged, the next epoch = epoch); returns hpnn_lr_valid */
+int hpnn_lr_host_init(hpnn_lr_state *s, unsigned int kind, double lr0, double gamma, unsigned int period,
+                      unsigned int span, double lr_end, double lr_min, unsigned int patience, unsigned int warmup,
+                      unsigned int epoch);
+int hpnn_lr_host_valid(const hpnn_lr_state *s);
+void hpnn_lr_host_advance(hpnn_lr_state *s);
+void hpnn_lr_host_plateau(hpnn_lr_state *s, double loss_sum);
+/* g = (G[0] + G[1] + ... + G[S-1]) * scale, slabs gstride elements apart, in slab order; then the
+ * scheduled BP / BPM element rule with lr = (T)s->lr on W and V (V may be NULL under BP) */
+void hpnn_sgd_sched_host_update(int f64, void *W, void *V, const void *G, int S, long gstride, long n, double scale,
+                                double alpha, int momentum, const hpnn_lr_state *s);
 
 #ifdef __cplusplus
 }

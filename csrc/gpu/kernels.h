@@ -17,6 +17,7 @@
 #include <hip/hip_runtime_api.h>
 #include <libhpnn/cg.h>
 #include <libhpnn/adam.h>
+#include <libhpnn/lrsched.h>
 #include <libhpnn/xar.h>
 
 #ifdef __cplusplus
@@ -454,6 +455,47 @@ int hpnn_adam_update_multi(const hpnn_adam_upd_layer *layers, int n, float scale
                            hipStream_t stream);
 /* loads the unit's code object (an empty launch and a synchronise) before a capture */
 int hpnn_adam_preload(hipStream_t stream);
+/* ---- learning-rate schedules (kernels_lrsched.hip; [lr_schedule], rule in <libhpnn/lrsched.h>) ----
+ * Every launch is capturable, allocates nothing and reads the rate from the DEVICE hpnn_lr_state
+ * when it runs.  Return: 0 launched, -1 refused, -2 bad shape / alignment, -5 launch error.
+ * advance: one thread runs hpnn_lr_advance, appends the new rate to hist[*hist_cursor] (a full
+ * history, *hist_cursor == hist_cap, drops the record; hist may be NULL) and, when adam is not
+ * NULL, stores it into adam->lr for the Adam advance of the next step. */
+int hpnn_lr_advance_dev(hpnn_lr_state *state, hpnn_adam_state *adam, double *hist, unsigned int *hist_cursor,
+                        unsigned int hist_cap, hipStream_t stream);
+/* one thread, behind hpnn_validate_commit on the same stream: hpnn_lr_plateau on
+ * vhist[*vcursor - 1].loss_sum; *vcursor == 0: a no-op */
+int hpnn_lr_plateau_dev(const hpnn_val_record *vhist, const unsigned int *vcursor, hpnn_lr_state *state,
+                        hipStream_t stream);
+/* a segment is one layer of the FP64 / FP32 engines: the weights, the momentum (NULL under BP),
+ * n elements each, and the S gradient slabs gstride elements apart.  hpnn_sgd_sched_table checks
+ * a host table (-1: refused, nothing written), fills first_block / blocks and copies it to the
+ * device (synchronises: setup), as hpnn_adam_table does */
+typedef struct {
+    void *w, *v;
+    const void *g;
+    int S;
+    int blocks;      /* filled by hpnn_sgd_sched_table */
+    int first_block; /* filled by hpnn_sgd_sched_table */
+    int pad;
+    long gstride;
+    unsigned long long n;
+} hpnn_sched_seg;
+#define HPNN_SCHED_MAX_SEGS 16
+int hpnn_sgd_sched_table(int f64, hpnn_sched_seg *segs, const hpnn_sched_seg *host_segs, int n_segs, int momentum,
+                         hipStream_t stream);
+/* every segment in one launch: g = (slab[0] + ... + slab[S-1]) * scale in slab order, then
+ * BP  w += lr g   or   BPM  v += lr g; w += v; v *= alpha   with lr = (T)state->lr */
+int hpnn_sgd_sched_fp(int f64, const hpnn_sched_seg *segs, int n_segs, double scale, double alpha, int momentum,
+                      const hpnn_lr_state *state, hipStream_t stream);
+/* the BF16 plan's BP / BPM step with the device rate, every layer in one launch (n > HPNN_UPD_MAX:
+ * groups of HPNN_UPD_MAX, at most 16 layers): the slab sum in the one order of
+ * hpnn_adam_update_multi, the rule in FP32, then BF16 W, W^T and Wf exactly where
+ * hpnn_sgd_update_multi writes them */
+int hpnn_sgd_sched_multi(const hpnn_upd_layer *layers, int n, float alpha, float scale, int momentum,
+                         const hpnn_lr_state *state, hipStream_t stream);
+/* loads the unit's code object (an empty launch and a synchronise) before a capture */
+int hpnn_lrsched_preload(hipStream_t stream);
 /* profiling (HPNN_TILE_TRACE=1): per-workgroup s_memtime stamps [1024][12] */
 int hpnn_mlp3_tile_trace(unsigned long long *out);
 /* HPNN_G0_TRACE=1 phase stamps of the fused G0 launch: out[512][8] */

@@ -43,6 +43,17 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
         hpnn_adam_state_init(&ast, o->lr, o->beta1, o->beta2, o->eps, o->decay);
         if (!net.set_adam(ast)) return FALSE;
     }
+    /* [lr_schedule]: the device state every update launch reads its rate from, a history of one
+     * rate per epoch; allocated only when scheduled */
+    const bool sched = o->sched != 0;
+    if (sched && cg) {
+        NN_ERROR(stderr, "[lr_schedule] is not supported by [train] CG (the line search chooses its own step)\n");
+        return FALSE;
+    }
+    if (sched && !net.set_schedule(o->lrs)) {
+        NN_ERROR(stderr, "[lr_schedule]: the schedule's keys are out of range\n");
+        return FALSE;
+    }
     if (!net.init(k, B, o->type, mom || adam, s, B % 32 == 0)) return FALSE;
     NN_OUT(stdout, "batched GPU training: %s, %d samples per step\n", Net::name(), B);
     if (mom && o->resume && !net.upload_momentum(k)) return FALSE;
@@ -50,6 +61,13 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
         if (o->resume && k->dv && !net.upload_moments(k)) return FALSE;
         NN_OUT(stdout, "batched GPU training: Adam, beta1 %g beta2 %g epsilon %g decay %g\n", o->beta1, o->beta2,
                o->eps, o->decay);
+    }
+    DevBuf<double> lrhist;
+    DevBuf<unsigned int> lrcur;
+    if (sched) {
+        HIPCHK(lrhist.alloc(o->epochs ? o->epochs : 1));
+        HIPCHK(lrcur.alloc(1));
+        HIPCHK(hipMemset(lrcur.get(), 0, sizeof(unsigned int)));
     }
     const int n_batches = (int)((n + B - 1) / B);
     int rows_p = (n_batches - 1) * B + net.Bp; /* last batch reads Bp rows */
@@ -129,6 +147,8 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
     auto validation = [&]() -> bool {
         if (net.evaluate(va.xs, va.T.get(), n_out, nval) &&
             hpnn_validate_commit(net.vacc(), vhist.get(), vcur.get(), (unsigned int)vsched.size(), s) == 0 &&
+            /* plateau sees the pass before the snapshot: the best state holds this pass */
+            (!sched || hpnn_lr_plateau_dev(vhist.get(), vcur.get(), net.lr_dev(), s) == 0) &&
             (!keep || (hpnn_best_commit(vhist.get(), vcur.get(), best.state.get(), (int)o->keep_best, o->patience,
                                         s) == 0 &&
                        hpnn_snapshot_if(best.table.get(), (int)best.segs.size(), best.take(), s) == 0)))
@@ -148,6 +168,11 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
     auto epoch = [&]() -> bool {
         if constexpr (Net::has_cg) {
             if (cg) return net.iterate_cg(xs, Td, n_out, (int)n);
+        }
+        /* the first launch of every epoch: the rate of this epoch into the device state */
+        if (sched && hpnn_lr_advance_dev(net.lr_dev(), net.adam_dev(), lrhist.get(), lrcur.get(), o->epochs, s)) {
+            NN_ERROR(stderr, "batched GPU training: the schedule advance could not be launched\n");
+            return false;
         }
         if (shuffle && !reshuffle()) {
             NN_ERROR(stderr, "batched GPU training: the epoch reshuffle could not be launched\n");
@@ -305,6 +330,23 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
             if (ok) crec.resize(hb.stop && !vrec.empty() ? vsched[vrec.size() - 1] - o->epoch0 : (size_t)e);
         }
     }
+    /* [lr_schedule]: the history, once, up to the last epoch that counts (the stopping pass's epoch
+     * after an early stop), and the state of the returned kernel */
+    std::vector<double> lrec;
+    hpnn_lr_state lrs_out = o->lrs;
+    if (ok && sched) {
+        unsigned int filed = 0;
+        lrec.resize(o->epochs);
+        ok = hipStreamSynchronize(s) == hipSuccess &&
+             hipMemcpy(&filed, lrcur.get(), sizeof filed, hipMemcpyDeviceToHost) == hipSuccess &&
+             hipMemcpy(lrec.data(), lrhist.get(), lrec.size() * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+        if (ok && filed < (unsigned int)e) {
+            NN_ERROR(stderr, "batched GPU training: %u learning rates filed, %d epochs run\n", filed, e);
+            ok = FALSE;
+        }
+        if (ok) lrec.resize(hb.stop && !vrec.empty() ? vsched[vrec.size() - 1] - o->epoch0 : (size_t)e);
+        if (ok) ok = net.read_schedule(hb.valid ? best.dst.data() : nullptr, &lrs_out);
+    }
     graphs.clear();
     if (ok) ok = net.download_from(k, hb.valid ? best.dst.data() : nullptr);
     if (ok && st) {
@@ -319,6 +361,14 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
             st->cg = (hpnn_cg_record *)malloc(crec.size() * sizeof(hpnn_cg_record));
             if (!st->cg) ok = FALSE;
             else memcpy(st->cg, crec.data(), crec.size() * sizeof(hpnn_cg_record));
+        }
+        st->lrs = lrs_out;
+        st->lr_hist = NULL;
+        st->n_lr = (UINT)lrec.size();
+        if (!lrec.empty()) {
+            st->lr_hist = (DOUBLE *)malloc(lrec.size() * sizeof(DOUBLE));
+            if (!st->lr_hist) ok = FALSE;
+            else memcpy(st->lr_hist, lrec.data(), lrec.size() * sizeof(DOUBLE));
         }
         st->val = NULL;
         st->n_val = (UINT)vrec.size();

@@ -51,7 +51,7 @@ XIn xin(uptr x, uptr xg, int u8, float scale) {
 void bind_plan(py::module_ &m) {
     py::class_<BPlan>(m, "BPlan")
         .def(py::init([](std::vector<int> sizes, int type, int batch, bool momentum, int fused,
-                         std::vector<int> splits, int mid_grid, bool device, py::object adam) {
+                         std::vector<int> splits, int mid_grid, bool device, py::object adam, py::object schedule) {
                  auto *p = new BPlan();
                  std::string err;
                  if (sizes.size() < 2) throw std::runtime_error("BPlan: at least two layer sizes");
@@ -62,6 +62,21 @@ void bind_plan(py::module_ &m) {
                          delete p;
                          throw std::invalid_argument("BPlan: adam = (lr, 0 <= beta1 < 1, 0 <= beta2 < 1, eps > 0, "
                                                      "decay >= 0)");
+                     }
+                 }
+                 if (!schedule.is_none()) { /* (kind, lr0, gamma, period, span, lr_end, lr_min, patience, warmup,
+                                               epoch): BPlan::set_schedule before configure */
+                     py::tuple a = schedule.cast<py::tuple>();
+                     hpnn_lr_state st;
+                     if (py::len(a) == 10)
+                         hpnn_lr_state_init(&st, a[0].cast<unsigned int>(), a[1].cast<double>(), a[2].cast<double>(),
+                                            a[3].cast<unsigned int>(), a[4].cast<unsigned int>(), a[5].cast<double>(),
+                                            a[6].cast<double>(), a[7].cast<unsigned int>(), a[8].cast<unsigned int>(),
+                                            a[9].cast<unsigned int>());
+                     if (py::len(a) != 10 || p->set_schedule(st)) {
+                         delete p;
+                         throw std::invalid_argument("BPlan: schedule = (kind, lr0, 0 < gamma <= 1, period >= 1, span, "
+                                                     "lr_end, lr_min >= 0, patience, warmup, epoch)");
                      }
                  }
                  std::vector<int> sp(sizes.size(), 0);
@@ -76,7 +91,7 @@ void bind_plan(py::module_ &m) {
              }),
              py::arg("sizes"), py::arg("type"), py::arg("batch"), py::arg("momentum"), py::arg("fused") = -1,
              py::arg("splits") = std::vector<int>(), py::arg("mid_grid") = 512, py::arg("device") = true,
-             py::arg("adam") = py::none())
+             py::arg("adam") = py::none(), py::arg("schedule") = py::none())
         .def("config",
              [](const BPlan &p) {
                  py::dict d;
@@ -209,6 +224,13 @@ void bind_plan(py::module_ &m) {
         .def_readwrite("side_launches", &BPlan::side_launches)
         .def_readonly("adam", &BPlan::adam)
         .def_readwrite("adam_launches", &BPlan::adam_launches)
+        .def_readonly("sched", &BPlan::sched)
+        .def_readwrite("sched_launches", &BPlan::sched_launches)
+        .def("advance_schedule",
+             [](BPlan &p, uptr hist, uptr cursor, unsigned int cap, uptr s) {
+                 check(p.advance_schedule((double *)P(hist), (unsigned int *)P(cursor), cap, S(s)), "advance_schedule");
+             },
+             py::arg("hist") = 0, py::arg("cursor") = 0, py::arg("cap") = 0, py::arg("stream") = 0)
         .def_property_readonly("nn_bwd", [](const BPlan &p) { return std::vector<bool>(p.nn_bwd, p.nn_bwd + 16); })
         .def("tn_update_ok", &BPlan::tn_update_ok)
         .def("predict", [](BPlan &p, uptr X, int n_valid, uptr O, int ldo, uptr s) {
@@ -661,6 +683,70 @@ PYBIND11_MODULE(_native, m) {
         py::arg("scratch"), py::arg("type"), py::arg("momentum"), py::arg("lr"), py::arg("alpha"), py::arg("delta"),
         py::arg("min_iter"), py::arg("max_iter"), py::arg("forward_only"), py::arg("variant"), py::arg("grid") = 0,
         py::arg("xch") = 0, py::arg("ctl") = 0, py::arg("n_slots") = 1, py::arg("stream") = 0);
+    /* [lr_schedule] (csrc/gpu/kernels_lrsched.hip; the host forms: csrc/cpu/cpu_lrsched.cpp) */
+    m.attr("LR_STATE_BYTES") = (int)sizeof(hpnn_lr_state);
+    m.attr("SCHED_SEG_BYTES") = (int)sizeof(hpnn_sched_seg);
+    m.def("lr_host_init", [](uptr state, unsigned int kind, double lr0, double gamma, unsigned int period,
+                             unsigned int span, double lr_end, double lr_min, unsigned int patience,
+                             unsigned int warmup, unsigned int epoch) {
+        return hpnn_lr_host_init((hpnn_lr_state *)P(state), kind, lr0, gamma, period, span, lr_end, lr_min, patience,
+                                 warmup, epoch);
+    });
+    m.def("lr_host_valid", [](uptr state) { return hpnn_lr_host_valid((const hpnn_lr_state *)P(state)); });
+    m.def("lr_host_advance", [](uptr state) { hpnn_lr_host_advance((hpnn_lr_state *)P(state)); });
+    m.def("lr_host_plateau", [](uptr state, double loss) { hpnn_lr_host_plateau((hpnn_lr_state *)P(state), loss); });
+    m.def("sgd_sched_host_update", [](int f64, uptr W, uptr V, uptr G, int Sn, long gstride, long n, double scale,
+                                      double alpha, int momentum, uptr state) {
+        hpnn_sgd_sched_host_update(f64, P(W), P(V), P(G), Sn, gstride, n, scale, alpha, momentum,
+                                   (const hpnn_lr_state *)P(state));
+    });
+    m.def("lrsched_preload", [](uptr stream) { return hpnn_lrsched_preload(S(stream)); });
+    m.def("lr_advance", [](uptr state, uptr adam, uptr hist, uptr cursor, unsigned int cap, uptr stream) {
+        return hpnn_lr_advance_dev((hpnn_lr_state *)P(state), (hpnn_adam_state *)P(adam), (double *)P(hist),
+                                   (unsigned int *)P(cursor), cap, S(stream));
+    });
+    m.def("lr_plateau", [](uptr vhist, uptr vcursor, uptr state, uptr stream) {
+        return hpnn_lr_plateau_dev((const hpnn_val_record *)P(vhist), (const unsigned int *)P(vcursor),
+                                   (hpnn_lr_state *)P(state), S(stream));
+    });
+    m.def("sgd_sched_table", [](int f64, uptr segs,
+                                const std::vector<std::tuple<uptr, uptr, uptr, int, long, unsigned long long>> &host,
+                                int momentum, uptr stream) {
+        std::vector<hpnn_sched_seg> h;
+        for (const auto &t : host)
+            h.push_back({P(std::get<0>(t)), P(std::get<1>(t)), P(std::get<2>(t)), std::get<3>(t), 0, 0, 0,
+                         std::get<4>(t), std::get<5>(t)});
+        return hpnn_sgd_sched_table(f64, (hpnn_sched_seg *)P(segs), h.data(), (int)h.size(), momentum, S(stream));
+    });
+    m.def("sgd_sched_fp", [](int f64, uptr segs, int n_segs, double scale, double alpha, int momentum, uptr state,
+                             uptr stream) {
+        return hpnn_sgd_sched_fp(f64, (const hpnn_sched_seg *)P(segs), n_segs, scale, alpha, momentum,
+                                 (const hpnn_lr_state *)P(state), S(stream));
+    });
+    m.def(
+        "sgd_sched_multi",
+        [](py::list layers, float alpha, float scale, int momentum, uptr state, uptr stream) {
+            hpnn_upd_layer L[2 * HPNN_UPD_MAX];
+            const int n = (int)py::len(layers);
+            if (n < 1 || n > 2 * HPNN_UPD_MAX) throw std::runtime_error("sgd_sched_multi: 1..16 layers");
+            for (int i = 0; i < n; i++) {
+                py::tuple t = layers[i].cast<py::tuple>();
+                if (py::len(t) != 10) throw std::runtime_error("sgd_sched_multi: layer tuple of 10");
+                L[i].W32 = (float *)P(t[0].cast<uptr>());
+                L[i].V32 = (float *)P(t[1].cast<uptr>());
+                L[i].G = (const float *)P(t[2].cast<uptr>());
+                L[i].gstride = t[3].cast<long>();
+                L[i].Wbf = P(t[4].cast<uptr>());
+                L[i].Wt = P(t[5].cast<uptr>());
+                L[i].Wf = P(t[6].cast<uptr>());
+                L[i].S = t[7].cast<int>();
+                L[i].N = t[8].cast<int>();
+                L[i].K = t[9].cast<int>();
+            }
+            check(hpnn_sgd_sched_multi(L, n, alpha, scale, momentum, (const hpnn_lr_state *)P(state), S(stream)),
+                  "sgd_sched_multi");
+        },
+        "layers: [(W32, V32, G, gstride, Wbf, Wt, Wf, S, N, K)] device addresses (0 = none)");
     m.def("mlp3_tile_grid", [](int Bp, int grid) { return hpnn_mlp3_tile_grid(Bp, grid); });
     m.def("mlp3_tile_trace", []() {
         std::vector<unsigned long long> v(1024 * 12);

@@ -20,6 +20,7 @@ NN_TRAIN = {"BP": 0, "BPM": 1, "CG": 2, "SPLX": 3, "ADAM": 4}
 NN_MODE = {"online": 0, "batched": 1}
 NN_DTYPE = {"f64": 0, "f32": 1, "bf16": 2}
 NN_DEVICE = {"auto": 0, "cpu": 1, "gpu": 2}
+NN_LR_SCHEDULE = {None: -1, "constant": 0, "step": 1, "linear": 2, "plateau": 3}
 NN_SHUFFLE = {"once": 0, "epoch": 1}
 NN_KEEP_BEST = {"off": 0, "loss": 1, "acc": 2}
 CG_FAILED, CG_RESTART, CG_VERTEX, CG_TOOK7 = 1, 2, 4, 8  # flags of a CG record (include/libhpnn/cg.h)
@@ -66,6 +67,11 @@ def lib():
             "nn_set_train": (None, [vp, i]), "nn_return_batch": (u, [vp]),
             "nn_set_adam": (None, [vp, d, d, d, d]),
             "nn_get_adam": (None, [vp, ctypes.POINTER(d), ctypes.POINTER(d), ctypes.POINTER(d), ctypes.POINTER(d)]),
+            "nn_set_lr_schedule": (None, [vp, i, d, u, u, d, d, u, u]),
+            "nn_get_lr_schedule": (None, [vp, ctypes.POINTER(i), ctypes.POINTER(d), ctypes.POINTER(u),
+                                          ctypes.POINTER(u), ctypes.POINTER(d), ctypes.POINTER(d), ctypes.POINTER(u),
+                                          ctypes.POINTER(u)]),
+            "nn_get_lr_history": (ctypes.POINTER(d), [vp, ctypes.POINTER(u)]),
             "nn_return_last_pass": (u, []), "nn_return_last_total": (u, []),
             "nn_return_version": (cp, []), "nn_return_type": (i, [vp]), "nn_return_train": (i, [vp]),
             "nn_dump_state": (i, [vp, cp]), "nn_load_state": (i, [vp, cp]), "nn_return_epochs_done": (u, [vp]),
@@ -122,7 +128,7 @@ class Network:
 
     # configuration
     def set(self, mode=None, dtype=None, device=None, batch=None, epochs=None, lr=None, momentum=None, seed=None,
-            shuffle=None, validate=None, keep_best=None, patience=None, adam=None):
+            shuffle=None, validate=None, keep_best=None, patience=None, adam=None, lr_schedule=None):
         if mode is not None:
             self.L.nn_set_mode(self.ptr, NN_MODE[mode])
         if dtype is not None:
@@ -154,7 +160,36 @@ class Network:
                 raise ValueError(f"adam: unknown keys {sorted(unknown)} (beta1, beta2, epsilon, decay)")
             cur.update({k: float(v) for k, v in adam.items()})
             self.L.nn_set_adam(self.ptr, cur["beta1"], cur["beta2"], cur["epsilon"], cur["decay"])
+        if lr_schedule is not None:  # dict(kind=, gamma=, period=, span=, lr_end=, lr_min=, patience=, warmup=)
+            cur = self.lr_schedule   # of [lr_schedule]; a missing key keeps its value, kind=None turns it off
+            unknown = set(lr_schedule) - set(cur)
+            if unknown:
+                raise ValueError(f"lr_schedule: unknown keys {sorted(unknown)} ({', '.join(cur)})")
+            cur.update(lr_schedule)
+            if cur["kind"] not in NN_LR_SCHEDULE:
+                raise ValueError(f"lr_schedule: kind {cur['kind']!r} (constant | step | linear | plateau)")
+            self.L.nn_set_lr_schedule(self.ptr, NN_LR_SCHEDULE[cur["kind"]], float(cur["gamma"]), int(cur["period"]),
+                                      int(cur["span"]), float(cur["lr_end"]), float(cur["lr_min"]),
+                                      int(cur["patience"]), int(cur["warmup"]))
         return self
+
+    @property
+    def lr_schedule(self):
+        """the [lr_schedule] keys a training call would use: kind (None: no schedule), gamma, period,
+        span, lr_end, lr_min, patience, warmup"""
+        k = ctypes.c_int()
+        g, e, m = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        p, sp, pa, w = ctypes.c_uint(), ctypes.c_uint(), ctypes.c_uint(), ctypes.c_uint()
+        self.L.nn_get_lr_schedule(self.ptr, *[ctypes.byref(x) for x in (k, g, p, sp, e, m, pa, w)])
+        return {"kind": {v: n for n, v in NN_LR_SCHEDULE.items()}[k.value], "gamma": g.value, "period": p.value,
+                "span": sp.value, "lr_end": e.value, "lr_min": m.value, "patience": pa.value, "warmup": w.value}
+
+    def lr_history(self):
+        """the learning rate of every epoch of the last train() call under [lr_schedule] (a list of
+        floats, empty without a schedule)"""
+        m = ctypes.c_uint()
+        r = self.L.nn_get_lr_history(self.ptr, ctypes.byref(m))
+        return [float(r[i]) for i in range(m.value)]
 
     @property
     def adam(self):

@@ -82,11 +82,16 @@ class MLP:
     optimizer: "sgd" (BP, or BPM with momentum=True) | "adam" with lr, betas, eps, decay (AdamW when
     decay > 0): the plan then keeps the moments V32 (first) and A32 (second) and the state
     `adam_state` ([11] float64, ops.read_adam_state), and train_step ignores its lr / alpha.
+    lr_schedule: None | dict(kind="constant" | "step" | "linear" | "plateau", lr=, gamma=, period=,
+    span=, lr_end=, lr_min=, patience=, warmup=, epoch=) (include/libhpnn/lrsched.h; lr defaults to
+    the `lr` argument): the plan keeps the state `lr_state` ([12] float64, ops.read_lr_state), every
+    step reads its rate from it and ignores train_step's lr, and the caller runs advance_schedule()
+    before the first step of every epoch (and ops.lr_plateau behind a validation pass).
     """
 
     def __init__(self, sizes, net_type="SNN", batch=256, device="cuda", momentum=False, weights=None, seed=10958,
                  init="reference", splits=None, fused=None, mid_grid=512, optimizer="sgd", lr=0.001,
-                 betas=(0.9, 0.999), eps=1e-8, decay=0.0):
+                 betas=(0.9, 0.999), eps=1e-8, decay=0.0, lr_schedule=None):
         self.sizes = list(sizes)
         self.L = len(sizes) - 1
         self.type = TYPES[net_type] if isinstance(net_type, str) else int(net_type)
@@ -98,11 +103,23 @@ class MLP:
             raise ValueError(f"optimizer {optimizer!r} (sgd | adam)")
         self.adam = optimizer == "adam"
         adam_cfg = (float(lr), float(betas[0]), float(betas[1]), float(eps), float(decay)) if self.adam else None
+        self.sched = lr_schedule is not None
+        sched_cfg = None
+        if self.sched:
+            d = dict(kind="constant", lr=lr, gamma=0.5, period=10, span=0, lr_end=0.0, lr_min=0.0, patience=2,
+                     warmup=0, epoch=0)
+            unknown = set(lr_schedule) - set(d)
+            if unknown:
+                raise ValueError(f"lr_schedule: unknown keys {sorted(unknown)} ({', '.join(d)})")
+            d.update(lr_schedule)
+            kind = ops.LR_KIND[d["kind"]] if isinstance(d["kind"], str) else int(d["kind"])
+            sched_cfg = (kind, float(d["lr"]), float(d["gamma"]), int(d["period"]), int(d["span"]), float(d["lr_end"]),
+                         float(d["lr_min"]), int(d["patience"]), int(d["warmup"]), int(d["epoch"]))
         on_gpu = self.device.type == "cuda"
         req = -1 if fused is None or fused is True else (0 if fused is False else ord({"mid": "m"}.get(fused, fused)))
         try:
             self.plan = native().BPlan(self.sizes, self.type, int(batch), bool(momentum), req, list(splits or []),
-                                       int(mid_grid), on_gpu, adam_cfg)
+                                       int(mid_grid), on_gpu, adam_cfg, sched_cfg)
         except ValueError as e:
             raise ValueError(f"fused={fused!r}: {e}") from None
         cfg = self.plan.config()
@@ -129,6 +146,10 @@ class MLP:
         if self.adam:  # the plan's "adam" buffer is the hpnn_adam_state itself
             self.adam_state = b[("adam", -1)].view(torch.float64)
             self.adam_state.copy_(ops.adam_state(*adam_cfg))
+        self.lr_state = None
+        if self.sched:  # the plan's "lrs" buffer is the hpnn_lr_state itself
+            self.lr_state = b[("lrs", -1)].view(torch.float64)
+            self.lr_state.copy_(ops.lr_state(sched_cfg[0], *sched_cfg[1:]))
         self.Wb = [b[("Wb", l)] for l in range(self.L)]
         self.Wt = [b[("Wt", l)] for l in range(self.L)]
         self.slab = [b[("slab", l)] for l in range(self.L)]
@@ -364,6 +385,9 @@ class MLP:
         if self.adam:
             raise RuntimeError("update_layer: Adam advances once per step and updates every layer in one launch "
                                "(train_step / update_all)")
+        if self.sched:
+            raise RuntimeError("update_layer: a scheduled plan updates every layer in one launch that reads the "
+                               "device rate (train_step / update_all)")
         if self._gpu:
             self.plan.update_layer(l, float(lr), float(alpha), float(scale), bool(from_G), _stream())
             return
@@ -379,6 +403,9 @@ class MLP:
         if self.adam:
             self._adam_update(scale, from_G=True)
             return
+        if self.sched:
+            self._sched_update(alpha, scale, from_G=True)
+            return
         for l in range(self.L):
             self.update_layer(l, lr, alpha, scale, from_G=True)
 
@@ -388,6 +415,22 @@ class MLP:
         ops.adam_update_multi([(self.W32[l], self.V32[l], self.A32[l], self.G[l] if from_G else self.slab[l],
                                 self.Wb[l], self.Wt[l], self.W0f if l == 0 else None) for l in range(self.L)],
                               self.adam_state, scale)
+
+    def _sched_update(self, alpha, scale, from_G=False):
+        """CPU emulation of the plan's BP / BPM step under a schedule: every layer, the state's rate"""
+        ops.sgd_sched_multi([(self.W32[l], self.V32[l], self.G[l] if from_G else self.slab[l], self.Wb[l], self.Wt[l],
+                              self.W0f if l == 0 else None) for l in range(self.L)],
+                            self.lr_state, alpha=alpha, scale=scale, momentum=self.momentum)
+
+    def advance_schedule(self, hist=None, cursor=None):
+        """the first launch of an epoch: the rate of the next epoch into lr_state (and, under Adam,
+        into adam_state), appended to hist at cursor when given (ops.lr_advance)"""
+        if not self.sched:
+            raise RuntimeError("advance_schedule: the model has no lr_schedule")
+        if self._gpu:
+            self.plan.advance_schedule(_p(hist), _p(cursor), hist.shape[0] if hist is not None else 0, _stream())
+        else:
+            ops.lr_advance(self.lr_state, self.adam_state, hist, cursor)
 
     def front(self, X, labels=None, T=None, n_valid=None):
         """fused modes: X -> the deltas (+ the [G1 | G2] block slabs), one launch"""
@@ -444,10 +487,12 @@ class MLP:
             if l > 0:
                 self.backward_layer(l)  # pre-update W_l^T, before layer l's step below
             self.grad_layer(l, X)
-            if not self.adam:
+            if not (self.adam or self.sched):
                 self.update_layer(l, lr, alpha, scale)
         if self.adam:
             self._adam_update(scale)
+        elif self.sched:
+            self._sched_update(alpha, scale)
 
     def predict(self, X, n_valid=None):
         """network outputs [n_valid, n_out] (fp32)."""
@@ -520,7 +565,8 @@ class MLP:
     # ------------------------------------------------------------------ keep the best pass
     def _masters(self):
         m = [t for l in range(self.L) for t in (self.W32[l], self.V32[l], self.A32[l]) if t is not None]
-        return m + ([self.adam_state.view(torch.float32)] if self.adam else [])
+        m += [self.adam_state.view(torch.float32)] if self.adam else []
+        return m + ([self.lr_state.view(torch.float32)] if self.sched else [])
 
     def keep_best(self, metric="loss", patience=0):
         """allocate the best state and the snapshot of the FP32 masters (and the momentum) for

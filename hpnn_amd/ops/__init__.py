@@ -1272,6 +1272,173 @@ def adam_update_multi(layers, state, scale=1.0):
     native().adam_update_multi(desc, float(scale), state.data_ptr(), _stream())
 
 
+# --------------------------------------------------------------------------- [lr_schedule]
+LR_KIND = {"constant": 0, "step": 1, "linear": 2, "plateau": 3}  # HPNN_LR_* (= nn_lr_schedule)
+_LR_D = ("lr0", "gamma", "lr_end", "lr_min", "scale", "best", "lr")  # float64 words 0..6 of hpnn_lr_state
+_LR_U = ("kind", "period", "span", "patience", "warmup", "epoch", "stale", "cuts", "valid")  # uint32 words 14..22
+
+
+def lr_state(kind="constant", lr0=0.01, gamma=0.5, period=10, span=0, lr_end=0.0, lr_min=0.0, patience=2, warmup=0,
+             epoch=0, device="cpu"):
+    """a fresh hpnn_lr_state (include/libhpnn/lrsched.h) as [12] float64 (96 bytes): lr0, gamma,
+    lr_end, lr_min, scale (1), best, lr, then the uint32 words kind, period, span, patience, warmup,
+    epoch (the absolute 0-based index of the next epoch), stale, cuts, valid, pad.  Raises when
+    hpnn_lr_valid refuses the keys."""
+    k = LR_KIND[kind] if isinstance(kind, str) else int(kind)
+    st = torch.zeros(12, dtype=torch.float64)
+    ok = native().lr_host_init(st.data_ptr(), k, float(lr0), float(gamma), int(period), int(span), float(lr_end),
+                               float(lr_min), int(patience), int(warmup), int(epoch))
+    if not ok:
+        raise ValueError("lr_state: lr0 and lr_end finite, 0 < gamma <= 1, period >= 1, lr_min >= 0, span >= 1 for "
+                         "linear, patience >= 1 for plateau")
+    return st.to(device)
+
+
+def lr_valid(state):
+    """hpnn_lr_valid on a state (synchronises)"""
+    return bool(native().lr_host_valid(state.cpu().contiguous().data_ptr()))
+
+
+def read_lr_state(state):
+    """the schedule state as a dict (synchronises); the counters are ints"""
+    s = state.cpu().contiguous()
+    out = {k: float(s[i]) for i, k in enumerate(_LR_D)}
+    u = s.view(torch.int32)
+    out.update({k: int(u[14 + i]) & 0xffffffff for i, k in enumerate(_LR_U)})
+    return out
+
+
+def write_lr_state(state, **kw):
+    """set fields of a schedule state (names of read_lr_state); returns the state"""
+    s = state.cpu().clone()
+    u = s.view(torch.int32)
+    for k, v in kw.items():
+        if k in _LR_U:
+            v = int(v) & 0xffffffff
+            u[14 + _LR_U.index(k)] = v - (1 << 32) if v >= 1 << 31 else v
+        else:
+            s[_LR_D.index(k)] = float(v)
+    state.copy_(s)
+    return state
+
+
+def lr_advance(state, adam=None, hist=None, cursor=None):
+    """the first launch of an epoch: hpnn_lr_advance on the state -- the rate of epoch `epoch` into
+    lr, epoch += 1 -- then, when given, lr appended to hist ([cap] float64) at cursor ([1] int32; a
+    full history drops the record) and stored into the lr word of an Adam state.  One capturable
+    one-thread launch (csrc/gpu/kernels_lrsched.hip); CPU tensors: the host form."""
+    if (hist is None) != (cursor is None):
+        raise ValueError("lr_advance: hist and cursor come together")
+    if _cpu(state):
+        native().lr_host_advance(state.data_ptr())
+        if adam is not None:
+            adam[0] = state[6]
+        if hist is not None:
+            c = int(cursor[0])
+            if c < hist.shape[0]:
+                hist[c] = state[6]
+                cursor[0] = c + 1
+        return state
+    _cg_rc(native().lr_advance(state.data_ptr(), _ptr(adam), _ptr(hist), _ptr(cursor),
+                               hist.shape[0] if hist is not None else 0, _stream()), "lr_advance")
+    return state
+
+
+def lr_plateau(vhist, vcursor, state):
+    """behind validate_commit: hpnn_lr_plateau on the loss sum of the pass just filed
+    (vhist[vcursor - 1]; vcursor == 0: a no-op).  A loss that is not a NaN and < best sets best and
+    zeroes stale, anything else adds one; stale == patience: scale *= gamma, stale = 0, cuts += 1.
+    One capturable one-thread launch; CPU tensors: the host form."""
+    if _cpu(state):
+        c = int(vcursor[0])
+        if c:
+            native().lr_host_plateau(state.data_ptr(), float(vhist[c - 1, 0]))
+        return state
+    _cg_rc(native().lr_plateau(vhist.data_ptr(), vcursor.data_ptr(), state.data_ptr(), _stream()), "lr_plateau")
+    return state
+
+
+class SgdSchedTable:
+    """the segment table of sgd_sched_fp: one segment per layer, a dict of flat (element stride 1)
+    tensors w and (BPM) v of one dtype (float64 / float32) with n elements each and slab: [S, n]
+    with any row stride >= n.  At most 16 segments.  Device tensors: uploaded once (a [n, 7] int64
+    device tensor; the table keeps the tensors alive)."""
+
+    def __init__(self, segs, momentum=False):
+        self.segs = [dict(s) for s in segs]
+        self.momentum = bool(momentum)
+        if not 1 <= len(self.segs) <= 16:
+            raise ValueError("SgdSchedTable: 1..16 segments")
+        w0 = self.segs[0]["w"]
+        self.dtype, self.device = w0.dtype, w0.device
+        if self.dtype not in (torch.float64, torch.float32):
+            raise ValueError("SgdSchedTable: float64 or float32 tensors")
+        self.f64 = int(self.dtype == torch.float64)
+        rows = []
+        for s in self.segs:
+            n, slab = s["w"].numel(), s["slab"]
+            for k in ("w", "v", "slab") if self.momentum else ("w", "slab"):
+                t = s[k]
+                if t.dtype != self.dtype or t.device != self.device or t.stride(-1) != 1:
+                    raise ValueError("SgdSchedTable: one dtype, one device, element stride 1")
+                if (k == "slab" and (t.dim() != 2 or t.shape[1] != n)) or (k != "slab" and t.numel() != n):
+                    raise ValueError("SgdSchedTable: every tensor of a segment has its n elements")
+            if n == 0 or slab.shape[0] < 1 or (slab.shape[0] > 1 and slab.stride(0) < n):
+                raise ValueError("SgdSchedTable: n >= 1, S >= 1, slab row stride >= n")
+            rows.append((_ptr(s["w"]), _ptr(s.get("v")) if self.momentum else 0, _ptr(slab), slab.shape[0],
+                         slab.stride(0) if slab.shape[0] > 1 else n, n))
+        self.dev = None
+        if self.device.type != "cpu":
+            self.dev = torch.zeros(len(rows), 7, dtype=torch.int64, device=self.device)
+            rc = native().sgd_sched_table(self.f64, self.dev.data_ptr(), rows, int(self.momentum), _stream())
+            if rc:
+                raise ValueError(f"sgd_sched_table refused the segments (rc={rc})")
+        self.rows = rows
+
+    def __len__(self):
+        return len(self.segs)
+
+
+def sgd_sched_fp(table, state, scale=1.0, alpha=0.0):
+    """per segment g = (slab[0] + ... + slab[S-1]) * scale in slab order, then the scheduled BP
+    (w += lr g) or BPM (v += lr g; w += v; v *= alpha) step of include/libhpnn/lrsched.h in the
+    tensors' dtype with lr = the state's rate, read when the launch runs: one capturable launch for
+    the whole table (csrc/gpu/kernels_lrsched.hip).  CPU tensors: the host entry point."""
+    if table.dev is None:
+        for r in table.rows:
+            native().sgd_sched_host_update(table.f64, r[0], r[1], r[2], r[3], r[4], r[5], float(scale), float(alpha),
+                                           int(table.momentum), state.data_ptr())
+        return
+    _cg_rc(native().sgd_sched_fp(table.f64, table.dev.data_ptr(), len(table), float(scale), float(alpha),
+                                 int(table.momentum), state.data_ptr(), _stream()), "sgd_sched_fp")
+
+
+def sgd_sched_multi(layers, state, alpha=0.0, scale=1.0, momentum=False):
+    """All layers' BP / BPM steps in one launch with the rate read from the schedule state (the
+    BF16 plan's scheduled update, csrc/gpu/kernels_lrsched.hip).  layers: list of (W32, V32, G, Wbf,
+    Wt, Wf) with the FP32 masters W32 and momentum V32 [N, K] (V32 may be None under BP), G [S, N,
+    K] (or a strided view) or [N, K]; Wf may be None.  More than 8 layers go in groups of 8.  The
+    slabs are summed in the order of adam_slab_sum.  CPU tensors: that sum, then the host entry
+    point of include/libhpnn/lrsched.h and the BF16 copies of the emulation."""
+    if _cpu(layers[0][0]):
+        for W32, V32, G, Wbf, Wt, Wf in layers:
+            g = adam_slab_sum(G.float()).contiguous()
+            if not (W32.is_contiguous() and (V32 is None or V32.is_contiguous())):
+                raise ValueError("sgd_sched_multi: contiguous W32, V32")
+            native().sgd_sched_host_update(0, W32.data_ptr(), _ptr(V32), g.data_ptr(), 1, 0, W32.numel(),
+                                           float(scale), float(alpha), int(bool(momentum)), state.data_ptr())
+            cast_weights(W32, Wbf, Wt, Wf)
+        return
+    desc = []
+    for W32, V32, G, Wbf, Wt, Wf in layers:
+        N, K = W32.shape
+        S = G.shape[0] if G.dim() == 3 else 1
+        gstride = G.stride(0) if G.dim() == 3 else 0
+        desc.append((W32.data_ptr(), _ptr(V32), G.data_ptr(), gstride, Wbf.data_ptr(), Wt.data_ptr(), _ptr(Wf), S,
+                     N, K))
+    native().sgd_sched_multi(desc, float(alpha), float(scale), int(bool(momentum)), state.data_ptr(), _stream())
+
+
 # --------------------------------------------------------------------------- online FP64 engine
 ONLINE_VARIANTS = ("lds", "global", "coop")
 

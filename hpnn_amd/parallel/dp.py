@@ -51,6 +51,9 @@ class DataParallel:
         if getattr(model, "adam", False):
             raise ValueError("DataParallel: optimizer='adam' trains on one device only (its moments and step "
                              "count live beside one device's masters); use one GPU or optimizer='sgd'")
+        if getattr(model, "sched", False):
+            raise ValueError("DataParallel: lr_schedule trains on one device only (its rate lives in one device's "
+                             "memory); use one GPU (MLP alone) or pass the rate of every step yourself")
         self.m = model
         self.group = group
         self.active = dist.is_initialized()

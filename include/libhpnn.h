@@ -13,6 +13,7 @@
 #include <libhpnn/common.h>
 #include <libhpnn/cg.h>
 #include <libhpnn/adam.h>
+#include <libhpnn/lrsched.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -112,6 +113,17 @@ typedef enum {
     NN_KEEP_ACC = 2,  /* those of the pass with the most hits (the loss breaks ties) */
 } nn_keep_best;
 
+/* [lr_schedule]: the learning rate of every epoch of batched training on one device
+ * (<libhpnn/lrsched.h>; the values are HPNN_LR_*) */
+typedef enum {
+    NN_LR_NONE = -1,    /* not set: [lr] for the whole call */
+    NN_LR_CONSTANT = 0, /* [lr] (with [warmup]: the ramp, then [lr]) */
+    NN_LR_STEP = 1,     /* [lr] * [lr_gamma]^(epoch / [lr_period]) */
+    NN_LR_LINEAR = 2,   /* from [lr] to [lr_end] over [lr_span] epochs, then [lr_end] */
+    NN_LR_PLATEAU = 3,  /* * [lr_gamma] after [lr_patience] validation passes without a smaller loss,
+                         * not below [lr_min] (needs [validate]) */
+} nn_lr_schedule;
+
 typedef struct {
     nn_runtime *rr;  /* link to the runtime parameters */
     CHAR *name;
@@ -160,6 +172,14 @@ typedef struct {
     void *cg_history;
     /* -- [train] ADAM: [beta1], [beta2], [epsilon], [decay]; a NaN: not set (0.9, 0.999, 1e-8, 0) -- */
     DOUBLE beta1, beta2, epsilon, decay;
+    /* -- [lr_schedule] constant | step | linear | plateau with [lr_gamma], [lr_period], [lr_span],
+     *    [lr_end], [lr_min], [lr_patience], [warmup] (<libhpnn/lrsched.h>); NN_LR_NONE, a NaN and 0:
+     *    not set; the rate of every epoch of the last nn_train_kernel call (nn_get_lr_history) -- */
+    nn_lr_schedule lr_schedule;
+    DOUBLE lr_gamma, lr_end, lr_min;
+    UINT lr_period, lr_span, lr_patience, warmup;
+    UINT n_lr_history;
+    DOUBLE *lr_history;
 } nn_def;
 
 #define _NN(a, b) nn_##a##_##b
@@ -341,6 +361,22 @@ const hpnn_cg_record *_NN(get, cg_history)(nn_def *conf, UINT *n);
  * the state file (nn_dump_state / nn_load_state), not across two calls in one process */
 void _NN(set, adam)(nn_def *conf, DOUBLE beta1, DOUBLE beta2, DOUBLE epsilon, DOUBLE decay);
 void _NN(get, adam)(nn_def *conf, DOUBLE *beta1, DOUBLE *beta2, DOUBLE *epsilon, DOUBLE *decay);
+/* [lr_schedule] (batched mode, one device, BP / BPM / ADAM): the rate of epoch e (absolute, 0-based)
+ * is a function of e and, for plateau, of the validation losses (<libhpnn/lrsched.h>); [warmup] W
+ * multiplies the first W epochs' rates by (e + 1) / W and composes with every kind (alone it
+ * schedules a constant rate).  There is no cosine form: the rule uses only operations that are
+ * correctly rounded on the host and on the device.  nn_set_lr_schedule: a NaN gamma / lr_end /
+ * lr_min and a 0 period / span / patience unset that key (defaults 0.5, 0, 0, 10, none, 2);
+ * nn_get_lr_schedule returns the values a training call would use (any pointer may be NULL).
+ * step and linear continue through nn_load_state with nothing stored; plateau's running state
+ * persists through the state file, not across two calls in one process.  nn_train_kernel prints
+ * "LR: epoch E lr=X" per epoch at -vv; nn_get_lr_history returns the rates of the last call (owned
+ * by conf; *n = their number, NULL when there is none) */
+void _NN(set, lr_schedule)(nn_def *conf, nn_lr_schedule kind, DOUBLE gamma, UINT period, UINT span, DOUBLE lr_end,
+                           DOUBLE lr_min, UINT patience, UINT warmup);
+void _NN(get, lr_schedule)(nn_def *conf, nn_lr_schedule *kind, DOUBLE *gamma, UINT *period, UINT *span,
+                           DOUBLE *lr_end, DOUBLE *lr_min, UINT *patience, UINT *warmup);
+const DOUBLE *_NN(get, lr_history)(nn_def *conf, UINT *n);
 /* the [shuffle] epoch permutation (libhpnn/shuffle.h): out[i] = index, in the order drawn once
  * from [seed], of the sample at position i of epoch `epoch` (epochs completed before it) */
 void hpnn_epoch_perm(UINT n, UINT seed, UINT epoch, UINT *out);

@@ -40,6 +40,11 @@ typedef struct {
     DOUBLE **dv;
     UINT64 adam_t;
     DOUBLE adam_p1, adam_p2;
+    /* [lr_schedule] plateau: the running fields of <libhpnn/lrsched.h> as the last batched call left
+     * them (nn_dump_state saves them); lr_loaded: nn_load_state filled them and the next call
+     * starts from them */
+    DOUBLE lr_scale, lr_best;
+    UINT lr_stale, lr_cuts, lr_valid, lr_loaded;
 } kernel_ann;
 
 /* allocation / I/O (reference ann.c:113-879) */

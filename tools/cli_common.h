@@ -14,6 +14,8 @@
  *   the last one (same as [validate] N),
  *   -K loss|acc (train_nn only) return the state of the best validation pass (same as
  *   [keep_best]), -P P (train_nn only) stop after P passes without improvement ([patience] P),
+ *   -L constant|step|linear|plateau (train_nn only) the learning-rate schedule of batched
+ *   training (same as [lr_schedule]; its other keys come from the conf),
  *   -r FILE exact-resume state (loaded when present, written after training),
  *   -M FILE JSON-lines metrics (same as HPNN_METRICS=FILE),
  *   -T trace ranges + timing table (same as HPNN_TRACE=1).
@@ -37,6 +39,7 @@ typedef struct {
     unsigned validate; /* -V N */
     int keep_best;     /* -K loss|acc */
     unsigned patience; /* -P P */
+    int lr_schedule;   /* -L kind; -1 = from conf */
     double lr, alpha;
     const char *state;   /* -r */
     const char *metrics; /* -M */
@@ -49,6 +52,7 @@ static int cli_parse(int argc, char **argv, cli_opts *o, int allow_x) {
     o->conf = "./nn.conf";
     o->mode = -1;
     o->dtype = -1;
+    o->lr_schedule = -1;
     o->lr = -1.0;
     o->alpha = -1.0;
     for (int i = 1; i < argc; i++) {
@@ -88,7 +92,7 @@ static int cli_parse(int argc, char **argv, cli_opts *o, int allow_x) {
                 j++;
                 continue;
             }
-            if (strchr("OBSGbemdlarM", c) || (strchr("VKP", c) && allow_x)) {
+            if (strchr("OBSGbemdlarM", c) || (strchr("VKPL", c) && allow_x)) {
                 const char *val = a[j + 1] ? &a[j + 1] : (i + 1 < argc ? argv[++i] : NULL);
                 if (!val) {
                     _OUT(stderr, "syntax error: missing -%c parameter!\n", c);
@@ -114,6 +118,14 @@ static int cli_parse(int argc, char **argv, cli_opts *o, int allow_x) {
                     o->keep_best = !strcmp(val, "loss") ? NN_KEEP_LOSS : (!strcmp(val, "acc") ? NN_KEEP_ACC : -1);
                     if (o->keep_best < 0) {
                         _OUT(stderr, "syntax error: bad -K parameter (loss | acc)!\n");
+                        return -1;
+                    }
+                } else if (c == 'L') {
+                    static const char *kinds[] = {"constant", "step", "linear", "plateau"};
+                    for (int q = 0; q < 4; q++)
+                        if (!strcmp(val, kinds[q])) o->lr_schedule = q;
+                    if (o->lr_schedule < 0) {
+                        _OUT(stderr, "syntax error: bad -L parameter (constant | step | linear | plateau)!\n");
                         return -1;
                     }
                 } else if (c == 'm') {
@@ -157,6 +169,7 @@ static void cli_apply_conf(const cli_opts *o, nn_def *conf) {
     if (o->validate) _NN(set, validate)(conf, o->validate);
     if (o->keep_best) _NN(set, keep_best)(conf, (nn_keep_best)o->keep_best);
     if (o->patience) _NN(set, patience)(conf, o->patience);
+    if (o->lr_schedule >= 0) conf->lr_schedule = (nn_lr_schedule)o->lr_schedule; /* the other keys: the conf's */
     if (o->lr > 0) _NN(set, learning_rate)(conf, o->lr);
     if (o->alpha >= 0) _NN(set, momentum)(conf, o->alpha);
 }
