@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../gpu/engine.h"
+#include "upd_host.h"
 
 extern "C" void hpnn_adam_host_init(hpnn_adam_state *s, double lr, double beta1, double beta2, double eps,
                                     double decay) {
@@ -23,23 +24,14 @@ extern "C" void hpnn_adam_host_update(int f64, void *W, void *M, void *V, const 
                                       double scale, const hpnn_adam_state *s) {
     if (f64) {
         const hpnn_adam_coef_f64 c = hpnn_adam_coef_f64_of(s);
-        double *w = (double *)W, *m = (double *)M, *v = (double *)V;
-        const double *g = (const double *)G;
-        for (long i = 0; i < n; i++) {
-            double a = 0.0;
-            for (int k = 0; k < S; k++) a += g[(size_t)k * gstride + i];
-            hpnn_adam_elem_f64(&c, a * scale, w + i, m + i, v + i);
-        }
+        double *const mv[2] = {(double *)M, (double *)V};
+        hpnn_host_slab_update((double *)W, mv, true, (const double *)G, S, gstride, n, scale,
+                              [&c](double g, double *w, double *e) { hpnn_adam_elem_f64(&c, g, w, e, e + 1); });
     } else {
         const hpnn_adam_coef_f32 c = hpnn_adam_coef_f32_of(s);
-        float *w = (float *)W, *m = (float *)M, *v = (float *)V;
-        const float *g = (const float *)G;
-        const float sc = (float)scale;
-        for (long i = 0; i < n; i++) {
-            float a = 0.f;
-            for (int k = 0; k < S; k++) a += g[(size_t)k * gstride + i];
-            hpnn_adam_elem_f32(&c, a * sc, w + i, m + i, v + i);
-        }
+        float *const mv[2] = {(float *)M, (float *)V};
+        hpnn_host_slab_update((float *)W, mv, true, (const float *)G, S, gstride, n, (float)scale,
+                              [&c](float g, float *w, float *e) { hpnn_adam_elem_f32(&c, g, w, e, e + 1); });
     }
 }
 

@@ -7,6 +7,7 @@
 #include <stddef.h>
 
 #include "../gpu/engine.h"
+#include "upd_host.h"
 
 extern "C" int hpnn_lr_host_init(hpnn_lr_state *s, unsigned int kind, double lr0, double gamma, unsigned int period,
                                  unsigned int span, double lr_end, double lr_min, unsigned int patience,
@@ -25,24 +26,14 @@ extern "C" void hpnn_sgd_sched_host_update(int f64, void *W, void *V, const void
                                            double scale, double alpha, int momentum, const hpnn_lr_state *s) {
     const int mom = momentum && V;
     if (f64) {
-        double *w = (double *)W, *v = (double *)V;
-        const double *g = (const double *)G;
         const double lr = s->lr;
-        for (long i = 0; i < n; i++) {
-            double a = 0.0, p = mom ? v[i] : 0.0;
-            for (int k = 0; k < S; k++) a += g[(size_t)k * gstride + i];
-            hpnn_sgd_sched_elem_f64(lr, alpha, mom, a * scale, w + i, &p);
-            if (mom) v[i] = p;
-        }
+        double *const v[1] = {(double *)V};
+        auto elem = [=](double g, double *w, double *e) { hpnn_sgd_sched_elem_f64(lr, alpha, mom, g, w, e); };
+        hpnn_host_slab_update((double *)W, v, mom, (const double *)G, S, gstride, n, scale, elem);
     } else {
-        float *w = (float *)W, *v = (float *)V;
-        const float *g = (const float *)G;
-        const float lr = (float)s->lr, al = (float)alpha, sc = (float)scale;
-        for (long i = 0; i < n; i++) {
-            float a = 0.f, p = mom ? v[i] : 0.f;
-            for (int k = 0; k < S; k++) a += g[(size_t)k * gstride + i];
-            hpnn_sgd_sched_elem_f32(lr, al, mom, a * sc, w + i, &p);
-            if (mom) v[i] = p;
-        }
+        const float lr = (float)s->lr, al = (float)alpha;
+        float *const v[1] = {(float *)V};
+        auto elem = [=](float g, float *w, float *e) { hpnn_sgd_sched_elem_f32(lr, al, mom, g, w, e); };
+        hpnn_host_slab_update((float *)W, v, mom, (const float *)G, S, gstride, n, (float)scale, elem);
     }
 }

@@ -445,7 +445,7 @@ int hpnn_adam_fp(int f64, const hpnn_adam_seg *segs, int n_segs, double scale, c
                  hipStream_t stream);
 /* the BF16 plan's update, every layer (n <= HPNN_UPD_MAX) in one launch: the layer descriptor
  * of hpnn_sgd_update_multi (V32 = the first moment) plus the second moment A32.  g = scale * the
- * S slabs summed in the kernel's one fixed order (kernels_adam.hip), the rule of adam.h in FP32,
+ * S slabs summed in the kernel's one fixed order (upd_common.h), the rule of adam.h in FP32,
  * then BF16 W, W^T and Wf exactly where hpnn_sgd_update_multi writes them */
 typedef struct {
     hpnn_upd_layer u;

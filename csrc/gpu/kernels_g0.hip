@@ -41,6 +41,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "frag_major.h"
 #include "kernels.h"
 
 HPNN_CO_PROBE(g0)
@@ -286,9 +287,8 @@ __device__ __forceinline__ void step_elem4(float *W32, float *V32, __bf16 *Wb, _
 #pragma unroll
     for (int r = 0; r < 4; r++) wb[r] = (__bf16)w[r];
     *(bf16x4 *)(Wb + idx) = wb;
-    if (Wf) { /* MFMA-fragment-major copy (kernels.h): 4 consecutive k stay contiguous */
-        const size_t fo = (((size_t)(n >> 4) * (K / 32) + (k >> 5)) * 64 + (n & 15) + 16 * ((k >> 3) & 3)) * 8 + (k & 7);
-        *(bf16x4 *)(Wf + fo) = wb;
+    if (Wf) { /* MFMA-fragment-major copy (frag_major.h): 4 consecutive k stay contiguous */
+        *(bf16x4 *)(Wf + hpnn_frag_major_offset(n, k, K)) = wb;
     }
     if (!G0_PROTO(u, 2048)) /* 2048: timing ablation, no W^T stores */
 #pragma unroll

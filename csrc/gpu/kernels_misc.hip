@@ -45,6 +45,7 @@
 #include <mutex>
 #include <tuple>
 
+#include "frag_major.h"
 #include "kernels.h"
 
 HPNN_CO_PROBE(misc)
@@ -394,9 +395,8 @@ __device__ __forceinline__ void sgd_tile(float *__restrict__ W32, float *__restr
     }
     *(bf16x4 *)(Wbf + idx) = wb;
     if (Wf) {
-        /* MFMA-fragment-major copy (kernels.h): 4 consecutive k stay contiguous */
-        const size_t fo = (((size_t)(n >> 4) * tiles_k + (k >> 5)) * 64 + (n & 15) + 16 * ((k >> 3) & 3)) * 8 + (k & 7);
-        *(bf16x4 *)(Wf + fo) = wb;
+        /* MFMA-fragment-major copy (frag_major.h): 4 consecutive k stay contiguous */
+        *(bf16x4 *)(Wf + hpnn_frag_major_offset(n, k, K)) = wb;
     }
     __syncthreads();
     /* transposed: thread writes Wt[k = tk*32 + ty][n = tn*32 + 4tx .. +3] */
@@ -506,10 +506,7 @@ __global__ __launch_bounds__(512) void sgd_update_multi_sub_kernel(UpdArgs a) {
             tilebuf[ty][tx * 4 + r] = wv[r];
         }
         *(bf16x4 *)((__bf16 *)L.Wbf + idx) = wb;
-        if (L.Wf) {
-            const size_t fo = (((size_t)(n >> 4) * tiles_k + (k >> 5)) * 64 + (n & 15) + 16 * ((k >> 3) & 3)) * 8 + (k & 7);
-            *(bf16x4 *)((__bf16 *)L.Wf + fo) = wb;
-        }
+        if (L.Wf) *(bf16x4 *)((__bf16 *)L.Wf + hpnn_frag_major_offset(n, k, L.K)) = wb;
     }
     __syncthreads();
     if (w == 0) {

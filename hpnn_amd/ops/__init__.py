@@ -1175,44 +1175,64 @@ def adam_advance(state):
     return state
 
 
-class AdamTable:
-    """the segment table of adam_update_fp: one segment per layer, a dict of flat (element stride
-    1) tensors w, m, v of one dtype (float64 / float32) with n elements each and slab: [S, n] with
-    any row stride >= n.  At most 16 segments.  Device tensors: uploaded once (a [n, 8] int64
-    device tensor; the table keeps the tensors alive)."""
+class _SegTable:
+    """a segment table of the update kernels (csrc/gpu/upd_common.h): one segment per layer, a dict
+    of flat (element stride 1) tensors w and the state arrays `keys` of one dtype (float64 /
+    float32) with n elements each and slab: [S, n] with any row stride >= n.  At most 16 segments.
+    A row is (w, the state pointers, slab, S, slab row stride, n); a state array outside `_used()`
+    is not looked at and its pointer is 0.  Device tensors: uploaded once by the native `entry` (a
+    [n, width] int64 device tensor; the table keeps the tensors alive)."""
+
+    name, keys, width, entry = None, (), 0, None
+
+    def _used(self):
+        """the state arrays this table's launches use"""
+        return self.keys
+
+    def _extra(self):
+        """what the native `entry` takes between the rows and the stream"""
+        return ()
 
     def __init__(self, segs):
+        name, used = self.name, self._used()
         self.segs = [dict(s) for s in segs]
         if not 1 <= len(self.segs) <= 16:
-            raise ValueError("AdamTable: 1..16 segments")
+            raise ValueError(f"{name}: 1..16 segments")
         w0 = self.segs[0]["w"]
         self.dtype, self.device = w0.dtype, w0.device
         if self.dtype not in (torch.float64, torch.float32):
-            raise ValueError("AdamTable: float64 or float32 tensors")
+            raise ValueError(f"{name}: float64 or float32 tensors")
         self.f64 = int(self.dtype == torch.float64)
         rows = []
         for s in self.segs:
             n, slab = s["w"].numel(), s["slab"]
-            for k in ("w", "m", "v", "slab"):
+            for k in ("w",) + used + ("slab",):
                 t = s[k]
                 if t.dtype != self.dtype or t.device != self.device or t.stride(-1) != 1:
-                    raise ValueError("AdamTable: one dtype, one device, element stride 1")
+                    raise ValueError(f"{name}: one dtype, one device, element stride 1")
                 if (k == "slab" and (t.dim() != 2 or t.shape[1] != n)) or (k != "slab" and t.numel() != n):
-                    raise ValueError("AdamTable: every tensor of a segment has its n elements")
+                    raise ValueError(f"{name}: every tensor of a segment has its n elements")
             if n == 0 or slab.shape[0] < 1 or (slab.shape[0] > 1 and slab.stride(0) < n):
-                raise ValueError("AdamTable: n >= 1, S >= 1, slab row stride >= n")
-            rows.append((_ptr(s["w"]), _ptr(s["m"]), _ptr(s["v"]), _ptr(slab), slab.shape[0],
-                         slab.stride(0) if slab.shape[0] > 1 else n, n))
+                raise ValueError(f"{name}: n >= 1, S >= 1, slab row stride >= n")
+            rows.append((_ptr(s["w"]),) + tuple(_ptr(s.get(k)) if k in used else 0 for k in self.keys) +
+                        (_ptr(slab), slab.shape[0], slab.stride(0) if slab.shape[0] > 1 else n, n))
         self.dev = None
         if self.device.type != "cpu":
-            self.dev = torch.zeros(len(rows), 8, dtype=torch.int64, device=self.device)
-            rc = native().adam_table(self.f64, self.dev.data_ptr(), rows, _stream())
+            self.dev = torch.zeros(len(rows), self.width, dtype=torch.int64, device=self.device)
+            rc = getattr(native(), self.entry)(self.f64, self.dev.data_ptr(), rows, *self._extra(), _stream())
             if rc:
-                raise ValueError(f"adam_table refused the segments (rc={rc})")
+                raise ValueError(f"{self.entry} refused the segments (rc={rc})")
         self.rows = rows
 
     def __len__(self):
         return len(self.segs)
+
+
+class AdamTable(_SegTable):
+    """the segment table of adam_update_fp: per segment w, m, v and slab; on a device a [n, 8]
+    int64 tensor"""
+
+    name, keys, width, entry = "AdamTable", ("m", "v"), 8, "adam_table"
 
 
 def adam_update_fp(table, state, scale=1.0):
@@ -1230,8 +1250,8 @@ def adam_update_fp(table, state, scale=1.0):
 
 
 def adam_slab_sum(G):
-    """the slab sum of adam_update_multi in the kernel's one fixed order (kernels_adam.hip): p_w =
-    the slabs w, w + 8, ... added in that order to 0, then ((p_0 + p_1) + ...) + p_7; FP32"""
+    """the slab sum of adam_update_multi in the kernel's one fixed order (csrc/gpu/upd_common.h):
+    p_w = the slabs w, w + 8, ... added in that order to 0, then ((p_0 + p_1) + ...) + p_7; FP32"""
     if G.dim() == 2:
         G = G.unsqueeze(0)
     parts = []
@@ -1358,45 +1378,21 @@ def lr_plateau(vhist, vcursor, state):
     return state
 
 
-class SgdSchedTable:
-    """the segment table of sgd_sched_fp: one segment per layer, a dict of flat (element stride 1)
-    tensors w and (BPM) v of one dtype (float64 / float32) with n elements each and slab: [S, n]
-    with any row stride >= n.  At most 16 segments.  Device tensors: uploaded once (a [n, 7] int64
-    device tensor; the table keeps the tensors alive)."""
+class SgdSchedTable(_SegTable):
+    """the segment table of sgd_sched_fp: per segment w, (BPM) v and slab; on a device a [n, 7]
+    int64 tensor"""
+
+    name, keys, width, entry = "SgdSchedTable", ("v",), 7, "sgd_sched_table"
 
     def __init__(self, segs, momentum=False):
-        self.segs = [dict(s) for s in segs]
         self.momentum = bool(momentum)
-        if not 1 <= len(self.segs) <= 16:
-            raise ValueError("SgdSchedTable: 1..16 segments")
-        w0 = self.segs[0]["w"]
-        self.dtype, self.device = w0.dtype, w0.device
-        if self.dtype not in (torch.float64, torch.float32):
-            raise ValueError("SgdSchedTable: float64 or float32 tensors")
-        self.f64 = int(self.dtype == torch.float64)
-        rows = []
-        for s in self.segs:
-            n, slab = s["w"].numel(), s["slab"]
-            for k in ("w", "v", "slab") if self.momentum else ("w", "slab"):
-                t = s[k]
-                if t.dtype != self.dtype or t.device != self.device or t.stride(-1) != 1:
-                    raise ValueError("SgdSchedTable: one dtype, one device, element stride 1")
-                if (k == "slab" and (t.dim() != 2 or t.shape[1] != n)) or (k != "slab" and t.numel() != n):
-                    raise ValueError("SgdSchedTable: every tensor of a segment has its n elements")
-            if n == 0 or slab.shape[0] < 1 or (slab.shape[0] > 1 and slab.stride(0) < n):
-                raise ValueError("SgdSchedTable: n >= 1, S >= 1, slab row stride >= n")
-            rows.append((_ptr(s["w"]), _ptr(s.get("v")) if self.momentum else 0, _ptr(slab), slab.shape[0],
-                         slab.stride(0) if slab.shape[0] > 1 else n, n))
-        self.dev = None
-        if self.device.type != "cpu":
-            self.dev = torch.zeros(len(rows), 7, dtype=torch.int64, device=self.device)
-            rc = native().sgd_sched_table(self.f64, self.dev.data_ptr(), rows, int(self.momentum), _stream())
-            if rc:
-                raise ValueError(f"sgd_sched_table refused the segments (rc={rc})")
-        self.rows = rows
+        super().__init__(segs)
 
-    def __len__(self):
-        return len(self.segs)
+    def _used(self):
+        return self.keys if self.momentum else ()
+
+    def _extra(self):
+        return (int(self.momentum),)
 
 
 def sgd_sched_fp(table, state, scale=1.0, alpha=0.0):

@@ -1,7 +1,8 @@
 """[train] ADAM on the GPU: the kernels of csrc/gpu/kernels_adam.hip against the rounding bounds of
-tests/adam_common.py (derived there), the state read at run time inside a captured graph, the
-f64 / f32 engines against the FP64 CPU oracle, the BF16 plan against the FP64 reference and,
-bit for bit, against train_nn, exact resume, [keep_best], the refusals, and BP / BPM untouched.
+tests/adam_common.py (derived there) and bit for bit against the host form, the state read at run
+time inside a captured graph, the f64 / f32 engines against the FP64 CPU oracle, the BF16 plan
+against the FP64 reference and, bit for bit, against train_nn, exact resume, [keep_best], the
+refusals, and BP / BPM untouched.
 
 Every case prints what it measured."""
 import math
@@ -16,23 +17,13 @@ from hpnn_amd import capi, ops
 from hpnn_amd.models import MLP, reference
 from hpnn_amd.utils import formats
 from tests import adam_common as A
+from tests import upd_common as U
 
 DTYPES = [torch.float64, torch.float32]
 IDS = ["f64", "f32"]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "bin")
 BIG = 1_048_576 + 3  # the smallest n that enters the grid-stride loop (4096 x 256 elements per pass)
-
-
-def _ibits(t):
-    return t.view(torch.int64 if t.dtype == torch.float64 else torch.int32)
-
-
-def _window(values, off, tail=3):
-    """values inside a NaN-filled buffer, `off` elements from its start"""
-    base = torch.full((off + values.numel() + tail,), float("nan"), dtype=values.dtype)
-    base[off:off + values.numel()] = values
-    return base, base[off:off + values.numel()]
 
 
 def _segment(n, S, off, dtype, seed):
@@ -51,27 +42,16 @@ def _segment(n, S, off, dtype, seed):
     if n > 9:
         sl[0, 5:9] = 1e30 if dtype == torch.float32 else 1e200
         sl[1:, 5:9] = 0.0
-    gs = n + 3
-    sbase = torch.full((off + S * gs + 1,), float("nan"), dtype=dtype)
-    slab = sbase[off:off + S * gs].view(S, gs)[:, :n]
-    slab.copy_(sl)
-    seg, bases = {"slab": slab}, {"slab": sbase}
+    seg, bases = {}, {}
+    bases["slab"], seg["slab"] = U.slab_window(sl, off)
     for k, t in (("w", w), ("m", m), ("v", v)):
-        bases[k], seg[k] = _window(t, off)
+        bases[k], seg[k] = U.window(t, off)
     return seg, bases
 
 
-def _to_cuda(seg, bases):
-    dev, dbase = {}, {}
-    for k, t in seg.items():
-        dbase[k] = bases[k].cuda()
-        dev[k] = dbase[k].as_strided(t.shape, t.stride(), t.storage_offset())
-    return dev, dbase
-
-
 def _run_fp(sizes, S, off, dtype, t, decay, seed):
-    """the kernel on `sizes` segments in one launch; checks bounds, padding, repeatability; returns
-    the worst error / bound ratios and whether the bits equal the host form's"""
+    """the kernel on `sizes` segments in one launch; checks bounds, padding, repeatability and that
+    every bit equals the host form's; returns the worst error / bound ratios and that equality"""
     cpu = [_segment(n, S, off, dtype, seed + i) for i, n in enumerate(sizes)]
     st = ops.adam_state(lr=0.01, decay=decay)
     for _ in range(t):
@@ -80,30 +60,32 @@ def _run_fp(sizes, S, off, dtype, t, decay, seed):
     assert sd["t"] == t
     runs = []
     for _ in range(2):
-        dev = [_to_cuda(seg, bases) for seg, bases in cpu]
+        dev = [U.to_cuda(seg, bases) for seg, bases in cpu]
         ops.adam_update_fp(ops.AdamTable([d for d, _ in dev]), st.cuda(), 1.0 / 7)
         torch.cuda.synchronize()
         runs.append(dev)
     worst, same_as_host = [0.0, 0.0, 0.0], True
     for (seg, bases), (d1, b1), (d2, b2) in zip(cpu, runs[0], runs[1]):
         for k in ("w", "m", "v", "slab"):
-            assert torch.equal(_ibits(b1[k].cpu()), _ibits(b2[k].cpu())), "two runs differ"
+            assert torch.equal(U.ibits(b1[k].cpu()), U.ibits(b2[k].cpu())), "two runs differ"
             # everything outside the windows (NaN padding, the gaps between slabs) is untouched
             mask = torch.ones_like(bases[k], dtype=torch.bool)
             mask.as_strided(seg[k].shape, seg[k].stride(), seg[k].storage_offset()).fill_(False)
-            assert torch.equal(_ibits(b1[k].cpu())[mask], _ibits(bases[k])[mask]), f"{k}: padding written"
-        assert torch.equal(_ibits(d1["slab"].cpu()), _ibits(seg["slab"])), "the slabs are read only"
+            assert torch.equal(U.ibits(b1[k].cpu())[mask], U.ibits(bases[k])[mask]), f"{k}: padding written"
+        assert torch.equal(U.ibits(d1["slab"].cpu()), U.ibits(seg["slab"])), "the slabs are read only"
         w1, m1, v1 = d1["w"].cpu(), d1["m"].cpu(), d1["v"].cpu()
         r = A.check_update(seg["w"], seg["m"], seg["v"], seg["slab"], 1.0 / 7, sd, w1, m1, v1, dtype,
                            f"n {seg['w'].numel()} S {S} off {off} t {t}")
         worst = [max(a, b) for a, b in zip(worst, r)]
         if decay == 0.0:  # g = 0, m = v = 0: not a bit changes
-            assert torch.equal(_ibits(w1[:5]), _ibits(seg["w"][:5])) and not m1[:5].any() and not v1[:5].any()
+            assert torch.equal(U.ibits(w1[:5]), U.ibits(seg["w"][:5])) and not m1[:5].any() and not v1[:5].any()
             if seg["w"].numel() > 9:  # g^2 overflows: v = inf, the step is 0
-                assert torch.isinf(v1[5:9]).all() and torch.equal(_ibits(w1[5:9]), _ibits(seg["w"][5:9]))
+                assert torch.isinf(v1[5:9]).all() and torch.equal(U.ibits(w1[5:9]), U.ibits(seg["w"][5:9]))
         hw, hm, hv = seg["w"].clone(), seg["m"].clone(), seg["v"].clone()
         ops.adam_update_fp(ops.AdamTable([dict(w=hw, m=hm, v=hv, slab=seg["slab"])]), st, 1.0 / 7)
-        same_as_host &= all(torch.equal(_ibits(a), _ibits(b)) for a, b in ((hw, w1), (hm, m1), (hv, v1)))
+        same = all(torch.equal(U.ibits(a), U.ibits(b)) for a, b in ((hw, w1), (hm, m1), (hv, v1)))
+        assert same, f"n {seg['w'].numel()} S {S} off {off} t {t} {dtype}: the bits differ from the host form's"
+        same_as_host &= same
     return worst, same_as_host
 
 
@@ -177,13 +159,7 @@ def _run_multi(names, S, seed):
     cpu = [_multi_layer(*LAYERS[n][:2], S, LAYERS[n][2], seed + i) for i, n in enumerate(names)]
     outs = []
     for _ in range(2):
-        dev = []
-        for c in cpu:
-            N, K = c["W"].shape
-            dev.append((c["W"].cuda(), c["M"].cuda(), c["V"].cuda(), c["G"].cuda(),
-                        torch.full((N, K), 7.0, dtype=torch.bfloat16, device="cuda"),
-                        torch.full((K, N), 7.0, dtype=torch.bfloat16, device="cuda"),
-                        torch.full((N * K,), 7.0, dtype=torch.bfloat16, device="cuda") if c["frag"] else None))
+        dev = [U.multi_dev(c, ("M", "V")) for c in cpu]
         ops.adam_update_multi(dev, st.cuda(), 1.0 / 5)
         torch.cuda.synchronize()
         outs.append(dev)
@@ -202,10 +178,11 @@ def _run_multi(names, S, seed):
         if c["frag"]:
             assert torch.equal(Wf, ops.frag_major(Wb))  # the layout of hpnn_sgd_update_multi's Wf
         assert not W1[-3:].any() and not M1[-3:].any() and not V1[-3:].any()  # g = 0 rows stay exactly 0
-        # the documented summation order, through the host form: the same bits or not, reported
+        # the documented summation order, through the host form: the same bits
         hw, hm, hv = c["W"].clone(), c["M"].clone(), c["V"].clone()
         ops.adam_update_multi([(hw, hm, hv, c["G"], torch.empty_like(Wb), torch.empty_like(Wt), None)], st, 1.0 / 5)
         c["host"] = torch.equal(hw, W1) and torch.equal(hm, M1) and torch.equal(hv, V1)
+        assert c["host"], f"{tuple(c['W'].shape)} S {S}: the bits differ from the host form's in the kernel's order"
     return worst, all(c["host"] for c in cpu)
 
 
@@ -223,12 +200,12 @@ def test_adam_update_multi_within_the_bounds(gpu, names, S):
 @pytest.mark.gpu
 def test_a_captured_step_reads_its_state_when_it_runs(gpu):
     seg, bases = _segment(257, 3, 1, torch.float32, 5)
-    dev, _ = _to_cuda(seg, bases)
-    eag, _ = _to_cuda(seg, bases)
+    dev, _ = U.to_cuda(seg, bases)
+    eag, _ = U.to_cuda(seg, bases)
     td, te = ops.AdamTable([dev]), ops.AdamTable([eag])
     sd = ops.adam_state(lr=0.01).cuda()
     se = ops.adam_state(lr=0.01).cuda()
-    warm, _ = _to_cuda(seg, bases)
+    warm, _ = U.to_cuda(seg, bases)
     sw = ops.adam_state(lr=0.01).cuda()
     ops.adam_advance(sw)  # loads the code object before the capture
     ops.adam_update_fp(ops.AdamTable([warm]), sw, 0.5)
@@ -249,7 +226,7 @@ def test_a_captured_step_reads_its_state_when_it_runs(gpu):
     got = ops.read_adam_state(sd)
     assert got == ops.read_adam_state(host) and got["t"] == 5  # p1, p2, c1, s2 equal as floats: the same bits
     for k in ("w", "m", "v"):
-        assert torch.equal(_ibits(dev[k].cpu()), _ibits(eag[k].cpu())), k
+        assert torch.equal(U.ibits(dev[k].cpu()), U.ibits(eag[k].cpu())), k
     # a new lr in the device state: the next replay must use it
     for s in (sd, se):
         ops.write_adam_state(s, lr=0.5)
@@ -258,7 +235,7 @@ def test_a_captured_step_reads_its_state_when_it_runs(gpu):
     ops.adam_advance(se)
     ops.adam_update_fp(te, se, 0.5)
     torch.cuda.synchronize()
-    assert torch.equal(_ibits(dev["w"].cpu()), _ibits(eag["w"].cpu()))
+    assert torch.equal(U.ibits(dev["w"].cpu()), U.ibits(eag["w"].cpu()))
     moved = (dev["w"].cpu() - before).abs()[9:]
     assert float(moved.max()) > 0.05, "the replay did not read the new lr"  # steps of about lr = 0.5, not 0.01
 

@@ -19,16 +19,13 @@ from hpnn_amd.utils import formats
 from tests import adam_common as A
 from tests import front_exact_common as fc
 from tests import lrsched_common as K
+from tests import upd_common as U
 
 DTYPES = [torch.float64, torch.float32]
 IDS = ["f64", "f32"]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "bin")
 BIG = 1_048_576 + 3  # the smallest n that enters the grid-stride loop (4096 x 256 elements per pass)
-
-
-def _ibits(t):
-    return t.view({torch.float64: torch.int64, torch.float32: torch.int32, torch.bfloat16: torch.int16}[t.dtype])
 
 
 def _segment(n, S, off, goff, dtype, seed):
@@ -42,24 +39,11 @@ def _segment(n, S, off, goff, dtype, seed):
     if n > 3:
         sl[:, :3] = 0.0
         v[:3] = 0.0
-    gs = n + 3
-    sbase = torch.full((goff + S * gs + 1,), float("nan"), dtype=dtype)
-    slab = sbase[goff:goff + S * gs].view(S, gs)[:, :n]
-    slab.copy_(sl)
-    seg, bases = {"slab": slab}, {"slab": sbase}
+    seg, bases = {}, {}
+    bases["slab"], seg["slab"] = U.slab_window(sl, goff)
     for k, t in (("w", w), ("v", v)):
-        bases[k] = torch.full((off + n + 3,), float("nan"), dtype=dtype)
-        seg[k] = bases[k][off:off + n]
-        seg[k].copy_(t)
+        bases[k], seg[k] = U.window(t, off)
     return seg, bases
-
-
-def _to_cuda(seg, bases):
-    dev, dbase = {}, {}
-    for k, t in seg.items():
-        dbase[k] = bases[k].cuda()
-        dev[k] = dbase[k].as_strided(t.shape, t.stride(), t.storage_offset())
-    return dev, dbase
 
 
 def _state(epochs=3, **kw):
@@ -76,7 +60,7 @@ def _run_fp(sizes, S, off, goff, dtype, momentum, seed):
     and v, the sentinels around them, the slabs read only"""
     cpu = [_segment(n, S, off, goff, dtype, seed + i) for i, n in enumerate(sizes)]
     st = _state()
-    dev = [_to_cuda(seg, bases) for seg, bases in cpu]
+    dev = [U.to_cuda(seg, bases) for seg, bases in cpu]
     ops.sgd_sched_fp(ops.SgdSchedTable([d for d, _ in dev], momentum=momentum), st.cuda(), scale=1.0 / 7, alpha=0.25)
     torch.cuda.synchronize()
     for (seg, bases), (d1, b1) in zip(cpu, dev):
@@ -84,16 +68,16 @@ def _run_fp(sizes, S, off, goff, dtype, momentum, seed):
         ops.sgd_sched_fp(ops.SgdSchedTable([dict(w=hw, v=hv, slab=seg["slab"])], momentum=momentum), st, scale=1.0 / 7,
                          alpha=0.25)
         who = f"n {seg['w'].numel()} S {S} off {off} goff {goff} {dtype} momentum {momentum}"
-        assert torch.equal(_ibits(d1["w"].cpu()), _ibits(hw)), who
-        assert torch.equal(_ibits(d1["v"].cpu()), _ibits(hv if momentum else seg["v"])), who
+        assert torch.equal(U.ibits(d1["w"].cpu()), U.ibits(hw)), who
+        assert torch.equal(U.ibits(d1["v"].cpu()), U.ibits(hv if momentum else seg["v"])), who
         assert not torch.equal(hw, seg["w"]), who
         for k in ("w", "v", "slab"):
             mask = torch.ones_like(bases[k], dtype=torch.bool)
             mask.as_strided(seg[k].shape, seg[k].stride(), seg[k].storage_offset()).fill_(False)
-            assert torch.equal(_ibits(b1[k].cpu())[mask], _ibits(bases[k])[mask]), f"{who}: {k} sentinels written"
-        assert torch.equal(_ibits(d1["slab"].cpu()), _ibits(seg["slab"])), "the slabs are read only"
+            assert torch.equal(U.ibits(b1[k].cpu())[mask], U.ibits(bases[k])[mask]), f"{who}: {k} sentinels written"
+        assert torch.equal(U.ibits(d1["slab"].cpu()), U.ibits(seg["slab"])), "the slabs are read only"
         if seg["w"].numel() > 3:  # g = 0 with v = 0 keeps w's bits
-            assert torch.equal(_ibits(d1["w"].cpu()[:3]), _ibits(seg["w"][:3]))
+            assert torch.equal(U.ibits(d1["w"].cpu()[:3]), U.ibits(seg["w"][:3]))
 
 
 # ------------------------------------------------------------------ 1. hpnn_sgd_sched_fp
@@ -148,13 +132,6 @@ def test_sgd_sched_table_refusals_write_nothing(gpu):
 LAYERS = {"32x32": (32, 32, False), "64x96": (64, 96, False), "128x800": (128, 800, True)}
 
 
-def _multi_dev(c):
-    N, K = c["W"].shape
-    return (c["W"].cuda(), c["V"].cuda(), c["G"].cuda(), torch.full((N, K), 7.0, dtype=torch.bfloat16, device="cuda"),
-            torch.full((K, N), 7.0, dtype=torch.bfloat16, device="cuda"),
-            torch.full((N * K,), 7.0, dtype=torch.bfloat16, device="cuda") if c["frag"] else None)
-
-
 def _check_copies(W1, Wb, Wt, Wf):
     assert torch.equal(Wb, W1.bfloat16()) and torch.equal(Wt, Wb.t())
     if Wf is not None:
@@ -180,7 +157,7 @@ def test_sgd_sched_multi_exact_on_integers(gpu, names, S, momentum):
         cpu.append(dict(W=torch.randint(-256, 257, (N, Kk), generator=g).float() / 64,
                         V=torch.randint(-256, 257, (N, Kk), generator=g).float() / 64 * (1.0 if momentum else 0.0),
                         G=torch.randint(-3, 4, (S, N, Kk), generator=g).float(), frag=frag))
-    dev = [_multi_dev(c) for c in cpu]
+    dev = [U.multi_dev(c, ("V",)) for c in cpu]
     ops.sgd_sched_multi(dev, st.cuda(), alpha=alpha, scale=scale, momentum=momentum)
     torch.cuda.synchronize()
     for c, d in zip(cpu, dev):
@@ -209,14 +186,14 @@ def test_sgd_sched_multi_random_equals_the_host_form(gpu, name):
                  G=torch.randn(S, N, Kk, generator=g), frag=frag)
         c["G"][:, -3:, :] = 0.0  # rows that behave like the plan's zero padding
         c["W"][-3:], c["V"][-3:] = 0.0, 0.0
-        d = _multi_dev(c)
+        d = U.multi_dev(c, ("V",))
         ops.sgd_sched_multi([d], st.cuda(), alpha=0.2, scale=1.0 / 5, momentum=momentum)
         torch.cuda.synchronize()
         W1, V1, G1, Wb, Wt, Wf = [None if t is None else t.cpu() for t in d]
         hw, hv = c["W"].clone(), c["V"].clone()
         ops.sgd_sched_multi([(hw, hv, c["G"], torch.empty_like(Wb), torch.empty_like(Wt), None)], st, alpha=0.2,
                             scale=1.0 / 5, momentum=momentum)
-        assert torch.equal(_ibits(W1), _ibits(hw)) and torch.equal(_ibits(V1), _ibits(hv if momentum else c["V"]))
+        assert torch.equal(U.ibits(W1), U.ibits(hw)) and torch.equal(U.ibits(V1), U.ibits(hv if momentum else c["V"]))
         assert not W1[-3:].any() and not V1[-3:].any()  # g = 0, v = 0 rows stay exactly 0
         _check_copies(W1, Wb, Wt, Wf)
 
@@ -227,7 +204,7 @@ def test_sgd_sched_multi_goes_in_groups_past_8_layers(gpu):
     g = torch.Generator().manual_seed(3)
     cpu = [dict(W=torch.randint(-8, 9, (32, 32), generator=g).float(), V=torch.zeros(32, 32),
                 G=torch.randint(-3, 4, (2, 32, 32), generator=g).float(), frag=False) for _ in range(11)]
-    dev = [_multi_dev(c) for c in cpu]
+    dev = [U.multi_dev(c, ("V",)) for c in cpu]
     ops.sgd_sched_multi(dev, st.cuda(), scale=1.0, momentum=False)
     torch.cuda.synchronize()
     for c, d in zip(cpu, dev):
@@ -291,13 +268,13 @@ def test_plateau_launch_equals_the_host_form(gpu):
         vhd = vh.cuda()
         cur = torch.zeros(1, dtype=torch.int32, device="cuda")
         ops.lr_plateau(vhd, cur, sd)  # an empty history: a no-op
-        assert torch.equal(_ibits(sd.cpu()), _ibits(sh))
+        assert torch.equal(U.ibits(sd.cpu()), U.ibits(sh))
         for e in range(len(losses)):
             cur.fill_(e + 1)
             ops.lr_advance(sd), ops.lr_advance(sh)
             ops.lr_plateau(vhd, cur, sd)
             ops.lr_plateau(vh, torch.tensor([e + 1], dtype=torch.int32), sh)
-            assert torch.equal(_ibits(sd.cpu()), _ibits(sh)), (case["name"], e)
+            assert torch.equal(U.ibits(sd.cpu()), U.ibits(sh)), (case["name"], e)
         t = K.trace(cfg, losses)
         r = ops.read_lr_state(sd)
         assert K.same([(r["lr"], r["scale"], r["best"], r["stale"], r["cuts"], r["valid"])], t[-1:])
