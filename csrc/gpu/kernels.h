@@ -100,6 +100,16 @@ int hpnn_gemm_nt8_bf16(const void *A, int lda, const void *B, int ldb, void *C, 
                        int M, int N, int K, int epi, int c_f32, hipStream_t stream);
 int hpnn_gemm_nt_ws_bf16(const void *X, int ldx, const void *W, int ldw, void *C, int ldc, int M, int N, int K,
                          int epi, int c_f32, hipStream_t stream);
+/* host only: the ring depth of the weight-stationary instance for this call, 0 where
+ * hpnn_gemm_nt_ws_bf16 returns 1 (no instance) */
+int hpnn_gemm_nt_ws_plan(int M, int N, int K, int ldx, int ldw, int ldc, int epi);
+/* host only: which kernel hpnn_gemm_nt_bf16 / hpnn_gemm_tn_bf16 (and _reduce) run for these
+ * arguments under the current toggles: the arm (index of hpnn_gemm_*_arm_name) and, in *stages,
+ * the ring depth of its instantiation (0: the 8-phase schedule), or the refusal code (< 0) */
+int hpnn_gemm_nt_plan(int M, int N, int K, int lda, int ldb, int ldc, int epi, int has_aux, int ldaux, int *stages);
+int hpnn_gemm_tn_plan(int N, int M, int Bt, int splits, int ldd, int ldh, int ldg, int *stages);
+const char *hpnn_gemm_nt_arm_name(int i); /* NULL past the last arm */
+const char *hpnn_gemm_tn_arm_name(int i);
 
 /* slab[s][N x M] = sum_{b in slice s} D[b][n] H[b][m] (FP32 out).
  * D: [Bt x N] BF16, H: [Bt x M] BF16. Bt % 64 == 0, 1 <= splits <= Bt/64, N,M % 32 == 0.

@@ -847,21 +847,33 @@ float *splitk_ws(size_t bytes, hipStream_t s) {
 
 }  // namespace
 
+/* host only: the shape and stride rules of hpnn_gemm_nt8_bf16 (all but the pointer alignment) */
+int hpnn_gemm_nt8_shape_ok(int M, int N, int K, int lda, int ldb, int ldc, int epi, int has_aux, int ldaux) {
+    if (M <= 0 || N <= 0 || K <= 0 || M % 256 || N % 256 || K % 128) return 0;
+    if (lda % 8 || ldb % 8 || ldc % 4) return 0;
+    if ((size_t)lda * 2 * 256 >= (1u << 31) || (size_t)ldb * 2 * 256 >= (1u << 31)) return 0; /* 32-bit offsets */
+    if (epi == HPNN_EPI_DACT && (!has_aux || ldaux % 4)) return 0;
+    return 1;
+}
+
 extern "C" int hpnn_gemm_nt8_bf16(const void *A, int lda, const void *B, int ldb, void *C, int ldc, const void *aux,
                                   int ldaux, int M, int N, int K, int epi, int c_f32, hipStream_t stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || M % 256 || N % 256 || K % 128) return -1;
-    if (lda % 8 || ldb % 8 || ldc % 4 || ((uintptr_t)A & 15) || ((uintptr_t)B & 15)) return -1;
-    if ((size_t)lda * 2 * 256 >= (1u << 31) || (size_t)ldb * 2 * 256 >= (1u << 31)) return -1; /* 32-bit offsets */
-    if (epi == HPNN_EPI_DACT && (!aux || ldaux % 4)) return -1;
+    if (!hpnn_gemm_nt8_shape_ok(M, N, K, lda, ldb, ldc, epi, aux != nullptr, ldaux)) return -1;
+    if (((uintptr_t)A & 15) || ((uintptr_t)B & 15)) return -1;
     return by_epi(epi, c_f32, [&](auto E, auto F) {
         return launch8<decltype(E)::value, decltype(F)::value>(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, stream);
     });
 }
 
+/* host only: whether hpnn_gemm_tn8_launch takes the shape */
+int hpnn_gemm_tn8_launch_ok(int N, int M, int Bt, int splits, int ldd, int ldh, int ldg) {
+    return tn8_shape_ok(N, M, Bt, ldd, ldh, splits) && ldg % 4 == 0;
+}
+
 /* TN entry for gemm_tn_dispatch (kernels_mfma.hip): -1 when the shape does not fit */
 int hpnn_gemm_tn8_launch(const void *D, int ldd, const void *H, int ldh, float *slab, int ldg, int N, int M, int Bt,
                          int splits, hipStream_t stream, const hpnn::TnTail &tail) {
-    if (!tn8_shape_ok(N, M, Bt, ldd, ldh, splits) || ldg % 4) return -1;
+    if (!hpnn_gemm_tn8_launch_ok(N, M, Bt, splits, ldd, ldh, ldg)) return -1;
     const int units = Bt / 64;
     const int tiles_n = N / 256, ntiles = tiles_n * (M / 256);
     hipLaunchKernelGGL(gemm_tn8_kernel<0>, dim3(ntiles * splits + tail.blocks), dim3(512), 0, stream,

@@ -40,6 +40,8 @@ HPNN_CO_PROBE(mfma)
 /* kernels_8ph.hip */
 int hpnn_gemm_tn8_launch(const void *D, int ldd, const void *H, int ldh, float *slab, int ldg, int N, int M, int Bt,
                          int splits, hipStream_t stream, const hpnn::TnTail &tail);
+int hpnn_gemm_tn8_launch_ok(int N, int M, int Bt, int splits, int ldd, int ldh, int ldg);
+int hpnn_gemm_nt8_shape_ok(int M, int N, int K, int lda, int ldb, int ldc, int epi, int has_aux, int ldaux);
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
@@ -462,15 +464,75 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_tn_pipe_kernel(const __bf16
         }
 }
 
+/* ---------------------------------------------------------------------- */
+/* Dispatch: which kernel runs for which shape.  nt_plan() / tn_plan() are pure host functions;   */
+/* the launchers below run what they return, and hpnn_gemm_nt_plan / hpnn_gemm_tn_plan export the  */
+/* same answer (arm and ring depth of the instantiation, or the refusal code) to the tests.        */
+/* ---------------------------------------------------------------------- */
+struct GemmPlan {
+    int arm;    /* >= 0: the arm; < 0: the refusal code of the launcher */
+    int stages; /* ring depth STAGES of the chosen instantiation (0: the 8-phase schedule) */
+};
+
+/* NT arms: the 4-wave 128 x BN tile with BK-wide K steps as NT_<BN>x<BK> */
+#define HPNN_NT_BNBK(X_) X_(128, 64) X_(128, 32) X_(64, 64) X_(64, 32) X_(32, 64) X_(32, 32)
+enum NtArm {
+    NT_WS,  /* weight-stationary (kernels_ws.hip) */
+    NT_8PH, /* 8-phase 256 x 256 (kernels_8ph.hip) */
+    NT_BIG, /* 1-phase 256 x 256, 8 waves */
+    NT_PP,  /* software-pipelined 128 x 128, 8 waves */
+    NT_W8,  /* 8-wave 128 x 128, two barriers per step */
+#define HPNN_X(BN_, BK_) NT_##BN_##x##BK_,
+    HPNN_NT_BNBK(HPNN_X)
+#undef HPNN_X
+    NT_ARMS
+};
+const char *const nt_arm_names[NT_ARMS] = {"ws", "8ph", "256x256", "pp128", "w8_128",
+#define HPNN_X(BN_, BK_) "bn" #BN_ "_bk" #BK_,
+                                           HPNN_NT_BNBK(HPNN_X)
+#undef HPNN_X
+};
+constexpr int NT_BIG_ST = 2, NT_PP_ST = 5, NT_W8_ST = 3;
+/* ring depth of the 4-wave 128 x BN x BK tile: ~64 KiB of staging -> 2 workgroups per CU */
+constexpr int nt_ring(int BN, int BK) {
+    const int st = 65536 / ((128 + BN) * BK * 2);
+    return st < 2 ? 2 : (st > 5 ? 5 : st);
+}
+
+/* TN arms: gemm_tn_pipe_kernel<TM, TN> as TN_<TM>x<TN> */
+#define HPNN_TN_PAIRS(X_)                                                                                     \
+    X_(128, 128) X_(128, 64) X_(128, 32) X_(160, 128) X_(160, 64) X_(160, 32) X_(96, 128) X_(96, 64) X_(96, 32) \
+    X_(64, 128) X_(64, 64) X_(64, 32) X_(32, 128) X_(32, 64) X_(32, 32)
+enum TnArm {
+    TN_8PH, /* 8-phase 256 x 256 (kernels_8ph.hip) */
+    TN_BIG, /* 256 x 256, 8 waves, 4 stages */
+    TN_T64, /* 64 x 64 for grids that leave CUs idle */
+#define HPNN_X(P_, Q_) TN_##P_##x##Q_,
+    HPNN_TN_PAIRS(HPNN_X)
+#undef HPNN_X
+    TN_ARMS
+};
+const char *const tn_arm_names[TN_ARMS] = {"8ph", "256x256", "t64",
+#define HPNN_X(P_, Q_) "tm" #P_ "_tn" #Q_,
+                                           HPNN_TN_PAIRS(HPNN_X)
+#undef HPNN_X
+};
+constexpr int TN_BIG_ST = 4;
+/* BKR-row stages (default 32), ring of ~72 KiB (2 workgroups per CU), or the deep ring
+ * (~144 KiB, one workgroup per CU: twice the bytes in flight per CU for a grid of <= 1
+ * GEMM workgroup per CU, where the stream is latency-bound by the ring depth) */
+constexpr int tn_ring(int TM, int TN, int RING = 73728, int MAXST = 6, int BKR = 32) {
+    const int st = RING / (BKR * (TM + TN) * 2);
+    return st < 2 ? 2 : (st > MAXST ? MAXST : st);
+}
+
 template <int BN, int BK, int EPI, bool CF32>
 int launch_nt_bn(const void *A, int lda, const void *B, int ldb, void *C, int ldc, const void *aux, int ldaux, int M,
                  int N, int K, hipStream_t s) {
     constexpr int BM = 128;
     constexpr int WM = (BN == 128) ? 2 : 4;
     constexpr int WN = 4 / WM;
-    /* ring depth: ~64 KiB of staging -> 2 workgroups per CU */
-    constexpr int STAGE_BYTES = (BM + BN) * BK * 2;
-    constexpr int ST = (65536 / STAGE_BYTES) < 2 ? 2 : ((65536 / STAGE_BYTES) > 5 ? 5 : (65536 / STAGE_BYTES));
+    constexpr int ST = nt_ring(BN, BK);
     const int tiles_n = N / BN, tiles_m = M / BM;
     hipLaunchKernelGGL((gemm_nt_pipe_kernel<BM, BN, BK, WM, WN, ST, EPI, CF32>), dim3(tiles_m * tiles_n), dim3(256), 0,
                        s, (const __bf16 *)A, lda, (const __bf16 *)B, ldb, C, ldc, (const __bf16 *)aux, ldaux, K,
@@ -490,7 +552,7 @@ int launch_nt_big(const void *A, int lda, const void *B, int ldb, void *C, int l
                   int N, int K, hipStream_t s) {
     constexpr int BM = 256, BN = 256;
     const int tiles_n = N / BN, tiles_m = M / BM;
-    hipLaunchKernelGGL((gemm_nt_pipe_kernel<BM, BN, 64, 2, 4, 2, EPI, CF32>), dim3(tiles_m * tiles_n), dim3(512), 0, s,
+    hipLaunchKernelGGL((gemm_nt_pipe_kernel<BM, BN, 64, 2, 4, NT_BIG_ST, EPI, CF32>), dim3(tiles_m * tiles_n), dim3(512), 0, s,
                        (const __bf16 *)A, lda, (const __bf16 *)B, ldb, C, ldc, (const __bf16 *)aux, ldaux, K, tiles_n);
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
@@ -503,22 +565,29 @@ int g_tn8 = [] { const char *e = getenv("HPNN_TN_8PH"); return !(e && e[0] == '0
 /* the software-pipelined 128 x 128 NT kernel for grids under two tiles per CU */
 int g_ntpp = [] { const char *e = getenv("HPNN_NT_PP"); return !(e && e[0] == '0'); }();
 
-template <int EPI, bool CF32>
-int launch_nt_epi(const void *A, int lda, const void *B, int ldb, void *C, int ldc, const void *aux, int ldaux, int M,
-                  int N, int K, hipStream_t s) {
+/* the arm and ring depth hpnn_gemm_nt_bf16 runs for this call, or its refusal code */
+GemmPlan nt_plan(int M, int N, int K, int lda, int ldb, int ldc, int epi, bool has_aux, int ldaux) {
+    if (M <= 0 || N <= 0 || K <= 0) return {-1, 0};
+    /* wide-input layer with a small weight matrix and a large batch: weight-stationary kernel */
+    static const int ws_off = [] { const char *e = getenv("HPNN_NO_WS"); return e && atoi(e) ? 1 : 0; }();
+    if (!ws_off && M % 32 == 0 && M >= 16384 && N <= 128) {
+        const int st = hpnn_gemm_nt_ws_plan(M, N, K, lda, ldb, ldc, epi);
+        if (st) return {NT_WS, st};
+    }
+    if (M % 128 || N % 32 || K % 32) return {-2, 0};
+    if (lda % 8 || ldb % 8 || ldc % 8 || ((epi == HPNN_EPI_DACT) && (ldaux % 4 || !has_aux))) return {-3, 0};
     const bool k64 = (K % 64) == 0;
     static const int big_off = [] { const char *e = getenv("HPNN_NT_BIG"); return e && e[0] == '0'; }();
-    if (!big_off && g_nt8 && K % 128 == 0 && M % 256 == 0 && N % 256 == 0 && (long)(M / 256) * (N / 256) >= 256 &&
-        K >= 512)
-        return hpnn_gemm_nt8_bf16(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, EPI, CF32 ? 1 : 0, s);
-    /* (a split-K form of the 8-phase kernel for grids of fewer 256x256 tiles than CUs,
-     * hpnn_gemm_nt8_splitk_bf16, measured slower on the RRUFF-shaped first layer: 168 vs
-     * 160 us per step -- the FP32 slabs cost more than the idle CUs; not dispatched here) */
-    if (!big_off && k64 && M % 256 == 0 && N % 256 == 0 && (long)(M / 256) * (N / 256) >= 256 && K >= 512)
-        return launch_nt_big<EPI, CF32>(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, s);
-#define HPNN_NT(BN_)                                                                                  \
-    return k64 ? launch_nt_bn<BN_, 64, EPI, CF32>(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, s)      \
-               : launch_nt_bn<BN_, 32, EPI, CF32>(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, s)
+    if (!big_off && k64 && M % 256 == 0 && N % 256 == 0 && (long)(M / 256) * (N / 256) >= 256 && K >= 512) {
+        if (g_nt8 && K % 128 == 0) {
+            if (!hpnn_gemm_nt8_shape_ok(M, N, K, lda, ldb, ldc, epi, has_aux, ldaux)) return {-1, 0};
+            return {NT_8PH, 0};
+        }
+        /* (a split-K form of the 8-phase kernel for grids of fewer 256x256 tiles than CUs,
+         * hpnn_gemm_nt8_splitk_bf16, measured slower on the RRUFF-shaped first layer: 168 vs
+         * 160 us per step -- the FP32 slabs cost more than the idle CUs; not dispatched here) */
+        return {NT_BIG, NT_BIG_ST};
+    }
     /* grids of fewer than two 128 x 128 tiles per CU (the 8 x 4096 net at its 8-GPU shard,
      * M = 1024: 256 tiles): 8 waves (2 x 4, 64 x 32 wave tiles) and a 3-stage ring, one
      * workgroup per CU with two waves per SIMD, instead of the 4-wave tile's one.  Synthetic
@@ -527,34 +596,48 @@ int launch_nt_epi(const void *A, int lda, const void *B, int ldb, void *C, int l
      * (profiles/r5/SUMMARY.md).  HPNN_NT_SMALL=0: the 4-wave tile. */
     static const bool small_off = [] { const char *e = getenv("HPNN_NT_SMALL"); return e && e[0] == '0'; }();
     if (!small_off && k64 && M % 128 == 0 && N % 128 == 0 && (long)(M / 128) * (N / 128) < 512) {
-        const int tiles_n = N / 128, tiles_m = M / 128;
-        if (g_ntpp) { /* the software-pipelined form (HPNN_NT_PP=0: the kernel below) */
-            hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI, CF32, 5>), dim3(tiles_m * tiles_n), dim3(512), 0, s,
-                               (const __bf16 *)A, lda, (const __bf16 *)B, ldb, C, ldc, (const __bf16 *)aux, ldaux, K,
-                               tiles_n);
-            return hipGetLastError() == hipSuccess ? 0 : -5;
-        }
-        hipLaunchKernelGGL((gemm_nt_pipe_kernel<128, 128, 64, 2, 4, 3, EPI, CF32>), dim3(tiles_m * tiles_n), dim3(512),
-                           0, s, (const __bf16 *)A, lda, (const __bf16 *)B, ldb, C, ldc, (const __bf16 *)aux, ldaux,
-                           K, tiles_n);
-        return hipGetLastError() == hipSuccess ? 0 : -5;
+        if (g_ntpp) return {NT_PP, NT_PP_ST}; /* the software-pipelined form (HPNN_NT_PP=0: the 8-wave kernel) */
+        return {NT_W8, NT_W8_ST};
     }
-    if (N % 128 == 0 && N >= 128) { HPNN_NT(128); }
-    if (N % 64 == 0) { HPNN_NT(64); }
-    HPNN_NT(32);
-#undef HPNN_NT
+    const int bn = (N % 128 == 0 && N >= 128) ? 128 : (N % 64 == 0 ? 64 : 32), bk = k64 ? 64 : 32;
+#define HPNN_X(BN_, BK_) \
+    if (bn == BN_ && bk == BK_) return {NT_##BN_##x##BK_, nt_ring(BN_, BK_)};
+    HPNN_NT_BNBK(HPNN_X)
+#undef HPNN_X
+    return {-2, 0}; /* not reached */
 }
 
-template <int TM, int TN, int RING = 73728, int MAXST = 6, int BKR = 32, int WM = 2, int WN = 2>
+template <int EPI, bool CF32>
+int launch_nt_epi(int arm, const void *A, int lda, const void *B, int ldb, void *C, int ldc, const void *aux,
+                  int ldaux, int M, int N, int K, hipStream_t s) {
+    const int tiles_n = N / 128, tiles_m = M / 128;
+    switch (arm) {
+    case NT_8PH: return hpnn_gemm_nt8_bf16(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, EPI, CF32 ? 1 : 0, s);
+    case NT_BIG: return launch_nt_big<EPI, CF32>(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, s);
+    case NT_PP:
+        hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI, CF32, NT_PP_ST>), dim3(tiles_m * tiles_n), dim3(512), 0, s,
+                           (const __bf16 *)A, lda, (const __bf16 *)B, ldb, C, ldc, (const __bf16 *)aux, ldaux, K,
+                           tiles_n);
+        return hipGetLastError() == hipSuccess ? 0 : -5;
+    case NT_W8:
+        hipLaunchKernelGGL((gemm_nt_pipe_kernel<128, 128, 64, 2, 4, NT_W8_ST, EPI, CF32>), dim3(tiles_m * tiles_n),
+                           dim3(512), 0, s, (const __bf16 *)A, lda, (const __bf16 *)B, ldb, C, ldc,
+                           (const __bf16 *)aux, ldaux, K, tiles_n);
+        return hipGetLastError() == hipSuccess ? 0 : -5;
+#define HPNN_X(BN_, BK_) \
+    case NT_##BN_##x##BK_: return launch_nt_bn<BN_, BK_, EPI, CF32>(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, s);
+        HPNN_NT_BNBK(HPNN_X)
+#undef HPNN_X
+    }
+    return -2;
+}
+
+template <int TM, int TN>
 int launch_tn_t(const void *D, int ldd, const void *H, int ldh, float *slab, int ldg, int N, int M, int Bt, int splits,
                 hipStream_t s, const TnTail &tail) {
+    constexpr int BKR = 32, WM = 2, WN = 2, ST = tn_ring(TM, TN);
     const int tiles_n = N / TN, tiles_m = M / TM;
     const int units = Bt / 64;
-    /* BKR-row stages (default 32), ring of ~72 KiB (2 workgroups per CU), or the deep ring
-     * (~144 KiB, one workgroup per CU: twice the bytes in flight per CU for a grid of <= 1
-     * GEMM workgroup per CU, where the stream is latency-bound by the ring depth) */
-    constexpr int STAGE = BKR * (TM + TN) * 2;
-    constexpr int ST = (RING / STAGE) < 2 ? 2 : ((RING / STAGE) > MAXST ? MAXST : (RING / STAGE));
     const int tiles = tiles_m * tiles_n;
     const int xcd_map = (splits % 8 == 0 && tiles > 1) ? 1 : 0;
     hipLaunchKernelGGL((gemm_tn_pipe_kernel<TM, TN, BKR, ST, WM, WN>), dim3(tiles * splits + tail.blocks),
@@ -567,19 +650,12 @@ int launch_tn_t(const void *D, int ldd, const void *H, int ldh, float *slab, int
  * ~144 KiB ring, one workgroup per CU, 74.3-74.6 vs 73.4-73.5 us per step -- the tail
  * reduction workgroups lose their co-residence; 8-wave / 64-row-stage variants 28.6-33.6
  * vs 29.6-29.8 us for the GEMM alone, none a clear win) */
-template <int TM>
-int launch_tn_m(const void *D, int ldd, const void *H, int ldh, float *slab, int ldg, int N, int M, int Bt, int splits,
-                hipStream_t s, const TnTail &t) {
-    if (N % 128 == 0) return launch_tn_t<TM, 128>(D, ldd, H, ldh, slab, ldg, N, M, Bt, splits, s, t);
-    if (N % 64 == 0) return launch_tn_t<TM, 64>(D, ldd, H, ldh, slab, ldg, N, M, Bt, splits, s, t);
-    return launch_tn_t<TM, 32>(D, ldd, H, ldh, slab, ldg, N, M, Bt, splits, s, t);
-}
 
 /* large weight gradients (>= 256 output tiles of 256x256, one split): 8-wave 256x256 tiles,
  * 4-stage ring of 32-row stages (128 KiB), one workgroup per CU (HPNN_TN_BIG=0 disables) */
 int launch_tn_big(const void *D, int ldd, const void *H, int ldh, float *slab, int ldg, int N, int M, int Bt,
                   int splits, hipStream_t s, const TnTail &t) {
-    constexpr int TM = 256, TN = 256, BKR = 32, ST = 4;
+    constexpr int TM = 256, TN = 256, BKR = 32, ST = TN_BIG_ST;
     const int tiles_n = N / TN, tiles_m = M / TM, tiles = tiles_m * tiles_n;
     const int xcd_map = (splits % 8 == 0 && tiles > 1) ? 1 : 0;
     hipLaunchKernelGGL((gemm_tn_pipe_kernel<TM, TN, BKR, ST, 2, 4>), dim3(tiles * splits + t.blocks), dim3(512), 0, s,
@@ -588,30 +664,45 @@ int launch_tn_big(const void *D, int ldd, const void *H, int ldh, float *slab, i
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
-int gemm_tn_dispatch(const void *D, int ldd, const void *H, int ldh, float *slab, int ldg, int N, int M, int Bt,
-                     int splits, hipStream_t stream, const TnTail &t) {
-    if (N <= 0 || M <= 0 || Bt <= 0 || splits <= 0) return -1;
-    if (N % 32 || M % 32 || Bt % 64 || splits > Bt / 64) return -2;
-    if (ldd % 8 || ldh % 8 || ldg % 4 || ldg < M) return -3;
+/* the arm and ring depth hpnn_gemm_tn_bf16 (and its _reduce form) runs for this call, or its
+ * refusal code */
+GemmPlan tn_plan(int N, int M, int Bt, int splits, int ldd, int ldh, int ldg) {
+    if (N <= 0 || M <= 0 || Bt <= 0 || splits <= 0) return {-1, 0};
+    if (N % 32 || M % 32 || Bt % 64 || splits > Bt / 64) return {-2, 0};
+    if (ldd % 8 || ldh % 8 || ldg % 4 || ldg < M) return {-3, 0};
     static const int big_off = [] { const char *e = getenv("HPNN_TN_BIG"); return e && e[0] == '0'; }();
     if (!big_off && N % 256 == 0 && M % 256 == 0 && (long)(N / 256) * (M / 256) * splits >= 256) {
-        if (g_tn8) {
-            const int rc = hpnn_gemm_tn8_launch(D, ldd, H, ldh, slab, ldg, N, M, Bt, splits, stream, t);
-            if (rc != -1) return rc;
-        }
-        return launch_tn_big(D, ldd, H, ldh, slab, ldg, N, M, Bt, splits, stream, t);
+        if (g_tn8 && hpnn_gemm_tn8_launch_ok(N, M, Bt, splits, ldd, ldh, ldg)) return {TN_8PH, 0};
+        return {TN_BIG, TN_BIG_ST};
     }
     /* 64 x 64 tiles when the 128 x 128 grid leaves CUs idle: RRUFF's G1 (256 x 256 over 16384
      * rows, 32 splits) as 16 x 32 = 512 workgroups instead of 4 x 32 = 128, 145.8 / 146.1 vs
      * 150.6 / 149.4 us per step (profiles/r4/u_rruff_t64.txt; HPNN_TN_T64=0: off) */
     static const int t64 = [] { const char *e = getenv("HPNN_TN_T64"); return e ? atoi(e) : 1; }();
     if (t64 && M % 64 == 0 && N % 64 == 0 && (long)(M / 128) * (N / 128) * splits < 256)
-        return launch_tn_t<64, 64>(D, ldd, H, ldh, slab, ldg, N, M, Bt, splits, stream, t);
-    if (M % 128 == 0) return launch_tn_m<128>(D, ldd, H, ldh, slab, ldg, N, M, Bt, splits, stream, t);
-    if (M % 160 == 0) return launch_tn_m<160>(D, ldd, H, ldh, slab, ldg, N, M, Bt, splits, stream, t);
-    if (M % 96 == 0) return launch_tn_m<96>(D, ldd, H, ldh, slab, ldg, N, M, Bt, splits, stream, t);
-    if (M % 64 == 0) return launch_tn_m<64>(D, ldd, H, ldh, slab, ldg, N, M, Bt, splits, stream, t);
-    return launch_tn_m<32>(D, ldd, H, ldh, slab, ldg, N, M, Bt, splits, stream, t);
+        return {TN_T64, tn_ring(64, 64)};
+    const int tm = M % 128 == 0 ? 128 : (M % 160 == 0 ? 160 : (M % 96 == 0 ? 96 : (M % 64 == 0 ? 64 : 32)));
+    const int tn = N % 128 == 0 ? 128 : (N % 64 == 0 ? 64 : 32);
+#define HPNN_X(P_, Q_) \
+    if (tm == P_ && tn == Q_) return {TN_##P_##x##Q_, tn_ring(P_, Q_)};
+    HPNN_TN_PAIRS(HPNN_X)
+#undef HPNN_X
+    return {-2, 0}; /* not reached */
+}
+
+int gemm_tn_dispatch(const void *D, int ldd, const void *H, int ldh, float *slab, int ldg, int N, int M, int Bt,
+                     int splits, hipStream_t stream, const TnTail &t) {
+    const GemmPlan p = tn_plan(N, M, Bt, splits, ldd, ldh, ldg);
+    switch (p.arm) {
+    case TN_8PH: return hpnn_gemm_tn8_launch(D, ldd, H, ldh, slab, ldg, N, M, Bt, splits, stream, t);
+    case TN_BIG: return launch_tn_big(D, ldd, H, ldh, slab, ldg, N, M, Bt, splits, stream, t);
+    case TN_T64: return launch_tn_t<64, 64>(D, ldd, H, ldh, slab, ldg, N, M, Bt, splits, stream, t);
+#define HPNN_X(P_, Q_) \
+    case TN_##P_##x##Q_: return launch_tn_t<P_, Q_>(D, ldd, H, ldh, slab, ldg, N, M, Bt, splits, stream, t);
+        HPNN_TN_PAIRS(HPNN_X)
+#undef HPNN_X
+    }
+    return p.arm; /* the refusal code */
 }
 
 }  // namespace
@@ -649,24 +740,37 @@ extern "C" int hpnn_gemm_nn_bf16(const void *A, int lda, const void *W, int ldw,
 
 extern "C" int hpnn_gemm_nt_bf16(const void *A, int lda, const void *B, int ldb, void *C, int ldc, const void *aux,
                                  int ldaux, int M, int N, int K, int epi, int c_f32, hipStream_t stream) {
-    if (M <= 0 || N <= 0 || K <= 0) return -1;
-    /* wide-input layer with a small weight matrix and a large batch: weight-stationary kernel */
-    static const int ws_off = [] { const char *e = getenv("HPNN_NO_WS"); return e && atoi(e) ? 1 : 0; }();
-    if (!ws_off && M % 32 == 0 && M >= 16384 && N <= 128) {
-        int rc = hpnn_gemm_nt_ws_bf16(A, lda, B, ldb, C, ldc, M, N, K, epi, c_f32, stream);
-        if (rc <= 0) return rc;
-    }
-    if (M % 128 || N % 32 || K % 32) return -2;
-    if (lda % 8 || ldb % 8 || ldc % 8 || ((epi == HPNN_EPI_DACT) && (ldaux % 4 || !aux))) return -3;
+    const GemmPlan p = nt_plan(M, N, K, lda, ldb, ldc, epi, aux != nullptr, ldaux);
+    if (p.arm < 0) return p.arm;
+    if (p.arm == NT_WS) return hpnn_gemm_nt_ws_bf16(A, lda, B, ldb, C, ldc, M, N, K, epi, c_f32, stream);
     if (c_f32) {
-        if (epi == HPNN_EPI_NONE) return launch_nt_epi<HPNN_EPI_NONE, true>(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, stream);
-        if (epi == HPNN_EPI_ACT) return launch_nt_epi<HPNN_EPI_ACT, true>(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, stream);
-        return launch_nt_epi<HPNN_EPI_DACT, true>(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, stream);
+        if (epi == HPNN_EPI_NONE) return launch_nt_epi<HPNN_EPI_NONE, true>(p.arm, A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, stream);
+        if (epi == HPNN_EPI_ACT) return launch_nt_epi<HPNN_EPI_ACT, true>(p.arm, A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, stream);
+        return launch_nt_epi<HPNN_EPI_DACT, true>(p.arm, A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, stream);
     }
-    if (epi == HPNN_EPI_NONE) return launch_nt_epi<HPNN_EPI_NONE, false>(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, stream);
-    if (epi == HPNN_EPI_ACT) return launch_nt_epi<HPNN_EPI_ACT, false>(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, stream);
-    return launch_nt_epi<HPNN_EPI_DACT, false>(A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, stream);
+    if (epi == HPNN_EPI_NONE) return launch_nt_epi<HPNN_EPI_NONE, false>(p.arm, A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, stream);
+    if (epi == HPNN_EPI_ACT) return launch_nt_epi<HPNN_EPI_ACT, false>(p.arm, A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, stream);
+    return launch_nt_epi<HPNN_EPI_DACT, false>(p.arm, A, lda, B, ldb, C, ldc, aux, ldaux, M, N, K, stream);
 }
+
+/* host only (no device call): what hpnn_gemm_nt_bf16 / hpnn_gemm_tn_bf16 do with these arguments,
+ * under the current run-time toggles and HPNN_* switches.  Returns the arm (an index into the
+ * names below) with the ring depth of its instantiation in *stages, or the launcher's refusal
+ * code (< 0). */
+extern "C" int hpnn_gemm_nt_plan(int M, int N, int K, int lda, int ldb, int ldc, int epi, int has_aux, int ldaux,
+                                 int *stages) {
+    const GemmPlan p = nt_plan(M, N, K, lda, ldb, ldc, epi, has_aux != 0, ldaux);
+    if (stages) *stages = p.stages;
+    return p.arm;
+}
+extern "C" int hpnn_gemm_tn_plan(int N, int M, int Bt, int splits, int ldd, int ldh, int ldg, int *stages) {
+    const GemmPlan p = tn_plan(N, M, Bt, splits, ldd, ldh, ldg);
+    if (stages) *stages = p.stages;
+    return p.arm;
+}
+/* the name of arm i, NULL past the last */
+extern "C" const char *hpnn_gemm_nt_arm_name(int i) { return i >= 0 && i < NT_ARMS ? nt_arm_names[i] : nullptr; }
+extern "C" const char *hpnn_gemm_tn_arm_name(int i) { return i >= 0 && i < TN_ARMS ? tn_arm_names[i] : nullptr; }
 
 extern "C" int hpnn_gemm_tn_bf16(const void *D, int ldd, const void *H, int ldh, float *slab, int ldg, int N, int M,
                                  int Bt, int splits, hipStream_t stream) {

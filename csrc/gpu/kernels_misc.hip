@@ -358,7 +358,8 @@ __device__ __forceinline__ void sgd_tile(float *__restrict__ W32, float *__restr
     const int n = tn * 32 + ty, k = tk * 32 + tx * 4;
     const size_t idx = (size_t)n * K + k;
     f32x4 g = *(const f32x4 *)(G + idx);
-    {
+    if (S > 1) { /* one slab: g as it is (g + 0 would turn a -0.0 into +0.0, and with it a -0.0 weight
+                  * under hpnn_cast_weights, whose lr = 0 step must leave W32 bit for bit) */
         /* four independent partial sums keep several slab loads in flight */
         f32x4 g1 = {0.f, 0.f, 0.f, 0.f}, g2 = g1, g3 = g1;
         int s = 1;

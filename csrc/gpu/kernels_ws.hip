@@ -145,10 +145,15 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_ws_kernel(const __bf16 *__rest
 
 int g_num_cus = 0;
 
+/* ring depth of the instance for K = 32 KS: ~152 KiB of 32-row X tiles, at most 4 */
+constexpr int ws_stages(int KS) {
+    const int stage = 32 * KS * 32 * 2;
+    return (155648 / stage) > 4 ? 4 : (155648 / stage);
+}
+
 template <int NT, int KS, int EPI, bool CF32>
 int launch_ws(const void *X, int ldx, const void *W, int ldw, void *C, int ldc, int M, hipStream_t s) {
-    constexpr int STAGE = 32 * KS * 32 * 2;
-    constexpr int ST = (155648 / STAGE) > 4 ? 4 : (155648 / STAGE);
+    constexpr int ST = ws_stages(KS);
     static_assert(ST >= 2, "ring");
     if (g_num_cus <= 0) {
         int dev = 0;
@@ -171,25 +176,36 @@ int launch_ws(const void *X, int ldx, const void *W, int ldw, void *C, int ldc, 
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
+/* the instantiated (N, K) pairs: one list behind the launcher and the host query */
+#define HPNN_WS_SHAPES(X_) X_(128, 800) X_(64, 800) X_(128, 512) X_(128, 1024)
+
 template <int EPI, bool CF32>
 int dispatch_ws(const void *X, int ldx, const void *W, int ldw, void *C, int ldc, int M, int N, int K, hipStream_t s) {
-#define HPNN_WS(N_, K_)                                                                     \
-    if (N == N_ && K == K_) return launch_ws<N_ / 64, K_ / 32, EPI, CF32>(X, ldx, W, ldw, C, ldc, M, s)
-    HPNN_WS(128, 800);
-    HPNN_WS(64, 800);
-    HPNN_WS(128, 512);
-    HPNN_WS(128, 1024);
+#define HPNN_WS(N_, K_) \
+    if (N == N_ && K == K_) return launch_ws<N_ / 64, K_ / 32, EPI, CF32>(X, ldx, W, ldw, C, ldc, M, s);
+    HPNN_WS_SHAPES(HPNN_WS)
 #undef HPNN_WS
     return 1; /* shape not instantiated */
 }
 
 }  // namespace
 
+/* host only: the ring depth of the instance hpnn_gemm_nt_ws_bf16 launches for this call, 0 where it
+ * returns 1 */
+extern "C" int hpnn_gemm_nt_ws_plan(int M, int N, int K, int ldx, int ldw, int ldc, int epi) {
+    if (M <= 0 || M % 32 || ldx % 8 || ldw % 8 || ldc % 8) return 0;
+    if (epi == HPNN_EPI_DACT) return 0;
+#define HPNN_WS(N_, K_) \
+    if (N == N_ && K == K_) return ws_stages(K_ / 32);
+    HPNN_WS_SHAPES(HPNN_WS)
+#undef HPNN_WS
+    return 0;
+}
+
 /* returns 0 when launched, 1 when the shape has no weight-stationary instance */
 extern "C" int hpnn_gemm_nt_ws_bf16(const void *X, int ldx, const void *W, int ldw, void *C, int ldc, int M, int N,
                                     int K, int epi, int c_f32, hipStream_t stream) {
-    if (M % 32 || ldx % 8 || ldw % 8 || ldc % 8) return 1;
-    if (epi == HPNN_EPI_DACT) return 1;
+    if (!hpnn_gemm_nt_ws_plan(M, N, K, ldx, ldw, ldc, epi)) return 1;
     if (c_f32) {
         if (epi == HPNN_EPI_ACT) return dispatch_ws<HPNN_EPI_ACT, true>(X, ldx, W, ldw, C, ldc, M, N, K, stream);
         return dispatch_ws<HPNN_EPI_NONE, true>(X, ldx, W, ldw, C, ldc, M, N, K, stream);

@@ -354,6 +354,38 @@ PYBIND11_MODULE(_native, m) {
     });
     m.def("gemm_tn_set_8ph", [](int on) { hpnn_gemm_tn_set_8ph(on); });
     m.def("gemm_nt_set_pp", [](int on) { hpnn_gemm_nt_set_pp(on); });
+    /* host only: (arm index or refusal code < 0, ring depth) of the NT / TN dispatch for these
+     * arguments under the current toggles; the arm names by index */
+    m.def("gemm_nt_plan", [](int M, int N, int K, int lda, int ldb, int ldc, int epi, int has_aux, int ldaux) {
+        int st = 0;
+        const int arm = hpnn_gemm_nt_plan(M, N, K, lda, ldb, ldc, epi, has_aux, ldaux, &st);
+        return std::make_pair(arm, st);
+    });
+    m.def("gemm_tn_plan", [](int N, int M, int Bt, int splits, int ldd, int ldh, int ldg) {
+        int st = 0;
+        const int arm = hpnn_gemm_tn_plan(N, M, Bt, splits, ldd, ldh, ldg, &st);
+        return std::make_pair(arm, st);
+    });
+    m.def("gemm_nt_arms", []() {
+        std::vector<std::string> v;
+        for (int i = 0; hpnn_gemm_nt_arm_name(i); i++) v.push_back(hpnn_gemm_nt_arm_name(i));
+        return v;
+    });
+    m.def("gemm_tn_arms", []() {
+        std::vector<std::string> v;
+        for (int i = 0; hpnn_gemm_tn_arm_name(i); i++) v.push_back(hpnn_gemm_tn_arm_name(i));
+        return v;
+    });
+    m.def("gemm_nt_ws_plan", [](int M, int N, int K, int ldx, int ldw, int ldc, int epi) {
+        return hpnn_gemm_nt_ws_plan(M, N, K, ldx, ldw, ldc, epi);
+    });
+    /* the weight-stationary kernel called directly: 0, or 1 where the shape has no instance */
+    m.def("gemm_nt_ws_bf16", [](uptr X, int ldx, uptr W, int ldw, uptr C, int ldc, int M, int N, int K, int epi,
+                                int c_f32, uptr stream) {
+        const int rc = hpnn_gemm_nt_ws_bf16(P(X), ldx, P(W), ldw, P(C), ldc, M, N, K, epi, c_f32, S(stream));
+        if (rc < 0) check(rc, "gemm_nt_ws_bf16");
+        return rc;
+    });
     m.def(
         "gemm_nt8_bf16",
         [](uptr A, int lda, uptr B, int ldb, uptr C, int ldc, uptr aux, int ldaux, int M, int N, int K, int epi,

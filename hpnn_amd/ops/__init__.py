@@ -50,6 +50,64 @@ def gemm_nt(A, B, epi=EPI_NONE, aux=None, out_f32=False, out=None):
     return out
 
 
+def _plan(arm, stages, names):
+    return (names[arm] if arm >= 0 else arm), stages
+
+
+def gemm_nt_arms():
+    """names of the kernels hpnn_gemm_nt_bf16 chooses between (csrc/gpu/kernels_mfma.hip)"""
+    return list(native().gemm_nt_arms())
+
+
+def gemm_tn_arms():
+    return list(native().gemm_tn_arms())
+
+
+def gemm_nt_plan(M, N, K, lda, ldb, ldc, epi=EPI_NONE, has_aux=False, ldaux=0):
+    """what gemm_nt launches for these arguments under the current toggles: (arm name, ring depth of
+    its instantiation; 0 for the 8-phase schedule), or (refusal code < 0, 0).  Pure host arithmetic."""
+    arm, st = native().gemm_nt_plan(int(M), int(N), int(K), int(lda), int(ldb), int(ldc), int(epi), int(has_aux),
+                                    int(ldaux))
+    return _plan(arm, st, gemm_nt_arms())
+
+
+def gemm_tn_plan(N, M, Bt, splits, ldd, ldh, ldg):
+    """the same for gemm_tn / gemm_tn_reduce"""
+    arm, st = native().gemm_tn_plan(int(N), int(M), int(Bt), int(splits), int(ldd), int(ldh), int(ldg))
+    return _plan(arm, st, gemm_tn_arms())
+
+
+def gemm_nt_ws(X, W, epi, out):
+    """out[M,N] = epi(X[M,K] @ W[N,K]^T) on the weight-stationary kernel (csrc/gpu/kernels_ws.hip) called
+    directly, at any M % 32 == 0.  Returns 0, or 1 with nothing launched where the kernel has no instance
+    (EPI_DACT, an (N, K) pair not instantiated, a row stride % 8); the CPU emulation refuses the same."""
+    M, K = X.shape
+    N = W.shape[0]
+    if _cpu(X):
+        if not native().gemm_nt_ws_plan(M, N, K, X.stride(0), W.stride(0), out.stride(0), epi):
+            return 1
+        out.copy_(ref_gemm_nt(X, W, epi, None))
+        return 0
+    return native().gemm_nt_ws_bf16(X.data_ptr(), X.stride(0), W.data_ptr(), W.stride(0), out.data_ptr(),
+                                    out.stride(0), M, N, K, epi, int(out.dtype == torch.float32), _stream())
+
+
+def gemm_nn(A, W, epi=EPI_NONE, aux=None, out_f32=False, out=None):
+    """C[M,N] = epi(A[M,K] @ W[K,N]), W row-major [K][N]: the NT product on W^T without the transposed
+    copy (M, N % 128, K % 64)."""
+    M, K = A.shape
+    N = W.shape[1]
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float32 if out_f32 else torch.bfloat16, device=A.device)
+    if _cpu(A):
+        out.copy_(ref_gemm_nt(A, W.t(), epi, aux))
+        return out
+    native().gemm_nn_bf16(A.data_ptr(), A.stride(0), W.data_ptr(), W.stride(0), out.data_ptr(), out.stride(0),
+                          _ptr(aux), aux.stride(0) if aux is not None else 0, M, N, K, epi,
+                          int(out.dtype == torch.float32), _stream())
+    return out
+
+
 def split_rows(Bt, splits):
     """batch rows of each split-K slice of gemm_tn: 64-row units, uneven when S does not
     divide them (csrc/gpu/kernels.h)"""
@@ -117,6 +175,8 @@ def _sum_sgd_tile(slab):
     """the slab sum of sgd_tile (csrc/gpu/kernels_misc.hip): slab 0, then slabs 1.. in four
     interleaved chains while four remain, the rest into chain 0, chain 0 + ((1 + 2) + 3)"""
     S = slab.shape[0]
+    if S == 1:  # one slab is taken as it is (a -0.0 stays -0.0)
+        return slab[0].clone()
     gend = 1 + 4 * ((S - 1) // 4)
     c = [slab[0].clone()] + [torch.zeros_like(slab[0]) for _ in range(3)]
     for k in range(1, S):
