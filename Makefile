@@ -59,6 +59,8 @@ $(BUILD)/csrc/gpu/kernels_cg.o: HIPFLAGS += -ffp-contract=off
 $(BUILD)/csrc/gpu/kernels_adam.o: HIPFLAGS += -ffp-contract=off
 # the learning-rate schedules (include/libhpnn/lrsched.h) and the scheduled step likewise
 $(BUILD)/csrc/gpu/kernels_lrsched.o: HIPFLAGS += -ffp-contract=off
+# the global-norm reduction and the clip rule (include/libhpnn/clip.h) likewise
+$(BUILD)/csrc/gpu/kernels_clip.o: HIPFLAGS += -ffp-contract=off
 
 $(LIB): $(CORE_OBJ) $(HIP_OBJ)
 	@mkdir -p $(LIBDIR)

@@ -87,6 +87,9 @@ extern "C" void _NN(deinit, conf)(nn_def *conf) {
     free(conf->lr_history);
     conf->lr_history = NULL;
     conf->n_lr_history = 0;
+    free(conf->clip_history);
+    conf->clip_history = NULL;
+    conf->n_clip_history = 0;
     conf->name = conf->f_kernel = conf->samples = conf->tests = NULL;
 }
 
@@ -211,6 +214,14 @@ extern "C" void _NN(get, lr_schedule)(nn_def *c, nn_lr_schedule *kind, DOUBLE *g
     if (lr_min) *lr_min = c->lr_min == c->lr_min ? c->lr_min : 0.0;
     if (patience) *patience = c->lr_patience ? c->lr_patience : HPNN_LR_PATIENCE;
     if (warmup) *warmup = c->warmup;
+}
+extern "C" void _NN(set, clip)(nn_def *c, DOUBLE max_norm) {
+    if (c) c->clip = max_norm;
+}
+extern "C" DOUBLE _NN(get, clip)(nn_def *c) { return c ? c->clip : 0.0; }
+extern "C" const nn_clip_record *_NN(get, clip_history)(nn_def *c, UINT *n) {
+    if (n) *n = c && c->clip_history ? c->n_clip_history : 0;
+    return c ? (const nn_clip_record *)c->clip_history : NULL;
 }
 extern "C" const DOUBLE *_NN(get, lr_history)(nn_def *c, UINT *n) {
     if (n) *n = c && c->lr_history ? c->n_lr_history : 0;
@@ -362,6 +373,12 @@ extern "C" nn_def *_NN(load, conf)(const CHAR *filename) {
             std::string u = v;
             for (auto &ch : u) ch = (char)tolower(ch);
             conf->parallel = u == "tp" ? NN_PARALLEL_TP : NN_PARALLEL_DP;
+        } else if (is("clip")) {
+            char *end = NULL;
+            const DOUBLE x = strtod(v.c_str(), &end);
+            if (v.empty() || end == v.c_str() || !hpnn_clip_valid(x))
+                CONF_FAIL("[clip] value: %s (the largest gradient norm, finite and > 0; 0: off)\n", v.c_str());
+            conf->clip = x;
         } else if (is("lr_schedule")) {
             std::string u = v;
             for (auto &ch : u) ch = (char)tolower(ch);
@@ -481,6 +498,7 @@ extern "C" void _NN(dump, conf)(nn_def *conf, FILE *fp) {
     if (conf->lr_min == conf->lr_min) _OUT(fp, "[lr_min] %.17g\n", conf->lr_min);
     if (conf->lr_patience) _OUT(fp, "[lr_patience] %u\n", conf->lr_patience);
     if (conf->warmup) _OUT(fp, "[warmup] %u\n", conf->warmup);
+    if (conf->clip > 0.0) _OUT(fp, "[clip] %.17g\n", conf->clip);
 }
 
 /* ------------------------------------------------------------------ */
@@ -709,6 +727,16 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
             return FALSE;
         }
     }
+    /* [clip]: a finite bound >= 0 (0: off); batched BP / BPM / ADAM on one device or the CPU */
+    if (!hpnn_clip_valid(conf->clip)) {
+        NN_ERROR(stderr, "[clip] %g is out of range (the largest gradient norm, finite and > 0; 0: off)\n", conf->clip);
+        return FALSE;
+    }
+    if (conf->clip > 0.0 && conf->mode == NN_MODE_BATCHED && conf->train == NN_TRAIN_CG) {
+        NN_ERROR(stderr, "[clip] is not supported by [train] CG (the line search chooses its own step); "
+                         "use [train] BP, BPM or ADAM\n");
+        return FALSE;
+    }
     HpnnTraceRange tr("nn_train_kernel");
     HpnnSamples src;
     if (!src.open(conf->samples)) {
@@ -742,6 +770,9 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
         free(conf->lr_history);
         conf->lr_history = NULL;
         conf->n_lr_history = 0;
+        free(conf->clip_history);
+        conf->clip_history = NULL;
+        conf->n_clip_history = 0;
         if (conf->keep_best && !conf->validate) {
             NN_ERROR(stderr, "[keep_best] needs [validate] N: there is no validation pass to keep the best of\n");
             return FALSE;
@@ -811,6 +842,9 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
                            "min %g patience %u warmup %u\n", gpu ? "GPU" : "CPU", lrn[lr_kind], lr, lr_gamma,
                    lr_period, lr_span, lr_end, lr_min, lr_patience, lr_warmup);
         }
+        o.clip = conf->clip;
+        if (o.clip > 0.0)
+            NN_OUT(stdout, "batched %s training: gradient clipping: max norm %g\n", gpu ? "GPU" : "CPU", o.clip);
         k->lr_loaded = 0;
         UINT ng = 1;
         _NN(get, n_gpu)(&ng);
@@ -866,6 +900,19 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
                 hpnn_metrics_emit("lr", buf);
             }
         }
+        for (UINT i = 0; ok && i < st.n_clip; i++) {
+            const hpnn_clip_record &r = st.clip_hist[i];
+            NN_OUT(stdout, "CLIP: epoch %u steps=%u clipped=%u max_norm=%.17g last_norm=%.17g\n", o.epoch0 + i + 1,
+                   r.steps, r.clipped, r.norm_max, r.norm_last);
+            if (hpnn_metrics_active()) {
+                char buf[256];
+                snprintf(buf, sizeof buf,
+                         "\"engine\": \"%s\", \"epoch\": %u, \"steps\": %u, \"clipped\": %u, \"max_norm\": %.17g, "
+                         "\"last_norm\": %.17g",
+                         gpu ? "gpu" : "cpu", o.epoch0 + i + 1, r.steps, r.clipped, r.norm_max, r.norm_last);
+                hpnn_metrics_emit("clip", buf);
+            }
+        }
         if (ok && o.sched) {
             /* the schedule state of the returned kernel: nn_dump_state saves plateau's */
             k->lr_scale = st.lrs.scale;
@@ -910,10 +957,13 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
             conf->n_cg_history = st.n_cg;
             conf->lr_history = st.lr_hist;
             conf->n_lr_history = st.n_lr;
+            conf->clip_history = st.clip_hist;
+            conf->n_clip_history = st.n_clip;
         } else {
             free(st.val);
             free(st.cg);
             free(st.lr_hist);
+            free(st.clip_hist);
         }
         if (hpnn_metrics_active()) {
             char buf[384];
@@ -947,6 +997,11 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
         static bool warned_l = false; /* no epochs here to change the rate between */
         if (!warned_l) NN_WARN(stderr, "[lr_schedule] has no effect in online mode (ignored)\n");
         warned_l = true;
+    }
+    if (conf->clip > 0.0) {
+        static bool warned_c = false; /* no minibatch gradient here whose norm could be bounded */
+        if (!warned_c) NN_WARN(stderr, "[clip] has no effect in online mode (ignored)\n");
+        warned_c = true;
     }
     if (conf->shuffle == NN_SHUFFLE_EPOCH) {
         static bool warned = false; /* no epochs here: every sample is trained to convergence once */

@@ -20,19 +20,31 @@ extern "C" void hpnn_adam_host_init(hpnn_adam_state *s, double lr, double beta1,
 
 extern "C" void hpnn_adam_host_advance(hpnn_adam_state *s) { hpnn_adam_advance(s); }
 
-extern "C" void hpnn_adam_host_update(int f64, void *W, void *M, void *V, const void *G, int S, long gstride, long n,
-                                      double scale, const hpnn_adam_state *s) {
+extern "C" void hpnn_adam_host_update_clip(int f64, void *W, void *M, void *V, const void *G, int S, long gstride,
+                                           long n, double scale, const hpnn_adam_state *s,
+                                           const hpnn_clip_state *clip) {
     if (f64) {
         const hpnn_adam_coef_f64 c = hpnn_adam_coef_f64_of(s);
+        const double cf = clip ? clip->factor : 1.0;
         double *const mv[2] = {(double *)M, (double *)V};
         hpnn_host_slab_update((double *)W, mv, true, (const double *)G, S, gstride, n, scale,
-                              [&c](double g, double *w, double *e) { hpnn_adam_elem_f64(&c, g, w, e, e + 1); });
+                              [&c, clip, cf](double g, double *w, double *e) {
+                                  hpnn_adam_elem_f64(&c, clip ? g * cf : g, w, e, e + 1);
+                              });
     } else {
         const hpnn_adam_coef_f32 c = hpnn_adam_coef_f32_of(s);
+        const float cf = clip ? (float)clip->factor : 1.f;
         float *const mv[2] = {(float *)M, (float *)V};
         hpnn_host_slab_update((float *)W, mv, true, (const float *)G, S, gstride, n, (float)scale,
-                              [&c](float g, float *w, float *e) { hpnn_adam_elem_f32(&c, g, w, e, e + 1); });
+                              [&c, clip, cf](float g, float *w, float *e) {
+                                  hpnn_adam_elem_f32(&c, clip ? g * cf : g, w, e, e + 1);
+                              });
     }
+}
+
+extern "C" void hpnn_adam_host_update(int f64, void *W, void *M, void *V, const void *G, int S, long gstride, long n,
+                                      double scale, const hpnn_adam_state *s) {
+    hpnn_adam_host_update_clip(f64, W, M, V, G, S, gstride, n, scale, s, NULL);
 }
 
 extern "C" DOUBLE hpnn_cpu_adam_step(kernel_ann *k, nn_type type, const DOUBLE *X, const DOUBLE *T, UINT B,

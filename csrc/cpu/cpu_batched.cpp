@@ -215,6 +215,18 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
                                                    : "the schedule's keys are out of range");
         return FALSE;
     }
+    /* [clip]: the state of <libhpnn/clip.h>; every step is the gradient, its global norm in the
+     * fixed order, the factor and the clipped host update (the oracle of kernels_clip.hip) */
+    const bool clip = o->clip > 0.0;
+    hpnn_clip_state cls;
+    hpnn_clip_state_init(&cls, o->clip);
+    std::vector<hpnn_clip_record> clh;
+    if (!hpnn_clip_valid(o->clip) || (clip && cg)) {
+        NN_ERROR(stderr, "[clip]: %s\n", cg ? "not supported by [train] CG (it chooses its own step); it applies to "
+                                              "BP, BPM and ADAM"
+                                            : "needs a finite value >= 0 (0 = off)");
+        return FALSE;
+    }
     const UINT B = o->batch ? o->batch : 1;
     /* [shuffle] epoch: epoch e trains on a permuted copy, position i = sample src(i) of
      * <libhpnn/shuffle.h> for (n, seed, epochs completed); one batch per epoch: nothing to do */
@@ -281,11 +293,19 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
         for (UINT s = 0; s < n && !cg; s += B) {
             UINT b = (n - s < B) ? n - s : B;
             const DOUBLE *xb = Xe + (size_t)s * k->n_inputs, *tb = Te + (size_t)s * k->n_outputs;
-            last = adam ? hpnn_cpu_adam_step(k, o->type, xb, tb, b, &ast, &hits)
-                        : hpnn_cpu_batched_step(k, o->type, xb, tb, b, lr_e, mom, o->alpha, &hits);
+            if (clip)
+                last = hpnn_cpu_clip_step(k, o->type, xb, tb, b, lr_e, mom, o->alpha, adam ? &ast : NULL, &cls, &hits);
+            else
+                last = adam ? hpnn_cpu_adam_step(k, o->type, xb, tb, b, &ast, &hits)
+                            : hpnn_cpu_batched_step(k, o->type, xb, tb, b, lr_e, mom, o->alpha, &hits);
             acc += last;
             nb++;
             samples += b;
+        }
+        if (clip) { /* the end of the epoch: its record, the counters back to zero */
+            clh.resize(clh.size() + 1);
+            unsigned int cur = 0;
+            hpnn_clip_commit(&cls, &clh.back(), &cur, 1u);
         }
         if (st) st->epoch_loss = acc / (nb ? nb : 1);
         if (hpnn_metrics_active())
@@ -360,6 +380,13 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
             st->lr_hist = (DOUBLE *)malloc(lrh.size() * sizeof(DOUBLE));
             if (!st->lr_hist) return FALSE;
             memcpy(st->lr_hist, lrh.data(), lrh.size() * sizeof(DOUBLE));
+        }
+        st->clip_hist = NULL;
+        st->n_clip = (UINT)clh.size();
+        if (!clh.empty()) {
+            st->clip_hist = (hpnn_clip_record *)malloc(clh.size() * sizeof(clh[0]));
+            if (!st->clip_hist) return FALSE;
+            memcpy(st->clip_hist, clh.data(), clh.size() * sizeof(clh[0]));
         }
         st->cg = NULL;
         st->n_cg = cg ? epochs_run : 0;

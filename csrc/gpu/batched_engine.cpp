@@ -44,6 +44,19 @@ extern "C" BOOL hpnn_gpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
         }
         return train_single(k, X, T, n, o, st);
     }
+    if (o->clip > 0.0) {
+        /* [clip] exists on one device only: the norm is reduced over one device's gradient */
+        if (o->tp) {
+            NN_ERROR(stderr, "[clip] is not supported by tensor-parallel batched training; it applies to [train] BP, "
+                             "BPM and ADAM on one GPU ([parallel] dp, 1 GPU) and to the CPU engine\n");
+            return FALSE;
+        }
+        if (lbr >= 2 || hpnn_boot_world() > 1 || o->n_gpu > 1 || (fr && fr[0] == '1') || getenv("HPNN_DP_FORCE")) {
+            NN_ERROR(stderr, "[clip] is not supported by data-parallel batched training; it applies to [train] BP, "
+                             "BPM and ADAM on one GPU and to the CPU engine\n");
+            return FALSE;
+        }
+    }
     if (o->train == NN_TRAIN_ADAM) {
         /* [train] ADAM exists on one device only: its moments and its step count live beside one
          * device's masters */

@@ -94,6 +94,16 @@ struct Batched {
     }
     hpnn_lr_state *lr_dev() const { return sched ? p.lrs_dev : nullptr; }
     hpnn_adam_state *adam_dev() const { return adam ? p.adam_dev : nullptr; }
+    /* [clip]: the plan's optimizer step becomes partials -> finalize -> update (BPlan::set_clip,
+     * behind set_adam / set_schedule and before init); the clip state is no snapshot segment */
+    bool clip = false;
+    BOOL set_clip(double max_norm, double lr) {
+        clip = p.set_clip(max_norm, lr) == 0;
+        return clip ? TRUE : FALSE;
+    }
+    BOOL clip_commit(hpnn_clip_record *hist, unsigned int *cursor, unsigned int cap) {
+        return clip && p.commit_clip(hist, cursor, cap, s) == 0;
+    }
     /* the schedule state of the live net, or of a [keep_best] snapshot (its last segment) */
     BOOL read_schedule(void *const *src, hpnn_lr_state *out) {
         HIPCHK(hipStreamSynchronize(s));
@@ -164,7 +174,8 @@ struct Batched {
         }
         if (p.cast_weights(s)) return FALSE;
         if (adam && hpnn_adam_preload(s)) return FALSE;
-        if (sched && hpnn_lrsched_preload(s)) return FALSE;
+        if ((sched || clip) && hpnn_lrsched_preload(s)) return FALSE;
+        if (clip && (hpnn_clip_preload(s) || p.prepare_clip(s))) return FALSE;
         acc = p.stats;
         gflat = p.gflat;
         memcpy(goff, p.goff, sizeof goff);
@@ -623,8 +634,9 @@ struct BatchedFP {
     /* backprop -> advance -> one update launch over every layer */
     BOOL step_adam(const XSet &xs, long row, const T *Tt, int ldt, int n_valid) {
         if (!backprop(at(xs, row), Tt, ldt, n_valid)) return FALSE;
+        if (!clip_factor(1.0 / (double)n_valid)) return FALSE;
         if (hpnn_adam_advance_dev(adam_state.get(), s) ||
-            hpnn_adam_fp(F64, adam_table.get(), L, 1.0 / (double)n_valid, adam_state.get(), s))
+            hpnn_adam_fp_clip(F64, adam_table.get(), L, 1.0 / (double)n_valid, adam_state.get(), clip_dev(), s))
             return FALSE;
         return hpnn_debug_check("batched Adam step (fp)") == 0;
     }
@@ -663,9 +675,10 @@ struct BatchedFP {
     }
     hpnn_lr_state *lr_dev() const { return sched ? sched_state.get() : nullptr; }
     hpnn_adam_state *adam_dev() const { return adam ? adam_state.get() : nullptr; }
-    BOOL init_schedule(bool momentum) {
+    /* the device state and, for BP / BPM, the table of step_sched ([clip] alone: a constant rate) */
+    BOOL init_sched_buffers(const hpnn_lr_state &cfg, bool momentum) {
         HIPCHK(sched_state.alloc(1));
-        HIPCHK(hipMemcpyAsync(sched_state.get(), &sched_cfg, sizeof sched_cfg, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(sched_state.get(), &cfg, sizeof cfg, hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
         if (!adam_req) {
             std::vector<hpnn_sched_seg> h(L);
@@ -679,13 +692,78 @@ struct BatchedFP {
                 return FALSE;
             }
         }
-        sched = true;
         return hpnn_lrsched_preload(s) == 0;
+    }
+    BOOL init_schedule(bool momentum) {
+        if (!init_sched_buffers(sched_cfg, momentum)) return FALSE;
+        sched = true;
+        return TRUE;
+    }
+
+    /* [clip] (kernels_clip.hip, docs/DESIGN.md 3.2k): the device state, the partials and the
+     * segment table of the global-norm reduction -- allocated only when clipping (init_clip, at the
+     * end of init).  The step is backprop -> partials -> finalize -> the update launch of
+     * [lr_schedule] / ADAM with the factor; plain BP / BPM runs the scheduled launch on a
+     * constant-kind state that holds lr.  Nothing here is carried from step to step: the clip
+     * state is no snapshot segment */
+    DevBuf<hpnn_gnorm_seg> clip_table;
+    DevBuf<hpnn_clip_state> clip_state;
+    DevBuf<double> clip_part;
+    int clip_count = 0;
+    bool clip = false, clip_req = false;
+    double clip_max = 0.0, clip_lr = 0.0;
+    long clip_launches = 0;
+    BOOL set_clip(double max_norm, double lr) { /* before init */
+        if (!hpnn_clip_valid(max_norm) || max_norm == 0.0) return FALSE;
+        clip_max = max_norm;
+        clip_lr = lr;
+        clip_req = true;
+        return TRUE;
+    }
+    hpnn_clip_state *clip_dev() const { return clip ? clip_state.get() : nullptr; }
+    BOOL init_clip(bool momentum) {
+        if (!adam_req && !sched_req) {
+            hpnn_lr_state c;
+            hpnn_lr_state_init(&c, HPNN_LR_CONSTANT, clip_lr, HPNN_LR_GAMMA, HPNN_LR_PERIOD, 0u, 0.0, 0.0,
+                               HPNN_LR_PATIENCE, 0u, 0u);
+            if (!init_sched_buffers(c, momentum)) return FALSE;
+        }
+        std::vector<hpnn_gnorm_seg> h(L);
+        for (int l = 0; l < L; l++) {
+            const size_t nw = (size_t)N[l] * M[l];
+            h[l] = {slab[l], (long)nw, (unsigned long long)nw, S[l], 0};
+        }
+        hpnn_clip_state c0;
+        hpnn_clip_state_init(&c0, clip_max);
+        HIPCHK(clip_table.alloc(L));
+        HIPCHK(clip_state.alloc(1));
+        HIPCHK(hipMemcpyAsync(clip_state.get(), &c0, sizeof c0, hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (hpnn_gnorm_table(F64, clip_table.get(), h.data(), L, &clip_count, s)) {
+            NN_ERROR(stderr, "[clip]: the segment table was refused (alignment or too many layers)\n");
+            return FALSE;
+        }
+        HIPCHK(clip_part.alloc(clip_count));
+        clip = true;
+        return hpnn_clip_preload(s) == 0;
+    }
+    /* behind backprop: the global norm of the gradient as the update sees it, and the factor */
+    BOOL clip_factor(double scale) {
+        if (!clip) return TRUE;
+        clip_launches += 2;
+        return hpnn_gnorm_partials(F64, 0, clip_table.get(), L, clip_count, scale, clip_part.get(), s) == 0 &&
+               hpnn_clip_finalize_dev(clip_part.get(), clip_count, clip_state.get(), s) == 0;
+    }
+    BOOL clip_commit(hpnn_clip_record *hist, unsigned int *cursor, unsigned int cap) {
+        clip_launches++;
+        return clip && hpnn_clip_commit_dev(clip_state.get(), hist, cursor, cap, s) == 0;
     }
     /* backprop -> one update launch over every layer, the rate read from the device state */
     BOOL step_sched(const XSet &xs, long row, const T *Tt, int ldt, int n_valid, double alpha, bool mom) {
         if (!backprop(at(xs, row), Tt, ldt, n_valid)) return FALSE;
-        if (hpnn_sgd_sched_fp(F64, sched_table.get(), L, 1.0 / (double)n_valid, alpha, mom ? 1 : 0, sched_state.get(), s))
+        if (!clip_factor(1.0 / (double)n_valid)) return FALSE;
+        if (hpnn_sgd_sched_fp_clip(F64, sched_table.get(), L, 1.0 / (double)n_valid, alpha, mom ? 1 : 0,
+                                   sched_state.get(), clip_dev(), s))
             return FALSE;
         return hpnn_debug_check("batched scheduled step (fp)") == 0;
     }
@@ -756,7 +834,8 @@ struct BatchedFP {
         HIPCHK(hpnn_dev_malloc(&acc, ACC_BYTES));
         HIPCHK(hipMemsetAsync(acc, 0, ACC_BYTES, s));
         if (adam_req && !init_adam(adam_cfg)) return FALSE;
-        return sched_req ? init_schedule(momentum) : TRUE;
+        if (sched_req && !init_schedule(momentum)) return FALSE;
+        return clip_req ? init_clip(momentum) : TRUE;
     }
 
     BOOL forward(const void *X, int rows) {
@@ -796,7 +875,7 @@ struct BatchedFP {
     }
 
     BOOL step(const XSet &xs, long row, const T *Tt, int ldt, int n_valid, double lr, double alpha, bool mom) {
-        if (sched) return step_sched(xs, row, Tt, ldt, n_valid, alpha, mom);
+        if (sched || clip) return step_sched(xs, row, Tt, ldt, n_valid, alpha, mom);
         if (!backprop(at(xs, row), Tt, ldt, n_valid)) return FALSE;
         const double scale = 1.0 / (double)n_valid;
         for (int l = 0; l < L; l++)

@@ -103,6 +103,57 @@ int BPlan::advance_schedule(double *hist, unsigned int *cursor, unsigned int cap
     return hpnn_lr_advance_dev(lrs_dev, adam ? adam_dev : nullptr, hist, cursor, cap, s);
 }
 
+int BPlan::set_clip(double max_norm, double lr) {
+    if (!hpnn_clip_valid(max_norm) || max_norm == 0.0) return -1;
+    hpnn_clip_state_init(&clip0, max_norm);
+    clip_lr = lr;
+    clip = true;
+    g0_fused = tn_update = tn8_side = false;
+    return 0;
+}
+
+int BPlan::clip_table(const hpnn_upd_layer *u, int n, hipStream_t s) {
+    if (!clip_tab || n < 1 || n > 16) return -1;
+    hpnn_gnorm_seg h[16];
+    bool same = n == clip_host_n_;
+    for (int i = 0; i < n; i++) {
+        h[i] = {u[i].G, u[i].gstride, (unsigned long long)u[i].N * (unsigned long long)u[i].K, u[i].S, 0};
+        same = same && h[i].g == clip_host_[i].g && h[i].gstride == clip_host_[i].gstride &&
+               h[i].n == clip_host_[i].n && h[i].S == clip_host_[i].S;
+    }
+    if (same) return 0;
+    clip_host_n_ = 0;
+    int count = 0;
+    const int r = hpnn_gnorm_table(0, clip_tab, h, n, &count, s);
+    if (r) return r;
+    if (count > clip_count) return -1; /* more blocks than "clip_part" holds */
+    for (int i = 0; i < n; i++) clip_host_[i] = h[i];
+    clip_host_n_ = n;
+    clip_blocks_ = count;
+    return 0;
+}
+
+int BPlan::prepare_clip(hipStream_t s) {
+    if (!clip) return -1;
+    hpnn_upd_layer u[16];
+    if (mode == 't' || mode == 'x' || mode == 'm') { /* the layers of step() in these modes */
+        const long n1 = (long)Np[1] * Kp[1];
+        u[0] = {W32[0], V32[0], slab[0], (long)Np[0] * Kp[0], Wb[0], Wt[0], W0f, S[0], Np[0], Kp[0]};
+        u[1] = {W32[1], V32[1], midtmp, slab_f, Wb[1], Wt[1], nullptr, mid_groups, Np[1], Kp[1]};
+        u[2] = {W32[2], V32[2], midtmp + n1, slab_f, Wb[2], Wt[2], nullptr, mid_groups, Np[2], Kp[2]};
+        return clip_table(u, 3, s);
+    }
+    for (int l = 0; l < L; l++)
+        u[l] = {W32[l], V32[l], slab[l], (long)Np[l] * Kp[l], Wb[l], Wt[l], nullptr, S[l], Np[l], Kp[l]};
+    return clip_table(u, L, s);
+}
+
+int BPlan::commit_clip(hpnn_clip_record *hist, unsigned int *cursor, unsigned int cap, hipStream_t s) {
+    if (!clip || !clip_dev) return -1;
+    clip_launches++;
+    return hpnn_clip_commit_dev(clip_dev, hist, cursor, cap, s);
+}
+
 int BPlan::configure(const int *sizes, int n_layers, int net_type, int batch_size, bool momentum_, int fused,
                      const int *splits, int mid_grid_req, bool device, std::string *err) {
     auto fail = [&](int code, const std::string &m) {
@@ -193,7 +244,18 @@ int BPlan::configure(const int *sizes, int n_layers, int net_type, int batch_siz
         add("D", l, BD_BF16, {Bp, Np[l]}, false);
     }
     if (adam) add("adam", -1, BD_F32, {(long)(sizeof(hpnn_adam_state) / 4)}, true);
-    if (sched) add("lrs", -1, BD_F32, {(long)(sizeof(hpnn_lr_state) / 4)}, true);
+    const bool const_lrs = clip && !sched && !adam; /* plain BP / BPM under [clip]: a constant rate */
+    if (const_lrs)
+        hpnn_lr_state_init(&lrs0, HPNN_LR_CONSTANT, clip_lr, HPNN_LR_GAMMA, HPNN_LR_PERIOD, 0u, 0.0, 0.0,
+                           HPNN_LR_PATIENCE, 0u, 0u);
+    if (sched || const_lrs) add("lrs", -1, BD_F32, {(long)(sizeof(hpnn_lr_state) / 4)}, true);
+    clip_count = 0;
+    if (clip) {
+        for (int l = 0; l < L; l++) clip_count += (int)hpnn_clip_blocks((unsigned long long)Np[l] * Kp[l]);
+        add("clip", -1, BD_F32, {(long)(sizeof(hpnn_clip_state) / 4)}, true);
+        add("clip_part", -1, BD_F32, {2L * clip_count}, true);
+        add("clip_tab", -1, BD_F32, {(long)(16 * sizeof(hpnn_gnorm_seg) / 4)}, true);
+    }
     add("gflat", -1, BD_F32, {(long)goff[L]}, true);
     add("Z", -1, BD_F32, {Bp, Np[L - 1]}, false);
     add("stats", -1, BD_F32, {HPNN_STAT_SLOTS, HPNN_STAT_STRIDE}, true);
@@ -237,6 +299,10 @@ void BPlan::name_pointers() {
     }
     adam_dev = (hpnn_adam_state *)buf("adam");
     lrs_dev = (hpnn_lr_state *)buf("lrs");
+    clip_dev = (hpnn_clip_state *)buf("clip");
+    clip_part = (double *)buf("clip_part");
+    clip_tab = (hpnn_gnorm_seg *)buf("clip_tab");
+    clip_host_n_ = 0;
     gflat = (float *)buf("gflat");
     Z = (float *)buf("Z");
     stats = (float *)buf("stats");
@@ -261,7 +327,8 @@ int BPlan::allocate(hipStream_t s) {
     name_pointers();
     /* adam0 is a member: it outlives the copy */
     if (adam && hipMemcpyAsync(adam_dev, &adam0, sizeof adam0, hipMemcpyHostToDevice, s) != hipSuccess) return -7;
-    if (sched && hipMemcpyAsync(lrs_dev, &lrs0, sizeof lrs0, hipMemcpyHostToDevice, s) != hipSuccess) return -7;
+    if (lrs_dev && hipMemcpyAsync(lrs_dev, &lrs0, sizeof lrs0, hipMemcpyHostToDevice, s) != hipSuccess) return -7;
+    if (clip && hipMemcpyAsync(clip_dev, &clip0, sizeof clip0, hipMemcpyHostToDevice, s) != hipSuccess) return -7;
     return 0;
 }
 
@@ -357,10 +424,18 @@ int BPlan::grad_layer(int l, const XIn &x, bool reduce, hipStream_t s) {
 }
 
 int BPlan::apply_optimizer(const hpnn_upd_layer *u, int n, float lr, float alpha, float scale, hipStream_t s) {
-    if (!adam && sched) { /* BP / BPM with the device rate: one launch (groups past HPNN_UPD_MAX layers) */
+    if (clip) { /* the global norm of the gradient as the update sees it, then the factor */
+        if (!clip_dev || !clip_part) return -1;
+        int r = clip_table(u, n, s);
+        if (!r) r = hpnn_gnorm_partials(0, 1, clip_tab, n, clip_blocks_, scale, clip_part, s);
+        if (!r) r = hpnn_clip_finalize_dev(clip_part, clip_blocks_, clip_dev, s);
+        if (r) return r;
+        clip_launches += 2;
+    }
+    if (!adam && (sched || clip)) { /* BP / BPM with the device rate: one launch (groups past HPNN_UPD_MAX layers) */
         if (!lrs_dev) return -1;
         sched_launches += (n + HPNN_UPD_MAX - 1) / HPNN_UPD_MAX;
-        return hpnn_sgd_sched_multi(u, n, alpha, scale, momentum ? 1 : 0, lrs_dev, s);
+        return hpnn_sgd_sched_multi_clip(u, n, alpha, scale, momentum ? 1 : 0, lrs_dev, clip ? clip_dev : nullptr, s);
     }
     if (!adam) return hpnn_sgd_update_multi(u, n, lr, alpha, scale, momentum ? 1 : 0, s);
     if (!adam_dev) return -1;
@@ -376,14 +451,14 @@ int BPlan::apply_optimizer(const hpnn_upd_layer *u, int n, float lr, float alpha
             a[i].u = u[i0 + i];
             a[i].A32 = A32[l];
         }
-        r = hpnn_adam_update_multi(a, cnt, scale, adam_dev, s);
+        r = hpnn_adam_update_multi_clip(a, cnt, scale, adam_dev, clip ? clip_dev : nullptr, s);
         adam_launches++;
     }
     return r;
 }
 
 int BPlan::update_layer(int l, float lr, float alpha, float scale, bool from_g, hipStream_t s) {
-    if (adam || sched) return -1; /* the whole net goes through apply_optimizer in one launch */
+    if (unfused()) return -1; /* the whole net goes through apply_optimizer in one launch */
     const float *G = from_g ? gflat + goff[l] : slab[l];
     const int Sn = from_g ? 1 : S[l];
     const long gs = from_g ? 0 : (long)Np[l] * Kp[l];
@@ -483,7 +558,7 @@ bool BPlan::tn_update_ok(int l) const {
 /* from the last layer to the first: gradient + step per layer (the deltas were all computed
  * with the pre-update weights already) */
 int BPlan::grad_and_update_layers(const XIn &x, float lr, float alpha, float scale, hipStream_t s) {
-    if (adam || sched) { /* every gradient into its slabs, then the one update over all layers */
+    if (unfused()) { /* every gradient into its slabs, then the one update over all layers */
         hpnn_upd_layer u[16];
         for (int l = L - 1; l >= 0; l--) {
             const int r = grad_layer(l, x, false, s);
@@ -567,7 +642,7 @@ int BPlan::step(const XIn &x, const int *labels, const float *T, int ldt, int n_
                                                         Wb[l], Wt[l], lr, alpha, scale, momentum ? 1 : 0, s) == 0)
                 continue;
             if ((r = grad_layer(l, x, false, s))) return r;
-            if (adam || sched || L <= HPNN_UPD_MAX)
+            if (unfused() || L <= HPNN_UPD_MAX)
                 u[nu++] = {W32[l], V32[l], slab[l], (long)Np[l] * Kp[l], Wb[l], Wt[l], nullptr, S[l], Np[l], Kp[l]};
             else if ((r = update_layer(l, lr, alpha, scale, false, s)))
                 return r;
@@ -633,7 +708,7 @@ int BPlan::grads_local(const XIn &x, const int *labels, const float *T, int ldt,
 int BPlan::xchg_step(const XIn &x, const int *labels, const float *T, int ldt, int n_valid, float lr, float alpha,
                      float scale, const hpnn_xar_view &xv, hipStream_t s) {
     if (mode != 't' && mode != 'x' && mode != 'm') return -1;
-    if (sched) return -1; /* the fused epilogue takes its rate by value */
+    if (sched || clip) return -1; /* the fused epilogue takes its rate by value and cannot clip */
     if (!fm_input(x) || !g0cnt || !g0_fused || !hpnn_gemm_fm_direct_update_ok(Kp[0], Np[0], Kp[0], Bp, S[0]) ||
         S[0] * hpnn_g0_tiles(Np[0], Kp[0]) > HPNN_XAR_MAX_BLOCKS || (long)goff[L] > xv.half)
         return -1;
@@ -716,7 +791,7 @@ int BPlan::grads_slabs(const XIn &x, const int *labels, const float *T, int ldt,
 }
 
 int BPlan::update_flat(const float *G, float lr, float alpha, float scale, hipStream_t s) {
-    if (L > HPNN_UPD_MAX && !adam && !sched) {
+    if (L > HPNN_UPD_MAX && !unfused()) {
         for (int l = 0; l < L; l++) {
             int r = hpnn_sgd_update(W32[l], V32[l], G + goff[l], 1, 0, Wb[l], Wt[l], Np[l], Kp[l], lr, alpha, scale,
                                     momentum ? 1 : 0, s);

@@ -101,6 +101,13 @@ class BPlan {
     bool sched = false;
     hpnn_lr_state lrs0;      /* the state a fresh plan starts from (allocate uploads it) */
     long sched_launches = 0; /* launches of kernels_lrsched.hip issued by this plan (tests) */
+    /* [clip] (set_clip): every optimizer step is gnorm_partials -> finalize -> update with the
+     * factor of "clip", the device hpnn_clip_state, read when the update runs */
+    bool clip = false;
+    hpnn_clip_state clip0;  /* the state a fresh plan starts from (allocate uploads it) */
+    double clip_lr = 0.0;   /* the rate of plain BP / BPM under [clip] (no schedule, no ADAM) */
+    long clip_launches = 0; /* launches of kernels_clip.hip issued by this plan (tests) */
+    int clip_count = 0;     /* entries of "clip_part": the 1024-element blocks of every layer */
     /* per-layer: the delta GEMM reads W (NN form, hpnn_gemm_nn_bf16) instead of W^T, which is
      * then not kept current (the sharded data-parallel step sets it: no transpose per update) */
     bool nn_bwd[16] = {false};
@@ -124,6 +131,23 @@ class BPlan {
     /* one hpnn_lr_advance_dev on the plan's state (and its Adam state, if any); hist / cursor /
      * cap: the device history of rates, may be null */
     int advance_schedule(double *hist, unsigned int *cursor, unsigned int cap, hipStream_t s);
+    /* [clip], before configure: gradient clipping by global norm (<libhpnn/clip.h>, docs/DESIGN.md
+     * 3.2k).  Adds the buffer specs "clip" (the device hpnn_clip_state), "clip_part" (one double per
+     * 1024-element block of every layer) and "clip_tab" (the segment table) and turns off the fused
+     * BP / BPM epilogues exactly as set_schedule does, so every mode ends in apply_optimizer:
+     * hpnn_gnorm_partials -> hpnn_clip_finalize_dev -> the update launch of ADAM / [lr_schedule]
+     * with the factor.  Plain BP / BPM runs hpnn_sgd_sched_multi on a constant-kind "lrs" that
+     * holds lr (step() / update_flat() then ignore their lr); update_layer() and xchg_step() are
+     * refused.  -1: max_norm is not a finite number > 0. */
+    int set_clip(double max_norm, double lr);
+    /* behind allocate / bind: uploads the segment table of step()'s optimizer launch (synchronises;
+     * a step whose layers differ from the uploaded table uploads its own, which a capture refuses) */
+    int prepare_clip(hipStream_t s);
+    /* one hpnn_clip_commit_dev on the plan's state, the last launch of an epoch; hist / cursor /
+     * cap: the device history of epoch records, may be null */
+    int commit_clip(hpnn_clip_record *hist, unsigned int *cursor, unsigned int cap, hipStream_t s);
+    /* the steps that are fused into a gradient launch are off: the optimizer runs on its own */
+    bool unfused() const { return adam || sched || clip; }
     /* fused: -1 auto (the fastest eligible mode), 0 per-layer only, or 't' / 'x' / 'm' / 'w'
      * (an error when not eligible); splits: per-layer split-K override (null / 0 = pick);
      * mid_grid_req: block slabs of mode 'm'; on_device = false: a host-only configuration
@@ -218,6 +242,9 @@ class BPlan {
     float *W32[16] = {0}, *V32[16] = {0}, *A32[16] = {0}, *slab[16] = {0};
     hpnn_adam_state *adam_dev = nullptr;
     hpnn_lr_state *lrs_dev = nullptr;
+    hpnn_clip_state *clip_dev = nullptr;
+    double *clip_part = nullptr;
+    hpnn_gnorm_seg *clip_tab = nullptr;
     void *Wb[16] = {0}, *Wt[16] = {0}, *H[16] = {0}, *D[16] = {0};
     float *Z = nullptr, *stats = nullptr, *vstats = nullptr, *gflat = nullptr, *midslab = nullptr, *midtmp = nullptr;
     void *W0f = nullptr;
@@ -242,6 +269,10 @@ class BPlan {
     int g0_fused_step(const XIn &x, float lr, float alpha, float scale, hipStream_t s, float *gout = nullptr,
                       const unsigned int *gsel = nullptr, long galt = 0, const hpnn_xar_view *xv = nullptr);
     const void *fm_input(const XIn &x) const;
+    /* [clip]: the table of the layers u on the device (uploaded when it differs from the last) */
+    int clip_table(const hpnn_upd_layer *u, int n, hipStream_t s);
+    hpnn_gnorm_seg clip_host_[16];
+    int clip_host_n_ = 0, clip_blocks_ = 0;
     void name_pointers();
 };
 

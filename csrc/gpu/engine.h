@@ -17,6 +17,7 @@
 #include <libhpnn/cg.h>
 #include <libhpnn/adam.h>
 #include <libhpnn/lrsched.h>
+#include <libhpnn/clip.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -76,6 +77,9 @@ typedef struct {
      * The step size of every epoch is then the state's lr (<libhpnn/lrsched.h>), not `lr` */
     UINT sched;
     hpnn_lr_state lrs;
+    /* [clip] c (single-device engines and the CPU oracle; 0: off): the gradient of every step is
+     * rescaled when its global L2 norm exceeds c (<libhpnn/clip.h>); BP, BPM and ADAM */
+    DOUBLE clip;
 } hpnn_batched_opts;
 
 /* one validation pass: the absolute epoch it followed, the mean loss per sample and the argmax
@@ -114,6 +118,10 @@ typedef struct {
     DOUBLE *lr_hist;
     UINT n_lr;
     hpnn_lr_state lrs;
+    /* [clip]: one record per epoch of the call up to the last one that counts (steps, clipped
+     * steps, the largest and the last norm), malloc'ed by the engine (the caller frees clip_hist) */
+    hpnn_clip_record *clip_hist;
+    UINT n_clip;
 } hpnn_batched_stats;
 
 /* the improvement rule of [keep_best] (one definition for every engine; the device form is
@@ -194,6 +202,31 @@ void hpnn_lr_host_plateau(hpnn_lr_state *s, double loss_sum);
  * scheduled BP / BPM element rule with lr = (T)s->lr on W and V (V may be NULL under BP) */
 void hpnn_sgd_sched_host_update(int f64, void *W, void *V, const void *G, int S, long gstride, long n, double scale,
                                 double alpha, int momentum, const hpnn_lr_state *s);
+
+/* ---- [clip] on the host (the CPU form of hpnn_amd.ops.gnorm_partials / clip_*): the rule of
+ * <libhpnn/clip.h> on host memory; f64 selects double, else float ---- */
+/* fills a fresh state (factor 1, counters 0); returns hpnn_clip_valid */
+int hpnn_clip_host_init(hpnn_clip_state *s, double max_norm);
+/* one segment: the element gs = (the slab sum, slabs 0 .. S-1 in order, or the 8-way order of the
+ * BF16 plan when interleaved) * scale, gs^2 in FP64, one double per block of 1024 elements into
+ * partials[] in the order of clip.h; returns the number of blocks */
+long hpnn_clip_host_sumsq(int f64, int interleaved, const void *G, int S, long gstride, long n, double scale,
+                          double *partials);
+/* partials[0 .. count) summed in the finalize's order, then hpnn_clip_finalize */
+void hpnn_clip_host_finalize(hpnn_clip_state *s, const double *partials, long count);
+void hpnn_clip_host_commit(hpnn_clip_state *s, hpnn_clip_record *hist, unsigned int *cursor, unsigned int cap);
+/* the update entry points with the element gs * (T)clip->factor (clip NULL: the forms above) */
+void hpnn_sgd_sched_host_update_clip(int f64, void *W, void *V, const void *G, int S, long gstride, long n,
+                                     double scale, double alpha, int momentum, const hpnn_lr_state *s,
+                                     const hpnn_clip_state *clip);
+void hpnn_adam_host_update_clip(int f64, void *W, void *M, void *V, const void *G, int S, long gstride, long n,
+                                double scale, const hpnn_adam_state *s, const hpnn_clip_state *clip);
+/* one clipped minibatch step on the CPU (FP64): the gradient, its global norm and the factor into
+ * *clip, then BP / BPM at the rate lr (momentum: k->dw allocated) or, with adam not NULL, the Adam
+ * step (advances *adam; k->dw, k->dv allocated); returns the mean loss before the update */
+DOUBLE hpnn_cpu_clip_step(kernel_ann *k, nn_type type, const DOUBLE *X, const DOUBLE *T, UINT b, DOUBLE lr,
+                          BOOL momentum, DOUBLE alpha, hpnn_adam_state *adam, hpnn_clip_state *clip,
+                          UINT *hits /* may be NULL: += argmax hits */);
 
 #ifdef __cplusplus
 }

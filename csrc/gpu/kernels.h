@@ -18,6 +18,7 @@
 #include <libhpnn/cg.h>
 #include <libhpnn/adam.h>
 #include <libhpnn/lrsched.h>
+#include <libhpnn/clip.h>
 #include <libhpnn/xar.h>
 
 #ifdef __cplusplus
@@ -506,6 +507,47 @@ int hpnn_sgd_sched_multi(const hpnn_upd_layer *layers, int n, float alpha, float
                          const hpnn_lr_state *state, hipStream_t stream);
 /* loads the unit's code object (an empty launch and a synchronise) before a capture */
 int hpnn_lrsched_preload(hipStream_t stream);
+/* ---- gradient clipping by global norm (kernels_clip.hip; [clip], rule in <libhpnn/clip.h>) ----
+ * Every launch is capturable, allocates nothing, reads the gradients only and reads / writes the
+ * DEVICE hpnn_clip_state when it runs.  Return: 0 launched, -1 refused (nothing written), -5 launch
+ * error.  A segment is one layer's gradient: n elements (linear index), S slabs gstride elements
+ * apart.  hpnn_gnorm_table checks a host table (at most 16 segments), fills first_block (segment y
+ * owns the blocks [first_block, first_block + ceil(n / 1024)) of the launch and the same entries of
+ * partials[]), stores the total into *count and copies the table to the device (synchronises:
+ * setup). */
+typedef struct {
+    const void *g;
+    long gstride;
+    unsigned long long n;
+    int S;
+    int first_block; /* filled by hpnn_gnorm_table */
+} hpnn_gnorm_seg;
+#define HPNN_GNORM_MAX_SEGS 16
+int hpnn_gnorm_table(int f64, hpnn_gnorm_seg *segs, const hpnn_gnorm_seg *host_segs, int n_segs, int *count,
+                     hipStream_t stream);
+/* one workgroup per block of 1024 elements (count = the table's total): the element gs = (the slab
+ * sum) * (T)scale -- slabs 0 .. S-1 in order from 0, or, interleaved, the 8-way order of the BF16
+ * plan's sub-tile update -- squared in FP64 and summed in the order of clip.h into partials[block] */
+int hpnn_gnorm_partials(int f64, int interleaved, const hpnn_gnorm_seg *segs, int n_segs, int count, double scale,
+                        double *partials, hipStream_t stream);
+/* one workgroup: partials[0 .. count) summed in the finalize's order, then hpnn_clip_finalize */
+int hpnn_clip_finalize_dev(const double *partials, int count, hpnn_clip_state *state, hipStream_t stream);
+/* one thread, the last launch of an epoch: hpnn_clip_commit (a full history, *cursor == cap, drops
+ * the record; hist may be NULL) */
+int hpnn_clip_commit_dev(hpnn_clip_state *state, hpnn_clip_record *hist, unsigned int *cursor, unsigned int cap,
+                         hipStream_t stream);
+/* the update launches above with the element gs * (T)clip->factor, the factor read when the launch
+ * runs; clip NULL: exactly the launches above */
+int hpnn_sgd_sched_fp_clip(int f64, const hpnn_sched_seg *segs, int n_segs, double scale, double alpha, int momentum,
+                           const hpnn_lr_state *state, const hpnn_clip_state *clip, hipStream_t stream);
+int hpnn_sgd_sched_multi_clip(const hpnn_upd_layer *layers, int n, float alpha, float scale, int momentum,
+                              const hpnn_lr_state *state, const hpnn_clip_state *clip, hipStream_t stream);
+int hpnn_adam_fp_clip(int f64, const hpnn_adam_seg *segs, int n_segs, double scale, const hpnn_adam_state *state,
+                      const hpnn_clip_state *clip, hipStream_t stream);
+int hpnn_adam_update_multi_clip(const hpnn_adam_upd_layer *layers, int n, float scale, const hpnn_adam_state *state,
+                                const hpnn_clip_state *clip, hipStream_t stream);
+/* loads the unit's code object (an empty launch and a synchronise) before a capture */
+int hpnn_clip_preload(hipStream_t stream);
 /* profiling (HPNN_TILE_TRACE=1): per-workgroup s_memtime stamps [1024][12] */
 int hpnn_mlp3_tile_trace(unsigned long long *out);
 /* HPNN_G0_TRACE=1 phase stamps of the fused G0 launch: out[512][8] */

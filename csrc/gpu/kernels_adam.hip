@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include <libhpnn/adam.h>
+#include <libhpnn/clip.h>
 
 #include "kernels.h"
 #include "upd_common.h"
@@ -40,9 +41,14 @@ struct AdamRule {
     typedef hpnn_adam_seg seg;
     typedef hpnn_adam_upd_layer layer;
     typedef hpnn_adam_state state;
-    typedef std::conditional_t<sizeof(T) == 8, hpnn_adam_coef_f64, hpnn_adam_coef_f32> coef;
+    struct coef {
+        std::conditional_t<sizeof(T) == 8, hpnn_adam_coef_f64, hpnn_adam_coef_f32> c;
+        T clipf; /* (T)clip->factor, in use when clip */
+        int clip;
+    };
     struct args {
         T scale;
+        const hpnn_clip_state *clip; /* [clip]: NULL = off */
     };
     static constexpr int NS = 2; /* the first and the second moment, always in use */
     /* a segment's arrays: the walker alone asks (the table builder has its own pointer check) */
@@ -59,17 +65,19 @@ struct AdamRule {
     }
     static __host__ __device__ const hpnn_upd_layer &base(const layer &L) { return L.u; }
     /* the coefficients the last advance left in the state */
-    static __device__ coef read(const args &, bool, const state *st) {
+    static __device__ coef read(const args &a, bool, const state *st) {
+        const T clipf = a.clip ? (T)a.clip->factor : (T)1;
         if constexpr (sizeof(T) == 8)
-            return hpnn_adam_coef_f64_of(st);
+            return {hpnn_adam_coef_f64_of(st), clipf, a.clip != nullptr};
         else
-            return hpnn_adam_coef_f32_of(st);
+            return {hpnn_adam_coef_f32_of(st), clipf, a.clip != nullptr};
     }
     static __device__ void elem(const coef &c, T g, T *w, T *e) {
+        if (c.clip) g = g * c.clipf;
         if constexpr (sizeof(T) == 8)
-            hpnn_adam_elem_f64(&c, g, w, e, e + 1);
+            hpnn_adam_elem_f64(&c.c, g, w, e, e + 1);
         else
-            hpnn_adam_elem_f32(&c, g, w, e, e + 1);
+            hpnn_adam_elem_f32(&c.c, g, w, e, e + 1);
     }
 };
 
@@ -99,14 +107,26 @@ extern "C" int hpnn_adam_table(int f64, hpnn_adam_seg *segs, const hpnn_adam_seg
     });
 }
 
+extern "C" int hpnn_adam_fp_clip(int f64, const hpnn_adam_seg *segs, int n_segs, double scale,
+                                 const hpnn_adam_state *state, const hpnn_clip_state *clip, hipStream_t stream) {
+    if ((uintptr_t)clip & 7u) return -1;
+    if (f64) return hpnn_upd::seg_walk<AdamRule<double>>(segs, n_segs, {scale, clip}, state, stream);
+    return hpnn_upd::seg_walk<AdamRule<float>>(segs, n_segs, {(float)scale, clip}, state, stream);
+}
+
 extern "C" int hpnn_adam_fp(int f64, const hpnn_adam_seg *segs, int n_segs, double scale,
                             const hpnn_adam_state *state, hipStream_t stream) {
-    if (f64) return hpnn_upd::seg_walk<AdamRule<double>>(segs, n_segs, {scale}, state, stream);
-    return hpnn_upd::seg_walk<AdamRule<float>>(segs, n_segs, {(float)scale}, state, stream);
+    return hpnn_adam_fp_clip(f64, segs, n_segs, scale, state, nullptr, stream);
+}
+
+extern "C" int hpnn_adam_update_multi_clip(const hpnn_adam_upd_layer *layers, int n, float scale,
+                                           const hpnn_adam_state *state, const hpnn_clip_state *clip,
+                                           hipStream_t stream) {
+    if (!layers || n < 1 || n > HPNN_UPD_MAX || !state || (((uintptr_t)state | (uintptr_t)clip) & 7u)) return -1;
+    return hpnn_upd::upd_tile<AdamRule<float>>(layers, n, {scale, clip}, state, stream);
 }
 
 extern "C" int hpnn_adam_update_multi(const hpnn_adam_upd_layer *layers, int n, float scale,
                                       const hpnn_adam_state *state, hipStream_t stream) {
-    if (!layers || n < 1 || n > HPNN_UPD_MAX || !state || ((uintptr_t)state & 7u)) return -1;
-    return hpnn_upd::upd_tile<AdamRule<float>>(layers, n, {scale}, state, stream);
+    return hpnn_adam_update_multi_clip(layers, n, scale, state, nullptr, stream);
 }

@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include <libhpnn/adam.h>
+#include <libhpnn/clip.h>
 #include <libhpnn/lrsched.h>
 
 #include "kernels.h"
@@ -46,10 +47,13 @@ struct SchedRule {
     struct args {
         T scale, alpha;
         int momentum;
+        const hpnn_clip_state *clip; /* [clip]: NULL = off */
     };
     struct coef {
         T lr, alpha;
         int mom;
+        T clipf; /* (T)clip->factor, in use when clip */
+        int clip;
     };
     static constexpr int NS = 1; /* the momentum: in use under BPM only (a segment's may be NULL under BP) */
     /* a segment's array: the walker alone asks (the table builder has its own pointer check) */
@@ -64,8 +68,11 @@ struct SchedRule {
     }
     static __host__ __device__ const hpnn_upd_layer &base(const layer &L) { return L; }
     /* the rate of this epoch */
-    static __device__ coef read(const args &a, bool on, const state *st) { return {(T)st->lr, a.alpha, on}; }
+    static __device__ coef read(const args &a, bool on, const state *st) {
+        return {(T)st->lr, a.alpha, on, a.clip ? (T)a.clip->factor : (T)1, a.clip != nullptr};
+    }
     static __device__ void elem(const coef &c, T g, T *w, T *e) {
+        if (c.clip) g = g * c.clipf;
         if constexpr (sizeof(T) == 8)
             hpnn_sgd_sched_elem_f64(c.lr, c.alpha, c.mom, g, w, e);
         else
@@ -133,14 +140,29 @@ extern "C" int hpnn_sgd_sched_table(int f64, hpnn_sched_seg *segs, const hpnn_sc
     return hpnn_upd::seg_table(f64, segs, host_segs, n_segs, stream, ptrs);
 }
 
+extern "C" int hpnn_sgd_sched_fp_clip(int f64, const hpnn_sched_seg *segs, int n_segs, double scale, double alpha,
+                                      int momentum, const hpnn_lr_state *state, const hpnn_clip_state *clip,
+                                      hipStream_t stream) {
+    if ((uintptr_t)clip & 7u) return -1;
+    if (f64)
+        return hpnn_upd::seg_walk<SchedRule<double>>(segs, n_segs, {scale, alpha, momentum, clip}, state, stream);
+    return hpnn_upd::seg_walk<SchedRule<float>>(segs, n_segs, {(float)scale, (float)alpha, momentum, clip}, state,
+                                                stream);
+}
+
 extern "C" int hpnn_sgd_sched_fp(int f64, const hpnn_sched_seg *segs, int n_segs, double scale, double alpha,
                                  int momentum, const hpnn_lr_state *state, hipStream_t stream) {
-    if (f64) return hpnn_upd::seg_walk<SchedRule<double>>(segs, n_segs, {scale, alpha, momentum}, state, stream);
-    return hpnn_upd::seg_walk<SchedRule<float>>(segs, n_segs, {(float)scale, (float)alpha, momentum}, state, stream);
+    return hpnn_sgd_sched_fp_clip(f64, segs, n_segs, scale, alpha, momentum, state, nullptr, stream);
+}
+
+extern "C" int hpnn_sgd_sched_multi_clip(const hpnn_upd_layer *layers, int n, float alpha, float scale, int momentum,
+                                         const hpnn_lr_state *state, const hpnn_clip_state *clip,
+                                         hipStream_t stream) {
+    if (!layers || n < 1 || n > 2 * HPNN_UPD_MAX || !state || (((uintptr_t)state | (uintptr_t)clip) & 7u)) return -1;
+    return hpnn_upd::upd_tile<SchedRule<float>>(layers, n, {scale, alpha, momentum ? 1 : 0, clip}, state, stream);
 }
 
 extern "C" int hpnn_sgd_sched_multi(const hpnn_upd_layer *layers, int n, float alpha, float scale, int momentum,
                                     const hpnn_lr_state *state, hipStream_t stream) {
-    if (!layers || n < 1 || n > 2 * HPNN_UPD_MAX || !state || ((uintptr_t)state & 7u)) return -1;
-    return hpnn_upd::upd_tile<SchedRule<float>>(layers, n, {scale, alpha, momentum ? 1 : 0}, state, stream);
+    return hpnn_sgd_sched_multi_clip(layers, n, alpha, scale, momentum, state, nullptr, stream);
 }

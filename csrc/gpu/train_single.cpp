@@ -54,6 +54,19 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
         NN_ERROR(stderr, "[lr_schedule]: the schedule's keys are out of range\n");
         return FALSE;
     }
+    /* [clip]: the global-norm reduction and the factor in front of every update launch, the epoch
+     * record filed by the last launch of every epoch; allocated only when clipping */
+    const bool clip = o->clip > 0.0;
+    if (!hpnn_clip_valid(o->clip)) {
+        NN_ERROR(stderr, "[clip]: needs a finite value >= 0 (0 = off)\n");
+        return FALSE;
+    }
+    if (clip && cg) {
+        NN_ERROR(stderr, "[clip] is not supported by [train] CG (the line search chooses its own step); it applies "
+                         "to BP, BPM and ADAM\n");
+        return FALSE;
+    }
+    if (clip && !net.set_clip(o->clip, o->lr)) return FALSE;
     if (!net.init(k, B, o->type, mom || adam, s, B % 32 == 0)) return FALSE;
     NN_OUT(stdout, "batched GPU training: %s, %d samples per step\n", Net::name(), B);
     if (mom && o->resume && !net.upload_momentum(k)) return FALSE;
@@ -68,6 +81,13 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
         HIPCHK(lrhist.alloc(o->epochs ? o->epochs : 1));
         HIPCHK(lrcur.alloc(1));
         HIPCHK(hipMemset(lrcur.get(), 0, sizeof(unsigned int)));
+    }
+    DevBuf<hpnn_clip_record> cliphist;
+    DevBuf<unsigned int> clipcur;
+    if (clip) {
+        HIPCHK(cliphist.alloc(o->epochs ? o->epochs : 1));
+        HIPCHK(clipcur.alloc(1));
+        HIPCHK(hipMemset(clipcur.get(), 0, sizeof(unsigned int)));
     }
     const int n_batches = (int)((n + B - 1) / B);
     int rows_p = (n_batches - 1) * B + net.Bp; /* last batch reads Bp rows */
@@ -186,6 +206,11 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
                 continue;
             }
             if (!net.step(xs, start, Td + (size_t)start * n_out, n_out, nv, o->lr, o->alpha, mom)) return false;
+        }
+        /* the last launch of every epoch: its clip record into the device history */
+        if (clip && !net.clip_commit(cliphist.get(), clipcur.get(), o->epochs)) {
+            NN_ERROR(stderr, "batched GPU training: the clip commit could not be launched\n");
+            return false;
         }
         return true;
     };
@@ -347,6 +372,21 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
         if (ok) lrec.resize(hb.stop && !vrec.empty() ? vsched[vrec.size() - 1] - o->epoch0 : (size_t)e);
         if (ok) ok = net.read_schedule(hb.valid ? best.dst.data() : nullptr, &lrs_out);
     }
+    /* [clip]: the history, once, up to the last epoch that counts, as the rates */
+    std::vector<hpnn_clip_record> clrec;
+    if (ok && clip) {
+        unsigned int filed = 0;
+        clrec.resize(o->epochs);
+        ok = hipStreamSynchronize(s) == hipSuccess &&
+             hipMemcpy(&filed, clipcur.get(), sizeof filed, hipMemcpyDeviceToHost) == hipSuccess &&
+             hipMemcpy(clrec.data(), cliphist.get(), clrec.size() * sizeof(hpnn_clip_record), hipMemcpyDeviceToHost) ==
+                 hipSuccess;
+        if (ok && filed < (unsigned int)e) {
+            NN_ERROR(stderr, "batched GPU training: %u clip records filed, %d epochs run\n", filed, e);
+            ok = FALSE;
+        }
+        if (ok) clrec.resize(hb.stop && !vrec.empty() ? vsched[vrec.size() - 1] - o->epoch0 : (size_t)e);
+    }
     graphs.clear();
     if (ok) ok = net.download_from(k, hb.valid ? best.dst.data() : nullptr);
     if (ok && st) {
@@ -369,6 +409,13 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
             st->lr_hist = (DOUBLE *)malloc(lrec.size() * sizeof(DOUBLE));
             if (!st->lr_hist) ok = FALSE;
             else memcpy(st->lr_hist, lrec.data(), lrec.size() * sizeof(DOUBLE));
+        }
+        st->clip_hist = NULL;
+        st->n_clip = (UINT)clrec.size();
+        if (!clrec.empty()) {
+            st->clip_hist = (hpnn_clip_record *)malloc(clrec.size() * sizeof(hpnn_clip_record));
+            if (!st->clip_hist) ok = FALSE;
+            else memcpy(st->clip_hist, clrec.data(), clrec.size() * sizeof(hpnn_clip_record));
         }
         st->val = NULL;
         st->n_val = (UINT)vrec.size();

@@ -51,7 +51,8 @@ XIn xin(uptr x, uptr xg, int u8, float scale) {
 void bind_plan(py::module_ &m) {
     py::class_<BPlan>(m, "BPlan")
         .def(py::init([](std::vector<int> sizes, int type, int batch, bool momentum, int fused,
-                         std::vector<int> splits, int mid_grid, bool device, py::object adam, py::object schedule) {
+                         std::vector<int> splits, int mid_grid, bool device, py::object adam, py::object schedule,
+                         py::object clip) {
                  auto *p = new BPlan();
                  std::string err;
                  if (sizes.size() < 2) throw std::runtime_error("BPlan: at least two layer sizes");
@@ -79,6 +80,13 @@ void bind_plan(py::module_ &m) {
                                                      "lr_end, lr_min >= 0, patience, warmup, epoch)");
                      }
                  }
+                 if (!clip.is_none()) { /* (max_norm, lr): BPlan::set_clip before configure */
+                     py::tuple a = clip.cast<py::tuple>();
+                     if (py::len(a) != 2 || p->set_clip(a[0].cast<double>(), a[1].cast<double>())) {
+                         delete p;
+                         throw std::invalid_argument("BPlan: clip = (a finite max_norm > 0, lr)");
+                     }
+                 }
                  std::vector<int> sp(sizes.size(), 0);
                  for (size_t i = 0; i < splits.size() && i < sp.size(); i++) sp[i] = splits[i];
                  const int rc = p->configure(sizes.data(), (int)sizes.size() - 1, type, batch, momentum, fused,
@@ -91,7 +99,7 @@ void bind_plan(py::module_ &m) {
              }),
              py::arg("sizes"), py::arg("type"), py::arg("batch"), py::arg("momentum"), py::arg("fused") = -1,
              py::arg("splits") = std::vector<int>(), py::arg("mid_grid") = 512, py::arg("device") = true,
-             py::arg("adam") = py::none(), py::arg("schedule") = py::none())
+             py::arg("adam") = py::none(), py::arg("schedule") = py::none(), py::arg("clip") = py::none())
         .def("config",
              [](const BPlan &p) {
                  py::dict d;
@@ -229,6 +237,16 @@ void bind_plan(py::module_ &m) {
         .def("advance_schedule",
              [](BPlan &p, uptr hist, uptr cursor, unsigned int cap, uptr s) {
                  check(p.advance_schedule((double *)P(hist), (unsigned int *)P(cursor), cap, S(s)), "advance_schedule");
+             },
+             py::arg("hist") = 0, py::arg("cursor") = 0, py::arg("cap") = 0, py::arg("stream") = 0)
+        .def_readonly("clip", &BPlan::clip)
+        .def_readonly("clip_count", &BPlan::clip_count)
+        .def_readwrite("clip_launches", &BPlan::clip_launches)
+        .def("prepare_clip", [](BPlan &p, uptr s) { check(p.prepare_clip(S(s)), "prepare_clip"); },
+             py::arg("stream") = 0)
+        .def("commit_clip",
+             [](BPlan &p, uptr hist, uptr cursor, unsigned int cap, uptr s) {
+                 check(p.commit_clip((hpnn_clip_record *)P(hist), (unsigned int *)P(cursor), cap, S(s)), "commit_clip");
              },
              py::arg("hist") = 0, py::arg("cursor") = 0, py::arg("cap") = 0, py::arg("stream") = 0)
         .def_property_readonly("nn_bwd", [](const BPlan &p) { return std::vector<bool>(p.nn_bwd, p.nn_bwd + 16); })
@@ -757,7 +775,7 @@ PYBIND11_MODULE(_native, m) {
     });
     m.def(
         "sgd_sched_multi",
-        [](py::list layers, float alpha, float scale, int momentum, uptr state, uptr stream) {
+        [](py::list layers, float alpha, float scale, int momentum, uptr state, uptr stream, uptr clip) {
             hpnn_upd_layer L[2 * HPNN_UPD_MAX];
             const int n = (int)py::len(layers);
             if (n < 1 || n > 2 * HPNN_UPD_MAX) throw std::runtime_error("sgd_sched_multi: 1..16 layers");
@@ -775,10 +793,72 @@ PYBIND11_MODULE(_native, m) {
                 L[i].N = t[8].cast<int>();
                 L[i].K = t[9].cast<int>();
             }
-            check(hpnn_sgd_sched_multi(L, n, alpha, scale, momentum, (const hpnn_lr_state *)P(state), S(stream)),
+            check(hpnn_sgd_sched_multi_clip(L, n, alpha, scale, momentum, (const hpnn_lr_state *)P(state),
+                                            (const hpnn_clip_state *)P(clip), S(stream)),
                   "sgd_sched_multi");
         },
-        "layers: [(W32, V32, G, gstride, Wbf, Wt, Wf, S, N, K)] device addresses (0 = none)");
+        py::arg("layers"), py::arg("alpha"), py::arg("scale"), py::arg("momentum"), py::arg("state"),
+        py::arg("stream"), py::arg("clip") = 0,
+        "layers: [(W32, V32, G, gstride, Wbf, Wt, Wf, S, N, K)] device addresses (0 = none); clip: a device "
+        "hpnn_clip_state (0 = none)");
+    /* [clip] (csrc/gpu/kernels_clip.hip; the host forms: csrc/cpu/cpu_clip.cpp) */
+    m.attr("CLIP_STATE_BYTES") = (int)sizeof(hpnn_clip_state);
+    m.attr("CLIP_RECORD_BYTES") = (int)sizeof(hpnn_clip_record);
+    m.attr("GNORM_SEG_BYTES") = (int)sizeof(hpnn_gnorm_seg);
+    m.def("clip_host_init", [](uptr state, double max_norm) {
+        return hpnn_clip_host_init((hpnn_clip_state *)P(state), max_norm);
+    });
+    m.def("clip_host_sumsq", [](int f64, int interleaved, uptr G, int Sn, long gstride, long n, double scale,
+                                uptr partials) {
+        return hpnn_clip_host_sumsq(f64, interleaved, P(G), Sn, gstride, n, scale, (double *)P(partials));
+    });
+    m.def("clip_host_finalize", [](uptr state, uptr partials, long count) {
+        hpnn_clip_host_finalize((hpnn_clip_state *)P(state), (const double *)P(partials), count);
+    });
+    m.def("clip_host_commit", [](uptr state, uptr hist, uptr cursor, unsigned int cap) {
+        hpnn_clip_host_commit((hpnn_clip_state *)P(state), (hpnn_clip_record *)P(hist), (unsigned int *)P(cursor), cap);
+    });
+    m.def("sgd_sched_host_update_clip", [](int f64, uptr W, uptr V, uptr G, int Sn, long gstride, long n, double scale,
+                                           double alpha, int momentum, uptr state, uptr clip) {
+        hpnn_sgd_sched_host_update_clip(f64, P(W), P(V), P(G), Sn, gstride, n, scale, alpha, momentum,
+                                        (const hpnn_lr_state *)P(state), (const hpnn_clip_state *)P(clip));
+    });
+    m.def("adam_host_update_clip", [](int f64, uptr W, uptr M, uptr V, uptr G, int Sn, long gstride, long n,
+                                      double scale, uptr state, uptr clip) {
+        hpnn_adam_host_update_clip(f64, P(W), P(M), P(V), P(G), Sn, gstride, n, scale,
+                                   (const hpnn_adam_state *)P(state), (const hpnn_clip_state *)P(clip));
+    });
+    m.def("clip_preload", [](uptr stream) { return hpnn_clip_preload(S(stream)); });
+    /* rows: (g, S, gstride, n); returns (rc, count) */
+    m.def("gnorm_table", [](int f64, uptr segs,
+                            const std::vector<std::tuple<uptr, int, long, unsigned long long>> &host, uptr stream) {
+        std::vector<hpnn_gnorm_seg> h;
+        for (const auto &t : host) h.push_back({P(std::get<0>(t)), std::get<2>(t), std::get<3>(t), std::get<1>(t), 0});
+        int count = 0;
+        const int rc = hpnn_gnorm_table(f64, (hpnn_gnorm_seg *)P(segs), h.data(), (int)h.size(), &count, S(stream));
+        return std::make_pair(rc, count);
+    });
+    m.def("gnorm_partials", [](int f64, int interleaved, uptr segs, int n_segs, int count, double scale, uptr partials,
+                               uptr stream) {
+        return hpnn_gnorm_partials(f64, interleaved, (const hpnn_gnorm_seg *)P(segs), n_segs, count, scale,
+                                   (double *)P(partials), S(stream));
+    });
+    m.def("clip_finalize", [](uptr partials, int count, uptr state, uptr stream) {
+        return hpnn_clip_finalize_dev((const double *)P(partials), count, (hpnn_clip_state *)P(state), S(stream));
+    });
+    m.def("clip_commit", [](uptr state, uptr hist, uptr cursor, unsigned int cap, uptr stream) {
+        return hpnn_clip_commit_dev((hpnn_clip_state *)P(state), (hpnn_clip_record *)P(hist),
+                                    (unsigned int *)P(cursor), cap, S(stream));
+    });
+    m.def("sgd_sched_fp_clip", [](int f64, uptr segs, int n_segs, double scale, double alpha, int momentum, uptr state,
+                                  uptr clip, uptr stream) {
+        return hpnn_sgd_sched_fp_clip(f64, (const hpnn_sched_seg *)P(segs), n_segs, scale, alpha, momentum,
+                                      (const hpnn_lr_state *)P(state), (const hpnn_clip_state *)P(clip), S(stream));
+    });
+    m.def("adam_fp_clip", [](int f64, uptr segs, int n_segs, double scale, uptr state, uptr clip, uptr stream) {
+        return hpnn_adam_fp_clip(f64, (const hpnn_adam_seg *)P(segs), n_segs, scale, (const hpnn_adam_state *)P(state),
+                                 (const hpnn_clip_state *)P(clip), S(stream));
+    });
     m.def("mlp3_tile_grid", [](int Bp, int grid) { return hpnn_mlp3_tile_grid(Bp, grid); });
     m.def("mlp3_tile_trace", []() {
         std::vector<unsigned long long> v(1024 * 12);
@@ -840,7 +920,7 @@ PYBIND11_MODULE(_native, m) {
         "layers: [(W32, V32, G, gstride, Wbf, Wt, Wf, S, N, K)] device addresses (0 = none)");
     m.def(
         "adam_update_multi",
-        [](py::list layers, float scale, uptr state, uptr stream) {
+        [](py::list layers, float scale, uptr state, uptr stream, uptr clip) {
             hpnn_adam_upd_layer L[HPNN_UPD_MAX];
             const int n = (int)py::len(layers);
             if (n < 1 || n > HPNN_UPD_MAX) throw std::runtime_error("adam_update_multi: 1..8 layers");
@@ -859,10 +939,13 @@ PYBIND11_MODULE(_native, m) {
                 L[i].u.N = t[9].cast<int>();
                 L[i].u.K = t[10].cast<int>();
             }
-            check(hpnn_adam_update_multi(L, n, scale, (const hpnn_adam_state *)P(state), S(stream)),
+            check(hpnn_adam_update_multi_clip(L, n, scale, (const hpnn_adam_state *)P(state),
+                                              (const hpnn_clip_state *)P(clip), S(stream)),
                   "adam_update_multi");
         },
-        "layers: [(W32, V32, A32, G, gstride, Wbf, Wt, Wf, S, N, K)] device addresses (Wf: 0 = none)");
+        py::arg("layers"), py::arg("scale"), py::arg("state"), py::arg("stream"), py::arg("clip") = 0,
+        "layers: [(W32, V32, A32, G, gstride, Wbf, Wt, Wf, S, N, K)] device addresses (Wf: 0 = none); clip: a "
+        "device hpnn_clip_state (0 = none)");
     /* ---- communication layer (include/libhpnn/comm.h) ---- */
     m.def("comm_available", []() { return hpnn_comm_available(); });
     m.def("comm_unique_id", []() {

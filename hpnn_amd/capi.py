@@ -32,6 +32,12 @@ class CgRecord(ctypes.Structure):
                 ("alpha", ctypes.c_double), ("trial", ctypes.c_uint), ("flags", ctypes.c_uint)]
 
 
+class ClipRecord(ctypes.Structure):
+    """nn_clip_record (= hpnn_clip_record)"""
+    _fields_ = [("steps", ctypes.c_uint), ("clipped", ctypes.c_uint), ("norm_max", ctypes.c_double),
+                ("norm_last", ctypes.c_double)]
+
+
 def lib():
     global _LIB, _LIBC
     if _LIB is None:
@@ -72,6 +78,8 @@ def lib():
                                           ctypes.POINTER(u), ctypes.POINTER(d), ctypes.POINTER(d), ctypes.POINTER(u),
                                           ctypes.POINTER(u)]),
             "nn_get_lr_history": (ctypes.POINTER(d), [vp, ctypes.POINTER(u)]),
+            "nn_set_clip": (None, [vp, d]), "nn_get_clip": (d, [vp]),
+            "nn_get_clip_history": (ctypes.POINTER(ClipRecord), [vp, ctypes.POINTER(u)]),
             "nn_return_last_pass": (u, []), "nn_return_last_total": (u, []),
             "nn_return_version": (cp, []), "nn_return_type": (i, [vp]), "nn_return_train": (i, [vp]),
             "nn_dump_state": (i, [vp, cp]), "nn_load_state": (i, [vp, cp]), "nn_return_epochs_done": (u, [vp]),
@@ -128,7 +136,7 @@ class Network:
 
     # configuration
     def set(self, mode=None, dtype=None, device=None, batch=None, epochs=None, lr=None, momentum=None, seed=None,
-            shuffle=None, validate=None, keep_best=None, patience=None, adam=None, lr_schedule=None):
+            shuffle=None, validate=None, keep_best=None, patience=None, adam=None, lr_schedule=None, clip=None):
         if mode is not None:
             self.L.nn_set_mode(self.ptr, NN_MODE[mode])
         if dtype is not None:
@@ -171,7 +179,25 @@ class Network:
             self.L.nn_set_lr_schedule(self.ptr, NN_LR_SCHEDULE[cur["kind"]], float(cur["gamma"]), int(cur["period"]),
                                       int(cur["span"]), float(cur["lr_end"]), float(cur["lr_min"]),
                                       int(cur["patience"]), int(cur["warmup"]))
+        if clip is not None:  # c: batched training rescales a gradient whose global L2 norm exceeds c (0 = off)
+            c = float(clip)
+            if not (c >= 0.0 and c != float("inf")):
+                raise ValueError(f"clip: {clip!r} (a finite norm > 0; 0 turns it off)")
+            self.L.nn_set_clip(self.ptr, c)
         return self
+
+    @property
+    def clip(self):
+        """the [clip] bound a training call would use (0.0: off)"""
+        return float(self.L.nn_get_clip(self.ptr))
+
+    def clip_history(self):
+        """one dict per epoch of the last train() call under [clip]: steps, clipped (the steps whose
+        gradient was rescaled), norm_max, norm_last; empty without [clip]"""
+        m = ctypes.c_uint()
+        r = self.L.nn_get_clip_history(self.ptr, ctypes.byref(m))
+        return [{"steps": r[i].steps, "clipped": r[i].clipped, "norm_max": r[i].norm_max, "norm_last": r[i].norm_last}
+                for i in range(m.value)]
 
     @property
     def lr_schedule(self):

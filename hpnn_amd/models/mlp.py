@@ -87,11 +87,16 @@ class MLP:
     the `lr` argument): the plan keeps the state `lr_state` ([12] float64, ops.read_lr_state), every
     step reads its rate from it and ignores train_step's lr, and the caller runs advance_schedule()
     before the first step of every epoch (and ops.lr_plateau behind a validation pass).
+    clip: None | c > 0 (include/libhpnn/clip.h): every optimizer step is the global norm of the
+    gradient as the update sees it (ops.gnorm_partials over the padded slabs, in the plan's 8-way
+    slab order), ops.clip_finalize into `clip_state` ([8] float64, ops.read_clip_state) and the
+    update with the factor.  Plain BP / BPM then steps at the constructor's `lr` (train_step's lr is
+    ignored, as under a schedule).  commit_clip() closes an epoch.
     """
 
     def __init__(self, sizes, net_type="SNN", batch=256, device="cuda", momentum=False, weights=None, seed=10958,
                  init="reference", splits=None, fused=None, mid_grid=512, optimizer="sgd", lr=0.001,
-                 betas=(0.9, 0.999), eps=1e-8, decay=0.0, lr_schedule=None):
+                 betas=(0.9, 0.999), eps=1e-8, decay=0.0, lr_schedule=None, clip=None):
         self.sizes = list(sizes)
         self.L = len(sizes) - 1
         self.type = TYPES[net_type] if isinstance(net_type, str) else int(net_type)
@@ -115,11 +120,17 @@ class MLP:
             kind = ops.LR_KIND[d["kind"]] if isinstance(d["kind"], str) else int(d["kind"])
             sched_cfg = (kind, float(d["lr"]), float(d["gamma"]), int(d["period"]), int(d["span"]), float(d["lr_end"]),
                          float(d["lr_min"]), int(d["patience"]), int(d["warmup"]), int(d["epoch"]))
+        self.clip = clip is not None and float(clip) != 0.0
+        clip_cfg = None
+        if self.clip:
+            if not (float(clip) > 0.0 and float(clip) != float("inf")):
+                raise ValueError(f"clip: {clip!r} (a finite norm > 0)")
+            clip_cfg = (float(clip), float(lr))
         on_gpu = self.device.type == "cuda"
         req = -1 if fused is None or fused is True else (0 if fused is False else ord({"mid": "m"}.get(fused, fused)))
         try:
             self.plan = native().BPlan(self.sizes, self.type, int(batch), bool(momentum), req, list(splits or []),
-                                       int(mid_grid), on_gpu, adam_cfg, sched_cfg)
+                                       int(mid_grid), on_gpu, adam_cfg, sched_cfg, clip_cfg)
         except ValueError as e:
             raise ValueError(f"fused={fused!r}: {e}") from None
         cfg = self.plan.config()
@@ -150,6 +161,16 @@ class MLP:
         if self.sched:  # the plan's "lrs" buffer is the hpnn_lr_state itself
             self.lr_state = b[("lrs", -1)].view(torch.float64)
             self.lr_state.copy_(ops.lr_state(sched_cfg[0], *sched_cfg[1:]))
+        self.clip_state = self.clip_part = None
+        if self.clip:  # the plan's "clip" buffer is the hpnn_clip_state itself
+            self.clip_state = b[("clip", -1)].view(torch.float64)
+            self.clip_state.copy_(ops.clip_state(clip_cfg[0]))
+            self.clip_part = b[("clip_part", -1)].view(torch.float64)
+            if not (self.sched or self.adam):  # plain BP / BPM: the scheduled launch at a constant rate
+                self.lr_state = b[("lrs", -1)].view(torch.float64)
+                self.lr_state.copy_(ops.lr_state("constant", clip_cfg[1]))
+            if on_gpu:
+                self.plan.prepare_clip(_stream())
         self.Wb = [b[("Wb", l)] for l in range(self.L)]
         self.Wt = [b[("Wt", l)] for l in range(self.L)]
         self.slab = [b[("slab", l)] for l in range(self.L)]
@@ -388,6 +409,9 @@ class MLP:
         if self.sched:
             raise RuntimeError("update_layer: a scheduled plan updates every layer in one launch that reads the "
                                "device rate (train_step / update_all)")
+        if self.clip:
+            raise RuntimeError("update_layer: a clipping plan needs every layer's gradient for the norm and updates "
+                               "them in one launch (train_step / update_all)")
         if self._gpu:
             self.plan.update_layer(l, float(lr), float(alpha), float(scale), bool(from_G), _stream())
             return
@@ -403,7 +427,7 @@ class MLP:
         if self.adam:
             self._adam_update(scale, from_G=True)
             return
-        if self.sched:
+        if self.sched or self.clip:
             self._sched_update(alpha, scale, from_G=True)
             return
         for l in range(self.L):
@@ -411,21 +435,44 @@ class MLP:
 
     def _adam_update(self, scale, from_G=False):
         """CPU emulation of the plan's optimizer under Adam: the advance, then every layer"""
+        self._clip_factor(scale, from_G)
         ops.adam_advance(self.adam_state)
         ops.adam_update_multi([(self.W32[l], self.V32[l], self.A32[l], self.G[l] if from_G else self.slab[l],
                                 self.Wb[l], self.Wt[l], self.W0f if l == 0 else None) for l in range(self.L)],
-                              self.adam_state, scale)
+                              self.adam_state, scale, clip=self.clip_state)
 
     def _sched_update(self, alpha, scale, from_G=False):
-        """CPU emulation of the plan's BP / BPM step under a schedule: every layer, the state's rate"""
+        """CPU emulation of the plan's BP / BPM step under a schedule or [clip]: every layer, the
+        state's rate"""
+        self._clip_factor(scale, from_G)
         ops.sgd_sched_multi([(self.W32[l], self.V32[l], self.G[l] if from_G else self.slab[l], self.Wb[l], self.Wt[l],
                               self.W0f if l == 0 else None) for l in range(self.L)],
-                            self.lr_state, alpha=alpha, scale=scale, momentum=self.momentum)
+                            self.lr_state, alpha=alpha, scale=scale, momentum=self.momentum, clip=self.clip_state)
+
+    def _clip_factor(self, scale, from_G=False):
+        """CPU emulation of the plan's norm launches: the partials of every layer's padded gradient in
+        the plan's slab order, then the finalize into clip_state"""
+        if not self.clip:
+            return
+        t = ops.GnormTable([(self.G[l] if from_G else self.slab[l]).reshape(-1, self.Np[l] * self.Kp[l])
+                            for l in range(self.L)], interleaved=True)
+        ops.gnorm_partials(t, self.clip_part, scale)
+        ops.clip_finalize(self.clip_part, t.count, self.clip_state)
+
+    def commit_clip(self, hist=None, cursor=None):
+        """the last launch of an epoch: the epoch's clip record appended to hist at cursor when given
+        (ops.clip_history), the counters of clip_state zeroed (ops.clip_commit)"""
+        if not self.clip:
+            raise RuntimeError("commit_clip: the model does not clip")
+        if self._gpu:
+            self.plan.commit_clip(_p(hist), _p(cursor), hist.shape[0] if hist is not None else 0, _stream())
+        else:
+            ops.clip_commit(self.clip_state, hist, cursor)
 
     def advance_schedule(self, hist=None, cursor=None):
         """the first launch of an epoch: the rate of the next epoch into lr_state (and, under Adam,
         into adam_state), appended to hist at cursor when given (ops.lr_advance)"""
-        if not self.sched:
+        if not self.sched:  # [clip] alone keeps a constant-rate state that nothing advances
             raise RuntimeError("advance_schedule: the model has no lr_schedule")
         if self._gpu:
             self.plan.advance_schedule(_p(hist), _p(cursor), hist.shape[0] if hist is not None else 0, _stream())
@@ -487,11 +534,11 @@ class MLP:
             if l > 0:
                 self.backward_layer(l)  # pre-update W_l^T, before layer l's step below
             self.grad_layer(l, X)
-            if not (self.adam or self.sched):
+            if not (self.adam or self.sched or self.clip):
                 self.update_layer(l, lr, alpha, scale)
         if self.adam:
             self._adam_update(scale)
-        elif self.sched:
+        elif self.sched or self.clip:
             self._sched_update(alpha, scale)
 
     def predict(self, X, n_valid=None):

@@ -90,27 +90,41 @@ def adam_step(W, M, V, G, state, advance=True):
         w.copy_(w + c(c1) * (m / (root / torch.full_like(v, s2) + c(state["eps"]))))
 
 
-def batched_step(weights, X, T, net_type, lr, momentum=None, alpha=0.2, adam=None):
+def clip_coefficient(G, max_norm):
+    """gradient clipping by global norm, the independent form: the L2 norm over every layer's
+    gradient (torch.linalg.vector_norm) and the coefficient min(1, max_norm / norm).  Returns
+    (coefficient, norm) as floats; a NaN norm gives 1."""
+    norm = float(torch.linalg.vector_norm(torch.cat([g.reshape(-1).double() for g in G])))
+    return (max_norm / norm if norm > max_norm else 1.0), norm
+
+
+def batched_step(weights, X, T, net_type, lr, momentum=None, alpha=0.2, adam=None, clip=None, norms=None):
     """In-place minibatch step; returns the mean loss before the update.
     momentum: list of dW tensors (BPM) or None (BP).  adam: (M, V, state) -- lists of moment
-    tensors and an adam_new_state dict -- selects adam_step (lr, alpha are then unused)."""
+    tensors and an adam_new_state dict -- selects adam_step (lr, alpha are then unused).
+    clip: None | max_norm -- the whole gradient is multiplied by clip_coefficient first; norms: a
+    list the step's gradient norm is appended to."""
     hs = forward(weights, X, net_type)
     loss = loss_per_sample(hs[-1], T, net_type).mean()
     d = deltas(weights, hs, T, net_type)
     B = X.shape[0]
+    G = [d[l].t() @ (X if l == 0 else hs[l - 1]) / B for l in range(len(weights))]
+    if clip is not None or norms is not None:
+        coef, norm = clip_coefficient(G, float("inf") if clip is None else clip)
+        if norms is not None:
+            norms.append(norm)
+        if clip is not None:
+            G = [g * coef for g in G]
     if adam is not None:
-        G = [d[l].t() @ (X if l == 0 else hs[l - 1]) / B for l in range(len(weights))]
         adam_step(weights, adam[0], adam[1], G, adam[2])
         return loss
     for l, W in enumerate(weights):
-        hin = X if l == 0 else hs[l - 1]
-        G = d[l].t() @ hin / B
         if momentum is not None:
-            momentum[l] += lr * G
+            momentum[l] += lr * G[l]
             W += momentum[l]
             momentum[l] *= alpha
         else:
-            W += lr * G
+            W += lr * G[l]
     return loss
 
 

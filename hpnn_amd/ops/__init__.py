@@ -1295,18 +1295,20 @@ class AdamTable(_SegTable):
     name, keys, width, entry = "AdamTable", ("m", "v"), 8, "adam_table"
 
 
-def adam_update_fp(table, state, scale=1.0):
+def adam_update_fp(table, state, scale=1.0, clip=None):
     """per segment g = (slab[0] + ... + slab[S-1]) * scale in slab order, then the Adam rule of
     include/libhpnn/adam.h on w, m, v in the tensors' dtype with the coefficients the last
     adam_advance left in the state, read when the launch runs: one capturable launch for the whole
-    table (csrc/gpu/kernels_adam.hip).  CPU tensors: the host entry point."""
+    table (csrc/gpu/kernels_adam.hip).  clip: a clip state (clip_state) -- the rule then sees
+    g * factor, the factor of the last clip_finalize read when the launch runs.  CPU tensors: the
+    host entry point."""
     if table.dev is None:
         for r in table.rows:
-            native().adam_host_update(table.f64, r[0], r[1], r[2], r[3], r[4], r[5], r[6], float(scale),
-                                      state.data_ptr())
+            native().adam_host_update_clip(table.f64, r[0], r[1], r[2], r[3], r[4], r[5], r[6], float(scale),
+                                           state.data_ptr(), _ptr(clip))
         return
-    _cg_rc(native().adam_fp(table.f64, table.dev.data_ptr(), len(table), float(scale), state.data_ptr(), _stream()),
-           "adam_update_fp")
+    _cg_rc(native().adam_fp_clip(table.f64, table.dev.data_ptr(), len(table), float(scale), state.data_ptr(),
+                                 _ptr(clip), _stream()), "adam_update_fp")
 
 
 def adam_slab_sum(G):
@@ -1326,20 +1328,21 @@ def adam_slab_sum(G):
     return g
 
 
-def adam_update_multi(layers, state, scale=1.0):
+def adam_update_multi(layers, state, scale=1.0, clip=None):
     """All layers' Adam steps in one launch (the BF16 plan's update, csrc/gpu/kernels_adam.hip).
     layers: list of (W32, V32, A32, G, Wbf, Wt, Wf) with the FP32 masters W32, first moment V32 and
     second moment A32 [N, K], G [S, N, K] (or a strided view) or [N, K]; Wf may be None.  The
     coefficients are those the last adam_advance left in the state, read when the launch runs.
-    CPU tensors: the slabs summed in the kernel's order, then the host entry point of
-    include/libhpnn/adam.h and the BF16 copies of the emulation."""
+    clip: a clip state -- the rule sees g * factor.  CPU tensors: the slabs summed in the kernel's
+    order, then the host entry point of include/libhpnn/adam.h and the BF16 copies of the
+    emulation."""
     if _cpu(layers[0][0]):
         for W32, V32, A32, G, Wbf, Wt, Wf in layers:
             g = adam_slab_sum(G.float()).contiguous()
             if not (W32.is_contiguous() and V32.is_contiguous() and A32.is_contiguous()):
                 raise ValueError("adam_update_multi: contiguous W32, V32, A32")
-            native().adam_host_update(0, W32.data_ptr(), V32.data_ptr(), A32.data_ptr(), g.data_ptr(), 1, 0,
-                                      W32.numel(), float(scale), state.data_ptr())
+            native().adam_host_update_clip(0, W32.data_ptr(), V32.data_ptr(), A32.data_ptr(), g.data_ptr(), 1, 0,
+                                           W32.numel(), float(scale), state.data_ptr(), _ptr(clip))
             cast_weights(W32, Wbf, Wt, Wf)
         return
     desc = []
@@ -1349,7 +1352,7 @@ def adam_update_multi(layers, state, scale=1.0):
         gstride = G.stride(0) if G.dim() == 3 else 0
         desc.append((W32.data_ptr(), V32.data_ptr(), A32.data_ptr(), G.data_ptr(), gstride, Wbf.data_ptr(),
                      Wt.data_ptr(), _ptr(Wf), S, N, K))
-    native().adam_update_multi(desc, float(scale), state.data_ptr(), _stream())
+    native().adam_update_multi(desc, float(scale), state.data_ptr(), _stream(), _ptr(clip))
 
 
 # --------------------------------------------------------------------------- [lr_schedule]
@@ -1455,34 +1458,38 @@ class SgdSchedTable(_SegTable):
         return (int(self.momentum),)
 
 
-def sgd_sched_fp(table, state, scale=1.0, alpha=0.0):
+def sgd_sched_fp(table, state, scale=1.0, alpha=0.0, clip=None):
     """per segment g = (slab[0] + ... + slab[S-1]) * scale in slab order, then the scheduled BP
     (w += lr g) or BPM (v += lr g; w += v; v *= alpha) step of include/libhpnn/lrsched.h in the
     tensors' dtype with lr = the state's rate, read when the launch runs: one capturable launch for
-    the whole table (csrc/gpu/kernels_lrsched.hip).  CPU tensors: the host entry point."""
+    the whole table (csrc/gpu/kernels_lrsched.hip).  clip: a clip state (clip_state) -- the rule
+    then sees g * factor, the factor of the last clip_finalize read when the launch runs.  CPU
+    tensors: the host entry point."""
     if table.dev is None:
         for r in table.rows:
-            native().sgd_sched_host_update(table.f64, r[0], r[1], r[2], r[3], r[4], r[5], float(scale), float(alpha),
-                                           int(table.momentum), state.data_ptr())
+            native().sgd_sched_host_update_clip(table.f64, r[0], r[1], r[2], r[3], r[4], r[5], float(scale),
+                                                float(alpha), int(table.momentum), state.data_ptr(), _ptr(clip))
         return
-    _cg_rc(native().sgd_sched_fp(table.f64, table.dev.data_ptr(), len(table), float(scale), float(alpha),
-                                 int(table.momentum), state.data_ptr(), _stream()), "sgd_sched_fp")
+    _cg_rc(native().sgd_sched_fp_clip(table.f64, table.dev.data_ptr(), len(table), float(scale), float(alpha),
+                                      int(table.momentum), state.data_ptr(), _ptr(clip), _stream()), "sgd_sched_fp")
 
 
-def sgd_sched_multi(layers, state, alpha=0.0, scale=1.0, momentum=False):
+def sgd_sched_multi(layers, state, alpha=0.0, scale=1.0, momentum=False, clip=None):
     """All layers' BP / BPM steps in one launch with the rate read from the schedule state (the
     BF16 plan's scheduled update, csrc/gpu/kernels_lrsched.hip).  layers: list of (W32, V32, G, Wbf,
     Wt, Wf) with the FP32 masters W32 and momentum V32 [N, K] (V32 may be None under BP), G [S, N,
     K] (or a strided view) or [N, K]; Wf may be None.  More than 8 layers go in groups of 8.  The
-    slabs are summed in the order of adam_slab_sum.  CPU tensors: that sum, then the host entry
-    point of include/libhpnn/lrsched.h and the BF16 copies of the emulation."""
+    slabs are summed in the order of adam_slab_sum.  clip: a clip state -- the rule sees
+    g * factor.  CPU tensors: that sum, then the host entry point of include/libhpnn/lrsched.h and
+    the BF16 copies of the emulation."""
     if _cpu(layers[0][0]):
         for W32, V32, G, Wbf, Wt, Wf in layers:
             g = adam_slab_sum(G.float()).contiguous()
             if not (W32.is_contiguous() and (V32 is None or V32.is_contiguous())):
                 raise ValueError("sgd_sched_multi: contiguous W32, V32")
-            native().sgd_sched_host_update(0, W32.data_ptr(), _ptr(V32), g.data_ptr(), 1, 0, W32.numel(),
-                                           float(scale), float(alpha), int(bool(momentum)), state.data_ptr())
+            native().sgd_sched_host_update_clip(0, W32.data_ptr(), _ptr(V32), g.data_ptr(), 1, 0, W32.numel(),
+                                                float(scale), float(alpha), int(bool(momentum)), state.data_ptr(),
+                                                _ptr(clip))
             cast_weights(W32, Wbf, Wt, Wf)
         return
     desc = []
@@ -1492,7 +1499,145 @@ def sgd_sched_multi(layers, state, alpha=0.0, scale=1.0, momentum=False):
         gstride = G.stride(0) if G.dim() == 3 else 0
         desc.append((W32.data_ptr(), _ptr(V32), G.data_ptr(), gstride, Wbf.data_ptr(), Wt.data_ptr(), _ptr(Wf), S,
                      N, K))
-    native().sgd_sched_multi(desc, float(alpha), float(scale), int(bool(momentum)), state.data_ptr(), _stream())
+    native().sgd_sched_multi(desc, float(alpha), float(scale), int(bool(momentum)), state.data_ptr(), _stream(),
+                             _ptr(clip))
+
+
+# --------------------------------------------------------------------------- [clip]
+_CLIP_D = ("max_norm", "sumsq", "norm", "factor", "norm_max", "norm_last")  # float64 words 0..5 of hpnn_clip_state
+_CLIP_U = ("steps", "clipped")  # uint32 words 12..13
+CLIP_BLOCK = 1024  # elements of one partial (HPNN_CLIP_BLOCK)
+
+
+def clip_state(max_norm, device="cpu"):
+    """a fresh hpnn_clip_state (include/libhpnn/clip.h) as [8] float64 (64 bytes): max_norm, sumsq,
+    norm, factor (1), norm_max, norm_last, then the uint32 words steps, clipped and two of padding.
+    Raises unless max_norm is finite and >= 0."""
+    st = torch.zeros(8, dtype=torch.float64)
+    if not native().clip_host_init(st.data_ptr(), float(max_norm)):
+        raise ValueError("clip_state: a finite max_norm >= 0")
+    return st.to(device)
+
+
+def read_clip_state(state):
+    """the clip state as a dict (synchronises); the counters are ints"""
+    s = state.cpu().contiguous()
+    out = {k: float(s[i]) for i, k in enumerate(_CLIP_D)}
+    u = s.view(torch.int32)
+    out.update({k: int(u[12 + i]) & 0xffffffff for i, k in enumerate(_CLIP_U)})
+    return out
+
+
+def write_clip_state(state, **kw):
+    """set fields of a clip state (names of read_clip_state); returns the state"""
+    s = state.cpu().clone()
+    u = s.view(torch.int32)
+    for k, v in kw.items():
+        if k in _CLIP_U:
+            v = int(v) & 0xffffffff
+            u[12 + _CLIP_U.index(k)] = v - (1 << 32) if v >= 1 << 31 else v
+        else:
+            s[_CLIP_D.index(k)] = float(v)
+    state.copy_(s)
+    return state
+
+
+def clip_history(cap, device="cpu"):
+    """an empty epoch history for clip_commit: (hist [cap, 3] float64 -- per record the uint32 words
+    steps, clipped, then norm_max, norm_last -- and cursor [1] int32)"""
+    return torch.zeros(cap, 3, dtype=torch.float64, device=device), torch.zeros(1, dtype=torch.int32, device=device)
+
+
+def read_clip_history(hist, cursor):
+    """the records filed so far as dicts (synchronises)"""
+    h, c = hist.cpu().contiguous(), int(cursor.cpu()[0])
+    u = h.view(torch.int32).reshape(-1, 6)
+    return [{"steps": int(u[i, 0]) & 0xffffffff, "clipped": int(u[i, 1]) & 0xffffffff, "norm_max": float(h[i, 1]),
+             "norm_last": float(h[i, 2])} for i in range(c)]
+
+
+class GnormTable:
+    """the segment table of gnorm_partials (csrc/gpu/kernels_clip.hip): one segment per layer, each
+    a slab tensor [S, n] (element stride 1, any row stride >= n) or [n], float64 or float32, all of
+    one dtype and device; at most 16.  `interleaved` selects the slab order: False the FP64 / FP32
+    engines' (slabs 0 .. S-1 in order), True the BF16 plan's 8-way order (adam_slab_sum).  Segment
+    y owns the entries [first[y], first[y] + ceil(n / 1024)) of the partials; `count` is their
+    total.  Device tensors: uploaded once (a [n, 4] int64 device tensor; the table keeps the slabs
+    alive)."""
+
+    def __init__(self, slabs, interleaved=False):
+        self.slabs = [s if s.dim() == 2 else s.unsqueeze(0) for s in slabs]
+        if not 1 <= len(self.slabs) <= 16:
+            raise ValueError("GnormTable: 1..16 segments")
+        s0 = self.slabs[0]
+        self.dtype, self.device, self.interleaved = s0.dtype, s0.device, bool(interleaved)
+        if self.dtype not in (torch.float64, torch.float32):
+            raise ValueError("GnormTable: float64 or float32 tensors")
+        self.f64 = int(self.dtype == torch.float64)
+        self.rows, self.first, count = [], [], 0
+        for s in self.slabs:
+            if s.dtype != self.dtype or s.device != self.device or s.dim() != 2 or s.stride(-1) != 1:
+                raise ValueError("GnormTable: one dtype, one device, [S, n] with element stride 1")
+            S, n = s.shape
+            if n == 0 or S < 1 or (S > 1 and s.stride(0) < n):
+                raise ValueError("GnormTable: n >= 1, S >= 1, slab row stride >= n")
+            self.rows.append((_ptr(s), S, s.stride(0) if S > 1 else n, n))
+            self.first.append(count)
+            count += (n + CLIP_BLOCK - 1) // CLIP_BLOCK
+        self.count, self.dev = count, None
+        if self.device.type != "cpu":
+            self.dev = torch.zeros(len(self.rows), 4, dtype=torch.int64, device=self.device)
+            rc, dev_count = native().gnorm_table(self.f64, self.dev.data_ptr(), self.rows, _stream())
+            if rc or dev_count != count:
+                raise ValueError(f"gnorm_table refused the segments (rc={rc})")
+
+    def __len__(self):
+        return len(self.slabs)
+
+
+def gnorm_partials(table, partials, scale=1.0):
+    """per block of 1024 elements of every segment the sum of gs^2 in FP64, gs = (the slab sum in
+    the table's order) * scale in the tensors' dtype, in the fixed order of include/libhpnn/clip.h,
+    into partials[0 .. table.count) (float64; the rest is left alone): one capturable launch with
+    one workgroup per block (csrc/gpu/kernels_clip.hip).  CPU tensors: the host entry point."""
+    if partials.dtype != torch.float64 or partials.dim() != 1 or partials.stride(0) != 1 or \
+            partials.numel() < table.count or partials.device != table.device:
+        raise ValueError("gnorm_partials: partials is float64 [>= table.count] on the table's device")
+    if table.dev is None:
+        for r, first in zip(table.rows, table.first):
+            native().clip_host_sumsq(table.f64, int(table.interleaved), r[0], r[1], r[2], r[3], float(scale),
+                                     partials.data_ptr() + 8 * first)
+        return partials
+    _cg_rc(native().gnorm_partials(table.f64, int(table.interleaved), table.dev.data_ptr(), len(table), table.count,
+                                   float(scale), partials.data_ptr(), _stream()), "gnorm_partials")
+    return partials
+
+
+def clip_finalize(partials, count, state):
+    """partials[0 .. count) summed in the finalize's order, norm = sqrt(sum), factor = max_norm /
+    norm when norm > max_norm, else 1, and the epoch's counters (steps, clipped, norm_max,
+    norm_last): one capturable launch of one workgroup; CPU tensors: the host form."""
+    if not 1 <= count <= partials.numel():
+        raise ValueError("clip_finalize: 1 <= count <= len(partials)")
+    if _cpu(state):
+        native().clip_host_finalize(state.data_ptr(), partials.data_ptr(), int(count))
+        return state
+    _cg_rc(native().clip_finalize(partials.data_ptr(), int(count), state.data_ptr(), _stream()), "clip_finalize")
+    return state
+
+
+def clip_commit(state, hist=None, cursor=None):
+    """the last launch of an epoch: the record (steps, clipped, norm_max, norm_last) appended to hist
+    at cursor (clip_history; a full history drops the record), then the four zeroed.  One capturable
+    one-thread launch; CPU tensors: the host form."""
+    if (hist is None) != (cursor is None):
+        raise ValueError("clip_commit: hist and cursor come together")
+    cap = hist.shape[0] if hist is not None else 0
+    if _cpu(state):
+        native().clip_host_commit(state.data_ptr(), _ptr(hist), _ptr(cursor), cap)
+        return state
+    _cg_rc(native().clip_commit(state.data_ptr(), _ptr(hist), _ptr(cursor), cap, _stream()), "clip_commit")
+    return state
 
 
 # --------------------------------------------------------------------------- online FP64 engine

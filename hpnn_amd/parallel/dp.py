@@ -54,6 +54,9 @@ class DataParallel:
         if getattr(model, "sched", False):
             raise ValueError("DataParallel: lr_schedule trains on one device only (its rate lives in one device's "
                              "memory); use one GPU (MLP alone) or pass the rate of every step yourself")
+        if getattr(model, "clip", False):
+            raise ValueError("DataParallel: clip trains on one device only (the norm is reduced over one device's "
+                             "gradient); use one GPU (MLP alone) with optimizer='sgd' or 'adam'")
         self.m = model
         self.group = group
         self.active = dist.is_initialized()

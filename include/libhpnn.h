@@ -180,6 +180,12 @@ typedef struct {
     UINT lr_period, lr_span, lr_patience, warmup;
     UINT n_lr_history;
     DOUBLE *lr_history;
+    /* -- [clip] c: batched training rescales the gradient of a step whose global L2 norm exceeds c
+     *    (<libhpnn/clip.h>); 0: off; one record per epoch of the last nn_train_kernel call
+     *    (nn_get_clip_history) -- */
+    DOUBLE clip;
+    UINT n_clip_history;
+    void *clip_history;
 } nn_def;
 
 #define _NN(a, b) nn_##a##_##b
@@ -377,6 +383,22 @@ void _NN(set, lr_schedule)(nn_def *conf, nn_lr_schedule kind, DOUBLE gamma, UINT
 void _NN(get, lr_schedule)(nn_def *conf, nn_lr_schedule *kind, DOUBLE *gamma, UINT *period, UINT *span,
                            DOUBLE *lr_end, DOUBLE *lr_min, UINT *patience, UINT *warmup);
 const DOUBLE *_NN(get, lr_history)(nn_def *conf, UINT *n);
+/* [clip] c (batched mode, one device or the CPU engine, BP / BPM / ADAM, any [dtype], with or
+ * without [lr_schedule]): when the L2 norm of the whole net's minibatch gradient exceeds c the
+ * gradient is multiplied by c / norm before the update rule sees it (<libhpnn/clip.h>: a
+ * deterministic FP64 reduction in a fixed order, the same bits on the host and on the device).
+ * c must be finite and >= 0; 0 or an absent key: off.  Nothing is carried from step to step, so
+ * the state file does not change and -r resumes exactly.  [train] CG and the multi-GPU engines
+ * refuse [clip]; online mode ignores it with one warning.  The log has one "gradient clipping:
+ * max norm c" line and "CLIP: epoch E steps=N clipped=M max_norm=X last_norm=Y" per epoch at -vv;
+ * nn_get_clip_history returns the records of the last call (owned by conf; *n = 0: none). */
+typedef struct {
+    UINT steps, clipped;         /* the steps of the epoch and those whose gradient was rescaled */
+    DOUBLE norm_max, norm_last;  /* the largest and the last gradient norm of the epoch */
+} nn_clip_record;
+void _NN(set, clip)(nn_def *conf, DOUBLE max_norm);
+DOUBLE _NN(get, clip)(nn_def *conf);
+const nn_clip_record *_NN(get, clip_history)(nn_def *conf, UINT *n);
 /* the [shuffle] epoch permutation (libhpnn/shuffle.h): out[i] = index, in the order drawn once
  * from [seed], of the sample at position i of epoch `epoch` (epochs completed before it) */
 void hpnn_epoch_perm(UINT n, UINT seed, UINT epoch, UINT *out);

@@ -16,6 +16,8 @@
  *   [keep_best]), -P P (train_nn only) stop after P passes without improvement ([patience] P),
  *   -L constant|step|linear|plateau (train_nn only) the learning-rate schedule of batched
  *   training (same as [lr_schedule]; its other keys come from the conf),
+ *   -C c (train_nn only) clip the gradient of every batched step to the global norm c (same as
+ *   [clip] c),
  *   -r FILE exact-resume state (loaded when present, written after training),
  *   -M FILE JSON-lines metrics (same as HPNN_METRICS=FILE),
  *   -T trace ranges + timing table (same as HPNN_TRACE=1).
@@ -40,6 +42,7 @@ typedef struct {
     int keep_best;     /* -K loss|acc */
     unsigned patience; /* -P P */
     int lr_schedule;   /* -L kind; -1 = from conf */
+    double clip;       /* -C c; < 0 = from conf */
     double lr, alpha;
     const char *state;   /* -r */
     const char *metrics; /* -M */
@@ -53,6 +56,7 @@ static int cli_parse(int argc, char **argv, cli_opts *o, int allow_x) {
     o->mode = -1;
     o->dtype = -1;
     o->lr_schedule = -1;
+    o->clip = -1.0;
     o->lr = -1.0;
     o->alpha = -1.0;
     for (int i = 1; i < argc; i++) {
@@ -92,7 +96,7 @@ static int cli_parse(int argc, char **argv, cli_opts *o, int allow_x) {
                 j++;
                 continue;
             }
-            if (strchr("OBSGbemdlarM", c) || (strchr("VKPL", c) && allow_x)) {
+            if (strchr("OBSGbemdlarM", c) || (strchr("VKPLC", c) && allow_x)) {
                 const char *val = a[j + 1] ? &a[j + 1] : (i + 1 < argc ? argv[++i] : NULL);
                 if (!val) {
                     _OUT(stderr, "syntax error: missing -%c parameter!\n", c);
@@ -126,6 +130,13 @@ static int cli_parse(int argc, char **argv, cli_opts *o, int allow_x) {
                         if (!strcmp(val, kinds[q])) o->lr_schedule = q;
                     if (o->lr_schedule < 0) {
                         _OUT(stderr, "syntax error: bad -L parameter (constant | step | linear | plateau)!\n");
+                        return -1;
+                    }
+                } else if (c == 'C') {
+                    char *end = NULL;
+                    o->clip = strtod(val, &end);
+                    if (end == val || *end || !(o->clip >= 0.0) || o->clip - o->clip != 0.0) {
+                        _OUT(stderr, "syntax error: bad -C parameter (a finite norm > 0; 0: off)!\n");
                         return -1;
                     }
                 } else if (c == 'm') {
@@ -170,6 +181,7 @@ static void cli_apply_conf(const cli_opts *o, nn_def *conf) {
     if (o->keep_best) _NN(set, keep_best)(conf, (nn_keep_best)o->keep_best);
     if (o->patience) _NN(set, patience)(conf, o->patience);
     if (o->lr_schedule >= 0) conf->lr_schedule = (nn_lr_schedule)o->lr_schedule; /* the other keys: the conf's */
+    if (o->clip >= 0.0) _NN(set, clip)(conf, o->clip);
     if (o->lr > 0) _NN(set, learning_rate)(conf, o->lr);
     if (o->alpha >= 0) _NN(set, momentum)(conf, o->alpha);
 }

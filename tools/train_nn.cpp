@@ -36,6 +36,7 @@ static void dump_help(void) {
     _OUT(stdout, "-K M\treturn the state of the best validation pass, M: loss | acc (needs -V; [keep_best]).\n");
     _OUT(stdout, "-P P\tstop after P validation passes without improvement (needs -K; [patience] P).\n");
     _OUT(stdout, "-L S\tlearning-rate schedule, S: constant | step | linear | plateau (batched mode; [lr_schedule]).\n");
+    _OUT(stdout, "-C c\tclip the gradient of every step to the global L2 norm c (batched mode; [clip]).\n");
     _OUT(stdout, "-r F\texact-resume state file (read if present, written after training).\n");
     _OUT(stdout, "-M F\tJSON-lines metrics file.  -T trace ranges + timing table.\n");
     _OUT(stdout, "***********************************\n");
