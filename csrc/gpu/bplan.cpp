@@ -348,6 +348,7 @@ BPlan::~BPlan() {
 
 /* ------------------------------------------------------------------ launches */
 int BPlan::cast_weights(hipStream_t s) {
+    if (!stale_captured_) stale_ = 0; /* every copy is rewritten below */
     for (int l = 0; l < L; l++) {
         int r;
         if (l == 0 && W0f) { /* an lr = 0 update is exactly a cast, and writes the fragment-major copy */
@@ -361,11 +362,24 @@ int BPlan::cast_weights(hipStream_t s) {
     return 0;
 }
 
+int BPlan::sync_copies(hipStream_t s) {
+    if (!stale_) return 0;
+    int r = 0;
+    if (stale_ & 0x10001u) r = hpnn_cast_weights(W32[0], Wb[0], Wt[0], Np[0], Kp[0], s);
+    for (int l = 1; l < L && !r; l++) {
+        if (stale_ & (1u << l)) r = hpnn_cast_weights(W32[l], Wb[l], Wt[l], Np[l], Kp[l], s);
+        else if (stale_ & (0x10000u << l)) r = hpnn_transpose_bf16(Wb[l], Wt[l], Np[l], Kp[l], s);
+    }
+    if (!r && !stale_captured_) stale_ = 0;
+    return r;
+}
+
 int BPlan::zero_stats(hipStream_t s) {
     return hipMemsetAsync(stats, 0, (size_t)HPNN_STAT_SLOTS * HPNN_STAT_STRIDE * 4, s) == hipSuccess ? 0 : -7;
 }
 
 int BPlan::forward(const void *X, hipStream_t s) {
+    if (int r = sync_copies(s)) return r;
     for (int l = 0; l < L; l++) {
         const void *A = l ? H[l - 1] : X;
         const bool last = l == L - 1;
@@ -387,6 +401,7 @@ int BPlan::output(const int *labels, const float *T, int ldt, int n_valid, float
 /* D[l-1] = (D[l] . W_l) * f'(H[l-1]) with the pre-update W_l^T ([Kp[l] x Np[l]]) */
 int BPlan::backward_layer(int l, hipStream_t s) {
     if (l < 1 || l >= L) return -1;
+    if (int r = sync_copies(s)) return r;
     if (nn_bwd[l])
         return hpnn_gemm_nn_bf16(D[l], Np[l], Wb[l], Kp[l], D[l - 1], Np[l - 1], H[l - 1], Np[l - 1], Bp, Np[l - 1],
                                  Np[l], HPNN_EPI_DACT, 0, s);
@@ -533,6 +548,11 @@ int BPlan::g0_fused_step(const XIn &x, float lr, float alpha, float scale, hipSt
         u.xv = *xv;
     }
     u.W32 = W32[0], u.V32 = V32[0], u.Wb = Wb[0], u.Wt = Wt[0], u.Wf = W0f;
+    /* a plain step of the tile path: W0 / W0^T / W1^T have no reader until sync_copies (the front
+     * and hpnn_mlp3_eval take W0f, W1, W2 and W2^T).  Not with the exchange in the launch, and
+     * a launch that only stores the gradient writes no weights at all */
+    const bool lazy = lazy_copies && mode == 't' && !gout && !xv;
+    if (lazy) u.Wb = u.Wt = nullptr;
     u.cnt = g0cnt, u.err = g0cnt + HPNN_G0_ERR_WORD;
     u.perm = g0_perm;
     u.fault = hpnn_fault_hit("handoff"); /* HPNN_FAULT=handoff:n: the n-th launch reports a timed-out wait */
@@ -544,8 +564,16 @@ int BPlan::g0_fused_step(const XIn &x, float lr, float alpha, float scale, hipSt
         u.W32b[l] = W32[l + 1], u.V32b[l] = V32[l + 1], u.Wbb[l] = Wb[l + 1], u.Wtb[l] = Wt[l + 1];
         u.Nb[l] = Np[l + 1], u.Kb[l] = Kp[l + 1];
     }
-    return hpnn_gemm_fm_direct_update(D[0], fm, x.u8, x.u8 ? x.scale : 1.f, slab[0], Kp[0], Np[0], Kp[0], Bp, S[0], &u,
-                                      s);
+    if (lazy) u.Wtb[0] = nullptr;
+    const int r = hpnn_gemm_fm_direct_update(D[0], fm, x.u8, x.u8 ? x.scale : 1.f, slab[0], Kp[0], Np[0], Kp[0], Bp,
+                                             S[0], &u, s);
+    if (r == 0 && lazy) {
+        stale_ |= 0x10001u | 0x20000u; /* Wb[0], Wt[0], Wt[1] */
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
+        else if (cs != hipStreamCaptureStatusNone) stale_captured_ = true;
+    }
+    return r;
 }
 
 /* the weight gradient and the step can run as ONE 8-phase TN launch (no gradient in memory):
@@ -846,6 +874,7 @@ int BPlan::health(hipStream_t s) {
 int BPlan::weights_digest(int which, unsigned long long *out, hipStream_t s) {
     if (!digest_ && hpnn_dev_malloc((void **)&digest_, sizeof *digest_) != hipSuccess) return -7;
     if (hipMemsetAsync(digest_, 0, sizeof *digest_, s) != hipSuccess) return -7;
+    if ((which & 1) && sync_copies(s)) return -7;
     long base = 0;
     for (int l = 0; l < L; l++) {
         const long n = (long)Np[l] * Kp[l];

@@ -87,6 +87,17 @@ class BPlan {
     int mid_grid = 0, mid_groups = 1, wide_ksplit = 1, slab_f = 0;
     bool g0_fused = true; /* modes t / x: G0 + reduction + every step in one launch when it applies */
     int g0_perm = 0;      /* tests: > 0 runs the fused G0 grid in a permuted block -> role order */
+    /* mode 't': the fused G0 step does not store the BF16 copies that neither the tile front nor
+     * hpnn_mlp3_eval reads -- W0, W0^T and W1^T; they go stale (stale_copies) until sync_copies
+     * re-derives them from the FP32 masters, which every reader of them does first.  false
+     * (tests): every step stores them */
+    bool lazy_copies = true;
+    /* bit l: Wb[l] is behind W32[l]; bit 16 + l: Wt[l] is */
+    unsigned stale_copies() const { return stale_; }
+    /* brings the stale copies up to date on s (a cast of layer 0, a transpose of layer 1); nothing
+     * is launched when none is stale.  Steps captured into a graph run again without the plan
+     * knowing: after such a capture the copies count as stale for good */
+    int sync_copies(hipStream_t s);
     bool tn_update = true; /* the step in the 8-phase TN gradient's epilogue where it applies */
     /* two-layer nets: layer 1's gradient + step as the side job of layer 0's fused TN launch */
     bool tn8_side = [] { const char *e = getenv("HPNN_TN8_SIDE"); return !(e && e[0] == '0'); }();
@@ -261,6 +272,8 @@ class BPlan {
     std::vector<void *> ptr_;
     bool owns_ = false;
     unsigned long long *digest_ = nullptr; /* device word of weights_digest */
+    unsigned stale_ = 0;                   /* stale_copies() */
+    bool stale_captured_ = false;          /* a lazy step sits in a captured graph */
     /* the one place a step's optimizer is applied to layers whose gradients are in memory:
      * hpnn_sgd_update_multi, or under ADAM the advance plus hpnn_adam_update_multi */
     int apply_optimizer(const hpnn_upd_layer *u, int n, float lr, float alpha, float scale, hipStream_t s);

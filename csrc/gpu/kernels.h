@@ -143,7 +143,7 @@ int hpnn_gemm_fm_direct_reduce(const void *Dg, const void *Hg, int h_u8, float h
  * HPNN_G0_FUSED=0 disables it. */
 typedef struct {
     float *W32, *V32; /* layer 0 [N][M] FP32 master / momentum (V32 NULL for BP) */
-    void *Wb, *Wt, *Wf; /* BF16 W [N][M], W^T [M][N], fragment-major copy (may be NULL) */
+    void *Wb, *Wt, *Wf; /* BF16 W [N][M], W^T [M][N], fragment-major copy (each may be NULL: not kept) */
     unsigned int *cnt;  /* HPNN_G0CNT_WORDS words, zeroed once: 64-bit tile counters, 32 words apart (monotonic) */
     unsigned int *err;  /* set when a wait for the other splits timed out */
     float lr, alpha, scale;
@@ -152,7 +152,7 @@ typedef struct {
     int mrows;
     long mstride, n12;
     float *W32b[2], *V32b[2]; /* layers 1, 2 */
-    void *Wbb[2], *Wtb[2];
+    void *Wbb[2], *Wtb[2]; /* (each may be NULL: that copy is not kept) */
     int Nb[2], Kb[2];
     /* non-NULL: no step -- the fully reduced gradients are stored instead, G0 [N][M] at gout,
      * [G1 | G2] right after it (the flat layout of the plan's gradient buffer; data parallel) */

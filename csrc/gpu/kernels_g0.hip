@@ -39,6 +39,9 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <atomic>
+#include <map>
+#include <mutex>
 #include <type_traits>
 
 #include "frag_major.h"
@@ -93,7 +96,7 @@ __device__ __forceinline__ void fm_role(int b, int splits, int tiles, int xcd_ma
     }
 }
 
-template <int WF, int WH, int PD, int KW, bool HU8, int WM = 2, int WN = 2, bool X16 = false>
+template <bool WIDE, int WF, int WH, int PD, int KW, bool HU8, int WM = 2, int WN = 2, bool X16 = false>
 __device__ __forceinline__ void fm_partial(const __bf16 *__restrict__ Dg, int nbd, const void *__restrict__ Hg, int nbh,
                                            int ksteps, int splits, int tiles_n, int tiles, int xcd_map, int vb,
                                            f32x4 (&acc)[WF][WH], int &tile, int &split, int &m0, int &n0) {
@@ -177,30 +180,95 @@ __device__ __forceinline__ void fm_partial(const __bf16 *__restrict__ Dg, int nb
             if (t + u < nk) mma(u);
     }
 
-    if constexpr (KW > 1) { /* groups 1.. hand their partial tiles to group 0 through LDS, in order */
-        __shared__ f32x4 part[GW][WF * WH][64];
-#pragma unroll
-        for (int g = 1; g < KW; g++) {
-            if (kg == g) {
+    if constexpr (KW > 1) {
+        /* groups 1.. hand their partial tiles to group 0 through LDS (dynamic: fm_meet_bytes).
+         * WIDE: every group has an area of its own, all write at once and ONE barrier follows;
+         * else one area, a write / barrier / add / barrier round per group.  Group 0 adds in
+         * the order g = 1, 2, ... either way: the same bits */
+        extern __shared__ __attribute__((aligned(16))) char fm_meet[];
+        constexpr int AREA = GW * WF * WH * 64; /* f32x4 per group */
+        f32x4 *const part = (f32x4 *)fm_meet + (wave % GW) * (WF * WH * 64) + lane;
+        if constexpr (WIDE) {
+            if (kg > 0) {
 #pragma unroll
                 for (int i = 0; i < WF; i++)
 #pragma unroll
-                    for (int j = 0; j < WH; j++) part[wave % GW][i * WH + j][lane] = acc[i][j];
+                    for (int j = 0; j < WH; j++) part[(kg - 1) * AREA + (i * WH + j) * 64] = acc[i][j];
             }
             __syncthreads();
             if (kg == 0) {
+                /* one row of WH accumulators at a time, its (KW - 1) WH reads in flight together
+                 * (all WF rows at once would cost the registers of a second accumulator tile) */
 #pragma unroll
-                for (int i = 0; i < WF; i++)
+                for (int i = 0; i < WF; i++) {
+                    f32x4 p[KW - 1][WH];
 #pragma unroll
-                    for (int j = 0; j < WH; j++) acc[i][j] += part[wave % GW][i * WH + j][lane];
+                    for (int g = 1; g < KW; g++)
+#pragma unroll
+                        for (int j = 0; j < WH; j++) p[g - 1][j] = part[(g - 1) * AREA + (i * WH + j) * 64];
+#pragma unroll
+                    for (int g = 1; g < KW; g++)
+#pragma unroll
+                        for (int j = 0; j < WH; j++) acc[i][j] += p[g - 1][j];
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             }
-            if (g + 1 < KW) __syncthreads();
+        } else {
+#pragma unroll
+            for (int g = 1; g < KW; g++) {
+                if (kg == g) {
+#pragma unroll
+                    for (int i = 0; i < WF; i++)
+#pragma unroll
+                        for (int j = 0; j < WH; j++) part[(i * WH + j) * 64] = acc[i][j];
+                }
+                __syncthreads();
+                if (kg == 0) {
+#pragma unroll
+                    for (int i = 0; i < WF; i++)
+#pragma unroll
+                        for (int j = 0; j < WH; j++) acc[i][j] += part[(i * WH + j) * 64];
+                }
+                if (g + 1 < KW) __syncthreads();
+            }
         }
     }
 }
 
-template <int WF, int WH, int PD, int KW, bool HU8 = false, int WM = 2, int WN = 2>
-__global__ __launch_bounds__(64 * WM * WN * KW) void gemm_fm_direct_kernel(const __bf16 *__restrict__ Dg, int nbd,
+/* dynamic LDS of a launch whose k-groups meet through fm_partial: one 16 WF WM x 16 WH WN FP32
+ * tile per area, KW - 1 areas when wide */
+template <int WF, int WH, int KW, int WM, int WN>
+constexpr size_t fm_meet_bytes(bool wide) {
+    return KW > 1 ? (size_t)(wide ? KW - 1 : 1) * WM * WN * WF * WH * 64 * sizeof(f32x4) : 0;
+}
+
+int g0_cus() {
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        return hipGetDevice(&dev) == hipSuccess &&
+                       hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess
+                   ? n
+                   : 0;
+    }();
+    return cus;
+}
+
+/* more than 64 KiB of dynamic LDS needs the attribute, once per kernel and device */
+template <auto KERN>
+void fm_allow_lds(size_t bytes) {
+    static std::atomic<unsigned long long> done{0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) dev = 63; /* unknown: set it every time */
+    const unsigned long long bit = 1ull << dev;
+    if (dev < 63 && (done.load(std::memory_order_relaxed) & bit)) return;
+    (void)hipFuncSetAttribute((const void *)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    done.fetch_or(bit, std::memory_order_relaxed);
+}
+
+template <bool WIDE, int WF, int WH, int PD, int KW, bool HU8 = false, int WM = 2, int WN = 2>
+/* (3 waves per SIMD: the register budget the meeting's static LDS used to imply) */
+__global__ __launch_bounds__(64 * WM * WN * KW, KW > 1 ? 3 : 1) void gemm_fm_direct_kernel(
+                                                                  const __bf16 *__restrict__ Dg, int nbd,
                                                                   const void *__restrict__ Hg, int nbh, float hscale,
                                                                   float *__restrict__ slab, int ldg, int N, int ksteps,
                                                                   int splits, int tiles_n, int tiles, int xcd_map,
@@ -211,8 +279,8 @@ __global__ __launch_bounds__(64 * WM * WN * KW) void gemm_fm_direct_kernel(const
     }
     f32x4 acc[WF][WH];
     int tile, split, m0, n0;
-    fm_partial<WF, WH, PD, KW, HU8, WM, WN>(Dg, nbd, Hg, nbh, ksteps, splits, tiles_n, tiles, xcd_map,
-                                            (int)blockIdx.x, acc, tile, split, m0, n0);
+    fm_partial<WIDE, WF, WH, PD, KW, HU8, WM, WN>(Dg, nbd, Hg, nbh, ksteps, splits, tiles_n, tiles, xcd_map,
+                                                  (int)blockIdx.x, acc, tile, split, m0, n0);
     if ((threadIdx.x >> 6) >= WM * WN) return;
     const int lane = threadIdx.x & 63, r16 = lane & 15, q = lane >> 4;
     float *out = slab + (size_t)split * N * ldg;
@@ -231,7 +299,9 @@ __global__ __launch_bounds__(64 * WM * WN * KW) void gemm_fm_direct_kernel(const
  * until all `splits` partials of the tile have arrived, reduces its 1/splits share of the
  * tile over the splits in a FIXED order (sc1 loads; bitwise repeatable whatever the arrival
  * order) and applies the BP / BPM step to those elements: FP32 master, momentum, BF16 W,
- * W^T and the fragment-major copy the front reads.  The front's [G1 | G2] block slabs are
+ * W^T and the fragment-major copy the front reads (a copy whose pointer is NULL is not kept:
+ * the tile path's plain step leaves W0, W0^T and W1^T to BPlan::sync_copies).  The front's
+ * [G1 | G2] block slabs are
  * summed completely (fixed order) and layers 1 and 2 stepped by TAIL workgroups appended to
  * the grid, on the CUs the GEMM grid leaves idle (MNIST: 240 GEMM workgroups + 16 tails on 256
  * CUs): the 9 MB of slab reads run beside the GEMM instead of after every workgroup's publish
@@ -275,7 +345,8 @@ __device__ __forceinline__ void bpm_step4(float *__restrict__ W32, float *__rest
     *(f32x4 *)(W32 + idx) = w;
 }
 
-/* element (n, k..k+3) of a [N][K] layer: FP32 master + BF16 W / W^T (+ fragment-major Wf) */
+/* element (n, k..k+3) of a [N][K] layer: FP32 master + the BF16 copies the caller keeps current
+ * (W, fragment-major Wf, W^T; a NULL one is left alone: four scattered 2-byte stores for W^T) */
 __device__ __forceinline__ void step_elem4(float *W32, float *V32, __bf16 *Wb, __bf16 *Wt, __bf16 *Wf, int N, int K,
                                            int n, int k, f32x4 g, const hpnn_g0_update &u, bool use = false,
                                            Pre4 pre = {}) {
@@ -286,11 +357,11 @@ __device__ __forceinline__ void step_elem4(float *W32, float *V32, __bf16 *Wb, _
     bf16x4 wb;
 #pragma unroll
     for (int r = 0; r < 4; r++) wb[r] = (__bf16)w[r];
-    *(bf16x4 *)(Wb + idx) = wb;
+    if (Wb) *(bf16x4 *)(Wb + idx) = wb;
     if (Wf) { /* MFMA-fragment-major copy (frag_major.h): 4 consecutive k stay contiguous */
         *(bf16x4 *)(Wf + hpnn_frag_major_offset(n, k, K)) = wb;
     }
-    if (!G0_PROTO(u, 2048)) /* 2048: timing ablation, no W^T stores */
+    if (Wt && !G0_PROTO(u, 2048)) /* 2048: timing ablation, no W^T stores */
 #pragma unroll
         for (int r = 0; r < 4; r++) Wt[(size_t)(k + r) * N + n] = wb[r];
 }
@@ -533,8 +604,9 @@ __device__ __forceinline__ f32x4 xtest_pattern(int rank, long i) {
 constexpr int G0TR_BLOCKS = 512, G0TR_MARKS = 8;
 __device__ unsigned long long g_g0_trace[G0TR_BLOCKS][G0TR_MARKS];
 
-template <int WF, int WH, int PD, int KW, bool HU8, bool TRACE = false, int WM = 2, int WN = 2, bool X16 = false>
-__global__ __launch_bounds__(64 * WM * WN * KW) void g0_fused_kernel(const __bf16 *__restrict__ Dg, int nbd,
+template <bool WIDE, int WF, int WH, int PD, int KW, bool HU8, bool TRACE = false, int WM = 2, int WN = 2,
+          bool X16 = false>
+__global__ __launch_bounds__(64 * WM * WN * KW, 3) void g0_fused_kernel(const __bf16 *__restrict__ Dg, int nbd,
                                                             const void *__restrict__ Hg, int nbh, float hscale,
                                                             float *__restrict__ slab, int ldg, int N, int ksteps,
                                                             int splits, int tiles_n, int tiles, int xcd_map,
@@ -594,8 +666,8 @@ __global__ __launch_bounds__(64 * WM * WN * KW) void g0_fused_kernel(const __bf1
         if (u.xtest) /* self-test of the in-kernel exchange: no GEMM (the role only) */
             fm_role(vb, splits, tiles, xcd_map, tile, split);
         else
-            fm_partial<WF, WH, PD, KW, HU8, WM, WN, X16>(Dg, nbd, Hg, nbh, ksteps, splits, tiles_n, tiles, xcd_map, vb, acc,
-                                                    tile, split, m0, n0);
+            fm_partial<WIDE, WF, WH, PD, KW, HU8, WM, WN, X16>(Dg, nbd, Hg, nbh, ksteps, splits, tiles_n, tiles,
+                                                               xcd_map, vb, acc, tile, split, m0, n0);
         mark(1);
         const int t = threadIdx.x, lane = t & 63;
         /* where the reduced gradient goes instead of a step: the plan's buffer, the xGMI
@@ -733,9 +805,23 @@ int launch_fm(const void *Dg, const void *Hg, float hscale, float *slab, int ldg
     constexpr int TMF = 16 * WF * WM, TNH = 16 * WH * WN;
     const int tiles_n = N / TNH, tiles = (M / TMF) * tiles_n;
     const int xcd_map = (splits >= 8 && tiles > 1) ? 1 : 0;
-    hipLaunchKernelGGL((gemm_fm_direct_kernel<WF, WH, PD, KW, HU8, WM, WN>), dim3(tiles * splits + tail.blocks),
-                       dim3(64 * WM * WN * KW), 0, s, (const __bf16 *)Dg, N / 16, Hg, M / 16, hscale, slab, ldg, N,
-                       Bt / 32, splits, tiles_n, tiles, xcd_map, tail);
+    /* one area per k-group while every workgroup has a CU to itself anyway; a larger grid keeps
+     * the small footprint (more workgroups per CU) */
+    const bool wide = KW > 1 && tiles * splits + tail.blocks <= g0_cus();
+    const size_t lds = fm_meet_bytes<WF, WH, KW, WM, WN>(wide);
+#define HPNN_FMK(W_)                                                                                               \
+    hipLaunchKernelGGL((gemm_fm_direct_kernel<W_, WF, WH, PD, KW, HU8, WM, WN>), dim3(tiles * splits + tail.blocks), \
+                       dim3(64 * WM * WN * KW), lds, s, (const __bf16 *)Dg, N / 16, Hg, M / 16, hscale, slab, ldg, N, \
+                       Bt / 32, splits, tiles_n, tiles, xcd_map, tail)
+    if constexpr (KW > 1) {
+        if (wide) {
+            fm_allow_lds<gemm_fm_direct_kernel<true, WF, WH, PD, KW, HU8, WM, WN>>(lds);
+            HPNN_FMK(true);
+            return hipGetLastError() == hipSuccess ? 0 : -5;
+        }
+    }
+    HPNN_FMK(false);
+#undef HPNN_FMK
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
@@ -760,13 +846,31 @@ int fm_dispatch(const void *Dg, const void *Hg, int h_u8, float hscale, float *s
 
 }  // namespace
 
-/* the fused G0 grid (tiles x splits workgroups of 512 threads) fits on the device at once;
- * both instantiations checked (they differ in the operand conversion) */
-static bool g0_fused_resident(int blocks) {
-    static const int cap =
-        std::min(hpnn_resident_capacity((const void *)g0_fused_kernel<5, 4, 1, 4, true, false, 1, 2>, 512, 0),
-                 hpnn_resident_capacity((const void *)g0_fused_kernel<5, 4, 1, 4, false, false, 1, 2>, 512, 0));
-    return blocks <= cap;
+/* the fused G0 grid (tiles x splits workgroups of 512 threads) fits on the device at once,
+ * with the LDS of the k-groups' meeting (wide: an area per group); both instantiations checked
+ * (they differ in the operand conversion) */
+static bool g0_fused_resident(int blocks, bool wide = false) {
+    constexpr auto k8 = g0_fused_kernel<false, 5, 4, 1, 4, true, false, 1, 2>;
+    constexpr auto k16 = g0_fused_kernel<false, 5, 4, 1, 4, false, false, 1, 2>;
+    constexpr auto k8w = g0_fused_kernel<true, 5, 4, 1, 4, true, false, 1, 2>;
+    constexpr auto k16w = g0_fused_kernel<true, 5, 4, 1, 4, false, false, 1, 2>;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    static std::mutex mu;
+    static std::map<int, std::pair<int, int>> caps; /* device -> {one area, wide} */
+    std::lock_guard<std::mutex> g(mu);
+    auto it = caps.find(dev);
+    if (it == caps.end()) {
+        const size_t l1 = fm_meet_bytes<5, 4, 4, 1, 2>(false), lw = fm_meet_bytes<5, 4, 4, 1, 2>(true);
+        fm_allow_lds<k8w>(lw);
+        fm_allow_lds<k16w>(lw);
+        const int c1 = std::min(hpnn_resident_capacity((const void *)k8, 512, l1),
+                                hpnn_resident_capacity((const void *)k16, 512, l1));
+        const int cw = std::min(hpnn_resident_capacity((const void *)k8w, 512, lw),
+                                hpnn_resident_capacity((const void *)k16w, 512, lw));
+        it = caps.emplace(dev, std::make_pair(c1, cw)).first;
+    }
+    return blocks <= (wide ? it->second.second : it->second.first);
 }
 
 static bool g0_fused_on() {
@@ -791,17 +895,15 @@ extern "C" int hpnn_gemm_fm_direct_update(const void *Dg, const void *Hg, int h_
      * (more splits than that, e.g. forced by HPNN_TN_SPLITS, take the slab form instead of
      * stalling to the timeout) */
     if (!g0_fused_resident(tiles * splits)) return -1;
+    /* an LDS area per k-group (one barrier instead of a round per group) wherever the grid is
+     * resident with that footprint too -- one workgroup per CU.  Not with the exchange in the
+     * launch: ranks that share one GPU must fit their waiting grids side by side */
+    const bool wide = !u->xchg && g0_fused_resident(tiles * splits, true);
     /* tail workgroups for the [G1 | G2] share on the CUs the GEMM grid leaves idle (MNIST: 240
      * GEMM workgroups, 16 tails on a 256-CU MI355X); HPNN_G0_TAILS overrides the count (0: none,
      * the GEMM workgroups sum [G1 | G2] after their publish -- the form for a device with no
      * idle CU) */
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        return hipGetDevice(&dev) == hipSuccess &&
-                       hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess
-                   ? n
-                   : 0;
-    }();
+    const int cus = g0_cus();
     static const int tails_env = [] { const char *e = getenv("HPNN_G0_TAILS"); return e ? atoi(e) : -1; }();
     /* one tail per 16 slab rows (each sums ~16 x the [G1 | G2] block, 563 KB on MNIST), at most
      * the CUs the GEMM grid leaves idle: ranks sharing one GPU (tests, rehearsals) keep their
@@ -809,7 +911,7 @@ extern "C" int hpnn_gemm_fm_direct_update(const void *Dg, const void *Hg, int h_
     int ntail = tails_env >= 0 ? tails_env : std::min(cus - tiles * splits, std::max(1, u->mrows / 16));
     if (ntail < 0) ntail = 0;
     if (ntail > 64) ntail = 64;
-    while (ntail > 0 && !g0_fused_resident(tiles * splits + ntail)) ntail--;
+    while (ntail > 0 && !g0_fused_resident(tiles * splits + ntail, wide)) ntail--;
     if (u->xchg && tiles * splits + ntail > HPNN_XAR_MAX_BLOCKS) ntail = HPNN_XAR_MAX_BLOCKS - tiles * splits;
     if (ntail < 0) ntail = 0;
     if (u->xchg) {
@@ -822,15 +924,25 @@ extern "C" int hpnn_gemm_fm_direct_update(const void *Dg, const void *Hg, int h_
     }
     const int xcd_map = (splits >= 8 && tiles > 1) ? 1 : 0;
     hpnn_g0_update uu = *u;
+    const size_t lds = fm_meet_bytes<5, 4, 4, 1, 2>(wide);
 #ifdef HPNN_ABLATIONS
     static const int proto = [] { const char *e = getenv("HPNN_G0_PROTO"); return e ? atoi(e) : 0; }();
     uu.proto |= proto;
 #endif
     static const bool trace = [] { const char *e = getenv("HPNN_G0_TRACE"); return e && e[0] == '1'; }();
 #define HPNN_G0F(...)                                                                                              \
-    hipLaunchKernelGGL((g0_fused_kernel<__VA_ARGS__>), dim3(tiles * splits + ntail), dim3(512), 0, stream,           \
-                       (const __bf16 *)Dg,                                                                         \
-                       N / 16, Hg, M / 16, hscale, slab, ldg, N, Bt / 32, splits, tiles_n, tiles, xcd_map, uu)
+    do {                                                                                                           \
+        if (wide) {                                                                                                \
+            fm_allow_lds<g0_fused_kernel<true, __VA_ARGS__>>(lds);                                                 \
+            HPNN_G0L(true, __VA_ARGS__);                                                                           \
+        } else {                                                                                                   \
+            HPNN_G0L(false, __VA_ARGS__);                                                                          \
+        }                                                                                                          \
+    } while (0)
+#define HPNN_G0L(...)                                                                                              \
+    hipLaunchKernelGGL((g0_fused_kernel<__VA_ARGS__>), dim3(tiles * splits + ntail), dim3(512), lds, stream,         \
+                       (const __bf16 *)Dg, N / 16, Hg, M / 16, hscale, slab, ldg, N, Bt / 32, splits, tiles_n,     \
+                       tiles, xcd_map, uu)
     /* HPNN_G0_PD=2 (ABLATIONS builds, tuning): two k-steps of operands in flight */
 #ifdef HPNN_ABLATIONS
     static const int pd = [] { const char *e = getenv("HPNN_G0_PD"); return e ? atoi(e) : 1; }();
@@ -843,6 +955,7 @@ extern "C" int hpnn_gemm_fm_direct_update(const void *Dg, const void *Hg, int h_
     else if (h_u8) HPNN_G0F(5, 4, 1, 4, true, false, 1, 2);
     else HPNN_G0F(5, 4, 1, 4, false, false, 1, 2);
 #undef HPNN_G0F
+#undef HPNN_G0L
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

@@ -227,6 +227,9 @@ void bind_plan(py::module_ &m) {
              })
         .def_readwrite("g0_fused", &BPlan::g0_fused)
         .def_readwrite("g0_perm", &BPlan::g0_perm)
+        .def_readwrite("lazy_copies", &BPlan::lazy_copies)
+        .def_property_readonly("stale_copies", &BPlan::stale_copies)
+        .def("sync_copies", [](BPlan &p, uptr s) { check(p.sync_copies(S(s)), "BPlan.sync_copies"); })
         .def_readwrite("tn_update", &BPlan::tn_update)
         .def_readwrite("tn8_side", &BPlan::tn8_side)
         .def_readwrite("side_launches", &BPlan::side_launches)

@@ -171,8 +171,8 @@ class MLP:
                 self.lr_state.copy_(ops.lr_state("constant", clip_cfg[1]))
             if on_gpu:
                 self.plan.prepare_clip(_stream())
-        self.Wb = [b[("Wb", l)] for l in range(self.L)]
-        self.Wt = [b[("Wt", l)] for l in range(self.L)]
+        self._Wb = [b[("Wb", l)] for l in range(self.L)]
+        self._Wt = [b[("Wt", l)] for l in range(self.L)]
         self.slab = [b[("slab", l)] for l in range(self.L)]
         self.H = [b[("H", l)] for l in range(self.L - 1)]
         self.D = [b[("D", l)] for l in range(self.L)]
@@ -194,6 +194,25 @@ class MLP:
     @property
     def _gpu(self):
         return self.device.type == "cuda"
+
+    def sync_copies(self):
+        """the BF16 copies a fused step of the tile path leaves stale (W0, W0^T, W1^T: no kernel of
+        that step reads them) brought up to date from the FP32 masters, on the current stream;
+        nothing is launched when none is stale (plan.stale_copies)"""
+        if self._gpu and self.plan.stale_copies:
+            self.plan.sync_copies(_stream())
+
+    @property
+    def Wb(self):
+        """BF16 weights [Np, Kp] per layer, current (sync_copies)"""
+        self.sync_copies()
+        return self._Wb
+
+    @property
+    def Wt(self):
+        """their transposes [Kp, Np], current (sync_copies)"""
+        self.sync_copies()
+        return self._Wt
 
     @property
     def tn_update(self):
