@@ -22,6 +22,7 @@
 #include <chrono>
 #include <vector>
 
+#include "../core/export_records.h"
 #include "../core/runtime_internal.h"
 #include "../gpu/engine.h"
 #include "cpu_cg.h"
@@ -366,35 +367,12 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
         st->best_epoch = have_best ? val[best_index].epoch : 0;
         st->best_index = best_index;
         st->stop_epoch = stop ? val.back().epoch : 0;
-        st->val = NULL;
-        st->n_val = (UINT)val.size();
-        if (!val.empty()) {
-            st->val = (hpnn_validation_record *)malloc(val.size() * sizeof(val[0]));
-            if (!st->val) return FALSE;
-            memcpy(st->val, val.data(), val.size() * sizeof(val[0]));
-        }
         st->lrs = have_best ? best_lrs : lrs;
-        st->lr_hist = NULL;
-        st->n_lr = (UINT)lrh.size();
-        if (!lrh.empty()) {
-            st->lr_hist = (DOUBLE *)malloc(lrh.size() * sizeof(DOUBLE));
-            if (!st->lr_hist) return FALSE;
-            memcpy(st->lr_hist, lrh.data(), lrh.size() * sizeof(DOUBLE));
-        }
-        st->clip_hist = NULL;
-        st->n_clip = (UINT)clh.size();
-        if (!clh.empty()) {
-            st->clip_hist = (hpnn_clip_record *)malloc(clh.size() * sizeof(clh[0]));
-            if (!st->clip_hist) return FALSE;
-            memcpy(st->clip_hist, clh.data(), clh.size() * sizeof(clh[0]));
-        }
-        st->cg = NULL;
-        st->n_cg = cg ? epochs_run : 0;
-        if (st->n_cg) {
-            st->cg = (hpnn_cg_record *)malloc(st->n_cg * sizeof(hpnn_cg_record));
-            if (!st->cg) return FALSE;
-            memcpy(st->cg, cgs.hist.data(), st->n_cg * sizeof(hpnn_cg_record));
-        }
+        std::vector<hpnn_cg_record> cgh;
+        if (cg) cgh.assign(cgs.hist.begin(), cgs.hist.begin() + epochs_run);
+        if (!export_records(val, &st->val, &st->n_val) || !export_records(lrh, &st->lr_hist, &st->n_lr) ||
+            !export_records(clh, &st->clip_hist, &st->n_clip) || !export_records(cgh, &st->cg, &st->n_cg))
+            return FALSE;
     }
     /* [keep_best]: the kernel as it was after the best pass's epoch */
     for (UINT l = 0; have_best && l < L; l++) {

@@ -1,7 +1,10 @@
 /*
  * libhpnn batched GPU engine -- the pieces its drivers share (train_*.cpp, infer_batched.cpp,
  * tp_engine.cpp).  All launches of a driver go to one HIP stream; nothing synchronises the
- * host inside an epoch (the reference synchronised every iteration).
+ * host inside an epoch (the reference synchronised every iteration).  Besides the
+ * owners of device memory, graphs and resident sets: StateSeg, the element of a net's one ordered
+ * list of state segments; BestSnap, the [keep_best] snapshot of that list; DevHistory, the
+ * records-plus-cursor buffer behind the rate, clip and validation histories.
  */
 #ifndef HPNN_GPU_BATCHED_COMMON_H
 #define HPNN_GPU_BATCHED_COMMON_H
@@ -168,27 +171,66 @@ struct ResidentSet {
     }
 };
 
-/* [keep_best]: the snapshot of a net's masters (FP32 / T weights and, with BPM, the momentum) in
- * one allocation beside them, the device segment table hpnn_snapshot_if copies by, and the best
- * state hpnn_best_commit keeps; dst[i] is the copy of source i */
+/* a device history: cap records a one-workgroup launch files one at a time, and the cursor word
+ * it advances; the host reads both once, after the last replay */
+template <typename Rec>
+struct DevHistory {
+    DevBuf<Rec> buf;
+    DevBuf<unsigned int> cur;
+    size_t n = 0;
+    /* extra: records allocated behind the cap the launches are given */
+    BOOL init(size_t cap, size_t extra = 0) {
+        n = cap;
+        HIPCHK(buf.alloc(cap + extra ? cap + extra : 1));
+        HIPCHK(cur.alloc(1));
+        HIPCHK(hipMemset(cur.get(), 0, sizeof(unsigned int)));
+        return TRUE;
+    }
+    Rec *hist() const { return buf.get(); }
+    unsigned int *cursor() const { return cur.get(); }
+    unsigned int cap() const { return (unsigned int)n; }
+    /* synchronises; *out = the cap records, *filed = how many of them the launches filed */
+    BOOL read(hipStream_t s, std::vector<Rec> *out, unsigned int *filed) const {
+        out->resize(n);
+        return hipStreamSynchronize(s) == hipSuccess &&
+               hipMemcpy(filed, cur.get(), sizeof *filed, hipMemcpyDeviceToHost) == hipSuccess &&
+               hipMemcpy(out->data(), buf.get(), n * sizeof(Rec), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+};
+
+/* the training state of a net adapter is ONE ordered list of device segments, built once at the
+ * end of its init: per layer the weights, then the momentum / first moment and the second moment
+ * where the net has them, then the Adam state, then the schedule state.  Everything that walks the
+ * state (NetState, batched_net.h) walks this list and finds a segment by kind and layer */
+enum SegKind { SEG_W, SEG_V, SEG_A, SEG_ADAM, SEG_LRS };
+struct StateSeg {
+    SegKind kind;
+    int layer; /* SEG_W, SEG_V, SEG_A; 0 otherwise */
+    void *dev;
+    size_t bytes;
+};
+
+/* [keep_best]: the snapshot of a net's state segments in one allocation beside them, the device
+ * segment table hpnn_snapshot_if copies by, and the best state hpnn_best_commit keeps; dst[i] is
+ * the copy of segment i */
 struct BestSnap {
     DevBuf<char> mem;
     DevBuf<hpnn_snap_seg> table;
     DevBuf<hpnn_best_state> state;
     std::vector<hpnn_snap_seg> segs;
     std::vector<void *> dst;
-    BOOL init(const std::vector<std::pair<const void *, size_t>> &src, hipStream_t s) {
+    BOOL init(const std::vector<StateSeg> &src, hipStream_t s) {
         size_t total = 0;
-        for (const auto &p : src) total += (p.second + 255) / 256 * 256;
+        for (const StateSeg &g : src) total += (g.bytes + 255) / 256 * 256;
         HIPCHK(mem.alloc(total ? total : 256));
         HIPCHK(table.alloc(src.size() ? src.size() : 1));
         HIPCHK(state.alloc(1));
         HIPCHK(hipMemsetAsync(state.get(), 0, sizeof(hpnn_best_state), s));
         size_t off = 0;
-        for (const auto &p : src) {
-            segs.push_back({p.first, mem.get() + off, (unsigned long long)p.second});
+        for (const StateSeg &g : src) {
+            segs.push_back({g.dev, mem.get() + off, (unsigned long long)g.bytes});
             dst.push_back(mem.get() + off);
-            off += (p.second + 255) / 256 * 256;
+            off += (g.bytes + 255) / 256 * 256;
         }
         if (hpnn_snapshot_table(table.get(), segs.data(), (int)segs.size(), s)) {
             NN_ERROR(stderr, "[keep_best]: the snapshot table was refused (alignment or too many layers)\n");

@@ -8,6 +8,9 @@
  *     gradient  gemm_tn split-K FP32 slabs      (MFMA bf16, tr-LDS reads)
  *     update    sgd_update (slab reduce + BP/BPM + BF16 W / W^T refresh)
  * Weights: host FP64 kernel_ann is the I/O master; the device keeps FP32 masters.
+ * Both adapters have ONE step entry point for every optimizer (step) and list their training
+ * state once, at the end of init, as ordered segments; NetState walks that list for the
+ * [keep_best] snapshot, the downloads, the replica state and the exact resume.
  */
 #ifndef HPNN_GPU_BATCHED_NET_H
 #define HPNN_GPU_BATCHED_NET_H
@@ -65,9 +68,116 @@ std::vector<E> to_fragment_major(const DOUBLE *src, int rows, int cols, int rows
     return out;
 }
 
+/* the training state of an adapter, written once over its segment list (StateSeg, batched_common.h;
+ * the adapter lists it at the end of init).  Net gives the stream s and two per-layer converters:
+ *     to_host(host FP64 [N][M], device matrix, layer, l)    to_dev(device matrix, host FP64, layer, l)
+ * Two layouts are contracts: segment i of the list pairs with BestSnap::dst[i], and get_state is
+ * the bytes of the segments in list order without the schedule state (train_dp_mp all-gathers them) */
+template <class Net>
+struct NetState {
+    std::vector<StateSeg> segs;
+    Net &self() { return *static_cast<Net *>(this); }
+    void list_layer(int l, void *W, void *V, void *A, size_t bytes) {
+        void *const b[3] = {W, V, A};
+        const SegKind kinds[3] = {SEG_W, SEG_V, SEG_A};
+        for (int i = 0; i < 3; i++)
+            if (b[i]) segs.push_back({kinds[i], l, b[i], bytes});
+    }
+    void list_tail(hpnn_adam_state *adam, hpnn_lr_state *lrs) {
+        if (adam) segs.push_back({SEG_ADAM, 0, adam, sizeof *adam});
+        if (lrs) segs.push_back({SEG_LRS, 0, lrs, sizeof *lrs});
+    }
+    /* the index of a segment in the list (and in a snapshot's dst); -1: the net has none */
+    int seg(SegKind kind, int layer = 0) const {
+        for (size_t i = 0; i < segs.size(); i++)
+            if (segs[i].kind == kind && segs[i].layer == layer) return (int)i;
+        return -1;
+    }
+    /* the host FP64 array of a per-layer segment */
+    static DOUBLE *host_of(kernel_ann *k, const StateSeg &g) {
+        return g.kind == SEG_W ? layer_of(k, g.layer)->weights : (g.kind == SEG_V ? k->dw : k->dv)[g.layer];
+    }
+
+    /* masters (the momentum into k->dw, Adam's second moment into k->dv and t, p1, p2) -> host
+     * FP64, from the live segments or from their copies in a [keep_best] snapshot (src) */
+    BOOL download(kernel_ann *k) { return download_from(k, nullptr); }
+    BOOL download_from(kernel_ann *k, void *const *src) {
+        HIPCHK(hipStreamSynchronize(self().s));
+        if (seg(SEG_V) >= 0) ann_momentum_init(k);
+        if (seg(SEG_ADAM) >= 0) ann_adam_init(k);
+        for (size_t i = 0; i < segs.size(); i++) {
+            const StateSeg &g = segs[i];
+            const void *from = src ? src[i] : g.dev;
+            if (g.kind == SEG_ADAM) {
+                hpnn_adam_state st;
+                HIPCHK(hipMemcpy(&st, from, sizeof st, hipMemcpyDeviceToHost));
+                k->adam_t = st.t;
+                k->adam_p1 = st.p1;
+                k->adam_p2 = st.p2;
+            } else if (g.kind != SEG_LRS && !self().to_host(host_of(k, g), from, layer_of(k, g.layer), g.layer)) {
+                return FALSE;
+            }
+        }
+        return TRUE;
+    }
+    /* the schedule state of the live net, or of a snapshot */
+    BOOL read_schedule(void *const *src, hpnn_lr_state *out) {
+        const int i = seg(SEG_LRS);
+        if (i < 0) return FALSE;
+        HIPCHK(hipStreamSynchronize(self().s));
+        HIPCHK(hipMemcpy(out, src ? src[i] : segs[i].dev, sizeof *out, hipMemcpyDeviceToHost));
+        return TRUE;
+    }
+
+    /* the replica state as bytes, and back: rank 0's state re-broadcast after an exchange fallback */
+    BOOL get_state(std::vector<char> &out) {
+        out.clear();
+        HIPCHK(hipStreamSynchronize(self().s));
+        for (const StateSeg &g : segs) {
+            if (g.kind == SEG_LRS) continue;
+            const size_t o = out.size();
+            out.resize(o + g.bytes);
+            HIPCHK(hipMemcpy(out.data() + o, g.dev, g.bytes, hipMemcpyDeviceToHost));
+        }
+        return TRUE;
+    }
+    BOOL set_state(const char *in) {
+        for (const StateSeg &g : segs) {
+            if (g.kind == SEG_LRS) continue;
+            HIPCHK(hipMemcpy(g.dev, in, g.bytes, hipMemcpyHostToDevice));
+            in += g.bytes;
+        }
+        return TRUE;
+    }
+
+    /* exact resume: host FP64 -> every segment of one kind */
+    BOOL upload_kind(const kernel_ann *k, SegKind kind) {
+        kernel_ann *kk = (kernel_ann *)k;
+        for (const StateSeg &g : segs)
+            if (g.kind == kind && !self().to_dev(g.dev, host_of(kk, g), layer_of(kk, g.layer), g.layer)) return FALSE;
+        return TRUE;
+    }
+    /* the BPM momentum k->dw */
+    BOOL upload_momentum(const kernel_ann *k) { return !k->dw || upload_kind(k, SEG_V); }
+    /* under ADAM: both moments k->dw, k->dv and t, p1, p2 into the device state */
+    BOOL upload_moments(const kernel_ann *k) {
+        const int i = seg(SEG_ADAM);
+        if (i < 0 || !k->dw || !k->dv) return TRUE;
+        if (!upload_kind(k, SEG_V) || !upload_kind(k, SEG_A)) return FALSE;
+        hpnn_adam_state st;
+        HIPCHK(hipStreamSynchronize(self().s));
+        HIPCHK(hipMemcpy(&st, segs[i].dev, sizeof st, hipMemcpyDeviceToHost));
+        st.t = k->adam_t;
+        st.p1 = k->adam_p1;
+        st.p2 = k->adam_p2;
+        HIPCHK(hipMemcpy(segs[i].dev, &st, sizeof st, hipMemcpyHostToDevice));
+        return TRUE;
+    }
+};
+
 /* BF16 batched engine: an adapter of the library's batched plan (bplan.h, the same object
  * hpnn_amd.models.MLP binds) to the precision-generic drivers below */
-struct Batched {
+struct Batched : NetState<Batched> {
     typedef float target_t; /* dense targets, uploaded once */
     typedef float grad_t;   /* flat gradient buffer (the all-reduce payload) */
     static constexpr hpnn_comm_dtype comm_dt = HPNN_DT_F32;
@@ -80,10 +190,6 @@ struct Batched {
     BOOL set_adam(const hpnn_adam_state &a) {
         adam = p.set_adam(a.lr, a.beta1, a.beta2, a.eps, a.decay) == 0;
         return adam ? TRUE : FALSE;
-    }
-    /* the plan's step ignores lr and alpha under ADAM */
-    BOOL step_adam(const XSet &xs, long row, const float *T, int ldt, int n_valid) {
-        return step(xs, row, T, ldt, n_valid, 0.f, 0.f, false);
     }
     /* [lr_schedule]: the plan's BP / BPM step reads its rate from the device state (BPlan::
      * set_schedule, before init; the buffer "lrs"); the driver launches the advance per epoch */
@@ -104,13 +210,6 @@ struct Batched {
     BOOL clip_commit(hpnn_clip_record *hist, unsigned int *cursor, unsigned int cap) {
         return clip && p.commit_clip(hist, cursor, cap, s) == 0;
     }
-    /* the schedule state of the live net, or of a [keep_best] snapshot (its last segment) */
-    BOOL read_schedule(void *const *src, hpnn_lr_state *out) {
-        HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(hipMemcpy(out, src ? src[masters().size() - 1] : (const void *)p.lrs_dev, sizeof *out,
-                         hipMemcpyDeviceToHost));
-        return TRUE;
-    }
     static constexpr size_t ACC_BYTES = HPNN_STAT_SLOTS * HPNN_STAT_STRIDE * 4;
     static int reduce_sum(grad_t *buf, int G, size_t count, hipStream_t st) {
         return hpnn_reduce_slabs(buf, G, (long)count, (long)count, buf, st);
@@ -130,7 +229,7 @@ struct Batched {
     BOOL read_stats(double *loss, unsigned int *hits) { return p.read_stats(loss, hits, s) == 0; }
 
     /* layer l: host FP64 [N][M] -> the zero-padded FP32 [Np][Kp] device buffer, and back */
-    BOOL pad_f32(float *dev, const DOUBLE *host, const layer_ann *ly, int l) {
+    BOOL to_dev(void *dev, const DOUBLE *host, const layer_ann *ly, int l) {
         const int M = (int)ly->n_inputs, N = (int)ly->n_neurons, Kp = p.Kp[l];
         std::vector<float> tmp((size_t)p.Np[l] * Kp, 0.f);
         for (int n = 0; n < N; n++)
@@ -139,7 +238,7 @@ struct Batched {
         HIPCHK(hipStreamSynchronize(s));
         return TRUE;
     }
-    BOOL unpad(DOUBLE *host, const float *dev, const layer_ann *ly, int l) {
+    BOOL to_host(DOUBLE *host, const void *dev, const layer_ann *ly, int l) {
         const int M = (int)ly->n_inputs, N = (int)ly->n_neurons, Kp = p.Kp[l];
         std::vector<float> tmp((size_t)p.Np[l] * Kp);
         HIPCHK(hipMemcpy(tmp.data(), dev, tmp.size() * 4, hipMemcpyDeviceToHost));
@@ -170,7 +269,7 @@ struct Batched {
         Bp = p.Bp;
         for (int l = 0; l < L; l++) {
             const layer_ann *ly = layer_of(k, l);
-            if (!pad_f32(p.W32[l], ly->weights, ly, l)) return FALSE;
+            if (!to_dev(p.W32[l], ly->weights, ly, l)) return FALSE;
         }
         if (p.cast_weights(s)) return FALSE;
         if (adam && hpnn_adam_preload(s)) return FALSE;
@@ -180,6 +279,9 @@ struct Batched {
         gflat = p.gflat;
         memcpy(goff, p.goff, sizeof goff);
         NN_DBG(stdout, "batched plan: mode %c, Bp %d, G0 splits %d\n", p.mode ? p.mode : '-', p.Bp, p.S[0]);
+        segs.clear();
+        for (int l = 0; l < L; l++) list_layer(l, p.W32[l], p.V32[l], p.A32[l], (size_t)p.Np[l] * p.Kp[l] * 4);
+        list_tail(adam_dev(), lr_dev());
         return TRUE;
     }
 
@@ -361,99 +463,9 @@ struct Batched {
         return p.weights_digest(sh ? 1 : 3, d, s) == 0;
     }
 
-    /* FP32 master weights (and BPM momentum, into k->dw) -> host FP64 */
-    BOOL download(kernel_ann *k) { return download_from(k, nullptr); }
-    /* [keep_best]: the buffers a snapshot copies, per layer the masters then the momentum;
-     * download_from reads copies of them in that order (null: the live ones) */
-    std::vector<std::pair<const void *, size_t>> masters() const {
-        std::vector<std::pair<const void *, size_t>> v;
-        for (int l = 0; l < L; l++)
-            for (const float *b : {p.W32[l], p.V32[l], p.A32[l]})
-                if (b) v.push_back({b, (size_t)p.Np[l] * p.Kp[l] * 4});
-        /* [train] ADAM: the state (t, p1, p2 and the coefficients) is one more segment */
-        if (adam) v.push_back({p.adam_dev, sizeof(hpnn_adam_state)});
-        /* [lr_schedule]: the schedule state, always the last segment */
-        if (sched) v.push_back({p.lrs_dev, sizeof(hpnn_lr_state)});
-        return v;
-    }
-    BOOL download_from(kernel_ann *k, void *const *src) {
-        HIPCHK(hipStreamSynchronize(s));
-        if (p.V32[0]) ann_momentum_init(k);
-        if (adam) ann_adam_init(k);
-        for (int l = 0, i = 0; l < L; l++) {
-            layer_ann *ly = layer_of(k, l);
-            if (!unpad(ly->weights, src ? (const float *)src[i] : p.W32[l], ly, l)) return FALSE;
-            i++;
-            if (!p.V32[l]) continue;
-            if (!unpad(k->dw[l], src ? (const float *)src[i] : p.V32[l], ly, l)) return FALSE;
-            i++;
-            if (!p.A32[l]) continue;
-            if (!unpad(k->dv[l], src ? (const float *)src[i] : p.A32[l], ly, l)) return FALSE;
-            i++;
-        }
-        if (adam) {
-            hpnn_adam_state st;
-            HIPCHK(hipMemcpy(&st, src ? src[3 * L] : (const void *)p.adam_dev, sizeof st, hipMemcpyDeviceToHost));
-            k->adam_t = st.t;
-            k->adam_p1 = st.p1;
-            k->adam_p2 = st.p2;
-        }
-        return TRUE;
-    }
-
-    /* the replica state (FP32 masters + momentum, padded) as bytes, and back (then the BF16
-     * copies are re-derived): rank 0's state re-broadcast after an exchange fallback */
-    BOOL get_state(std::vector<char> &out) {
-        out.clear();
-        HIPCHK(hipStreamSynchronize(s));
-        for (int l = 0; l < L; l++)
-            for (float *b : {p.W32[l], p.V32[l], p.A32[l]}) {
-                if (!b) continue;
-                const size_t n = (size_t)p.Np[l] * p.Kp[l] * 4, o = out.size();
-                out.resize(o + n);
-                HIPCHK(hipMemcpy(out.data() + o, b, n, hipMemcpyDeviceToHost));
-            }
-        if (adam) {
-            const size_t o = out.size();
-            out.resize(o + sizeof(hpnn_adam_state));
-            HIPCHK(hipMemcpy(out.data() + o, p.adam_dev, sizeof(hpnn_adam_state), hipMemcpyDeviceToHost));
-        }
-        return TRUE;
-    }
+    /* a state from another replica: the BF16 copies are re-derived from the masters */
     BOOL set_state(const char *in) {
-        size_t o = 0;
-        for (int l = 0; l < L; l++)
-            for (float *b : {p.W32[l], p.V32[l], p.A32[l]}) {
-                if (!b) continue;
-                const size_t n = (size_t)p.Np[l] * p.Kp[l] * 4;
-                HIPCHK(hipMemcpy(b, in + o, n, hipMemcpyHostToDevice));
-                o += n;
-            }
-        if (adam) HIPCHK(hipMemcpy(p.adam_dev, in + o, sizeof(hpnn_adam_state), hipMemcpyHostToDevice));
-        return p.cast_weights(s) == 0 && hipStreamSynchronize(s) == hipSuccess;
-    }
-
-    /* exact resume: BPM momentum k->dw (host FP64) -> padded FP32 V32 */
-    BOOL upload_momentum(const kernel_ann *k) {
-        if (!k->dw) return TRUE;
-        for (int l = 0; l < L; l++)
-            if (p.V32[l] && !pad_f32(p.V32[l], k->dw[l], layer_of((kernel_ann *)k, l), l)) return FALSE;
-        return TRUE;
-    }
-    /* exact resume under ADAM: both moments (the padding stays zero) and t, p1, p2 */
-    BOOL upload_moments(const kernel_ann *k) {
-        if (!adam || !k->dw || !k->dv) return TRUE;
-        if (!upload_momentum(k)) return FALSE;
-        for (int l = 0; l < L; l++)
-            if (!pad_f32(p.A32[l], k->dv[l], layer_of((kernel_ann *)k, l), l)) return FALSE;
-        hpnn_adam_state st;
-        HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(hipMemcpy(&st, p.adam_dev, sizeof st, hipMemcpyDeviceToHost));
-        st.t = k->adam_t;
-        st.p1 = k->adam_p1;
-        st.p2 = k->adam_p2;
-        HIPCHK(hipMemcpy(p.adam_dev, &st, sizeof st, hipMemcpyHostToDevice));
-        return TRUE;
+        return NetState::set_state(in) && p.cast_weights(s) == 0 && hipStreamSynchronize(s) == hipSuccess;
     }
 };
 
@@ -465,7 +477,7 @@ struct Batched {
  * padding: the kernels take any shape; the backward delta reads W itself (transposed
  * operand), so no W^T copy is kept. */
 template <typename T>
-struct BatchedFP {
+struct BatchedFP : NetState<BatchedFP<T>> {
     typedef T target_t;
     typedef T grad_t;
     static constexpr int F64 = sizeof(T) == 8 ? 1 : 0;
@@ -631,34 +643,6 @@ struct BatchedFP {
         adam = true;
         return hpnn_adam_preload(s) == 0;
     }
-    /* backprop -> advance -> one update launch over every layer */
-    BOOL step_adam(const XSet &xs, long row, const T *Tt, int ldt, int n_valid) {
-        if (!backprop(at(xs, row), Tt, ldt, n_valid)) return FALSE;
-        if (!clip_factor(1.0 / (double)n_valid)) return FALSE;
-        if (hpnn_adam_advance_dev(adam_state.get(), s) ||
-            hpnn_adam_fp_clip(F64, adam_table.get(), L, 1.0 / (double)n_valid, adam_state.get(), clip_dev(), s))
-            return FALSE;
-        return hpnn_debug_check("batched Adam step (fp)") == 0;
-    }
-    /* exact resume: the moments k->dw, k->dv (host FP64) -> V, A2; t, p1, p2 -> the device state */
-    BOOL upload_moments(const kernel_ann *k) {
-        if (!adam || !k->dw || !k->dv) return TRUE;
-        if (!upload_momentum(k)) return FALSE;
-        for (int l = 0; l < L; l++) {
-            const size_t nw = (size_t)N[l] * M[l];
-            std::vector<T> tmp(nw);
-            for (size_t i = 0; i < nw; i++) tmp[i] = (T)k->dv[l][i];
-            HIPCHK(hipMemcpyAsync(A2[l], tmp.data(), nw * sizeof(T), hipMemcpyHostToDevice, s));
-            HIPCHK(hipStreamSynchronize(s));
-        }
-        hpnn_adam_state st;
-        HIPCHK(hipMemcpy(&st, adam_state.get(), sizeof st, hipMemcpyDeviceToHost));
-        st.t = k->adam_t;
-        st.p1 = k->adam_p1;
-        st.p2 = k->adam_p2;
-        HIPCHK(hipMemcpy(adam_state.get(), &st, sizeof st, hipMemcpyHostToDevice));
-        return TRUE;
-    }
 
     /* [lr_schedule] (kernels_lrsched.hip, docs/DESIGN.md 3.2j): the device state, and for BP / BPM
      * the segment table of the one update launch that reads its rate from it -- allocated only
@@ -675,7 +659,7 @@ struct BatchedFP {
     }
     hpnn_lr_state *lr_dev() const { return sched ? sched_state.get() : nullptr; }
     hpnn_adam_state *adam_dev() const { return adam ? adam_state.get() : nullptr; }
-    /* the device state and, for BP / BPM, the table of step_sched ([clip] alone: a constant rate) */
+    /* the device state and, for BP / BPM, the table of the scheduled update ([clip] alone: a constant rate) */
     BOOL init_sched_buffers(const hpnn_lr_state &cfg, bool momentum) {
         HIPCHK(sched_state.alloc(1));
         HIPCHK(hipMemcpyAsync(sched_state.get(), &cfg, sizeof cfg, hipMemcpyHostToDevice, s));
@@ -758,21 +742,6 @@ struct BatchedFP {
         clip_launches++;
         return clip && hpnn_clip_commit_dev(clip_state.get(), hist, cursor, cap, s) == 0;
     }
-    /* backprop -> one update launch over every layer, the rate read from the device state */
-    BOOL step_sched(const XSet &xs, long row, const T *Tt, int ldt, int n_valid, double alpha, bool mom) {
-        if (!backprop(at(xs, row), Tt, ldt, n_valid)) return FALSE;
-        if (!clip_factor(1.0 / (double)n_valid)) return FALSE;
-        if (hpnn_sgd_sched_fp_clip(F64, sched_table.get(), L, 1.0 / (double)n_valid, alpha, mom ? 1 : 0,
-                                   sched_state.get(), clip_dev(), s))
-            return FALSE;
-        return hpnn_debug_check("batched scheduled step (fp)") == 0;
-    }
-    BOOL read_schedule(void *const *src, hpnn_lr_state *out) {
-        HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(hipMemcpy(out, src ? src[masters().size() - 1] : (const void *)sched_state.get(), sizeof *out,
-                         hipMemcpyDeviceToHost));
-        return TRUE;
-    }
 
     BOOL evaluate(const XSet &vs, const T *Tt, int ldt, int nv) {
         for (long row = 0; row < nv; row += Bp) {
@@ -825,17 +794,35 @@ struct BatchedFP {
             }
             HIPCHK(hpnn_dev_malloc(&D[l], (size_t)Bp * N[l] * sizeof(T)));
             if (l < L - 1) HIPCHK(hpnn_dev_malloc(&H[l], (size_t)Bp * N[l] * sizeof(T)));
-            std::vector<T> tmp(nw);
-            for (size_t i = 0; i < nw; i++) tmp[i] = (T)ly->weights[i];
-            HIPCHK(hipMemcpyAsync(W[l], tmp.data(), nw * sizeof(T), hipMemcpyHostToDevice, s));
-            HIPCHK(hipStreamSynchronize(s));
+            if (!to_dev(W[l], ly->weights, ly, l)) return FALSE;
         }
         HIPCHK(hpnn_dev_malloc(&Z, (size_t)Bp * N[L - 1] * sizeof(T)));
         HIPCHK(hpnn_dev_malloc(&acc, ACC_BYTES));
         HIPCHK(hipMemsetAsync(acc, 0, ACC_BYTES, s));
         if (adam_req && !init_adam(adam_cfg)) return FALSE;
         if (sched_req && !init_schedule(momentum)) return FALSE;
-        return clip_req ? init_clip(momentum) : TRUE;
+        if (clip_req && !init_clip(momentum)) return FALSE;
+        this->segs.clear();
+        for (int l = 0; l < L; l++) this->list_layer(l, W[l], V[l], A2[l], (size_t)N[l] * M[l] * sizeof(T));
+        this->list_tail(adam_dev(), lr_dev());
+        return TRUE;
+    }
+
+    /* layer l: host FP64 [N][M] -> the device matrix of T (a cast; no padding), and back */
+    BOOL to_dev(void *dev, const DOUBLE *host, const layer_ann *, int l) {
+        const size_t nw = (size_t)N[l] * M[l];
+        std::vector<T> tmp(nw);
+        for (size_t i = 0; i < nw; i++) tmp[i] = (T)host[i];
+        HIPCHK(hipMemcpyAsync(dev, tmp.data(), nw * sizeof(T), hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return TRUE;
+    }
+    BOOL to_host(DOUBLE *host, const void *dev, const layer_ann *, int l) {
+        const size_t nw = (size_t)N[l] * M[l];
+        std::vector<T> tmp(nw);
+        HIPCHK(hipMemcpy(tmp.data(), dev, nw * sizeof(T), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < nw; i++) host[i] = (DOUBLE)tmp[i];
+        return TRUE;
     }
 
     BOOL forward(const void *X, int rows) {
@@ -874,10 +861,26 @@ struct BatchedFP {
         return TRUE;
     }
 
+    /* one minibatch under every optimizer: backprop -> the clip factor ([clip]) -> the update */
     BOOL step(const XSet &xs, long row, const T *Tt, int ldt, int n_valid, double lr, double alpha, bool mom) {
-        if (sched || clip) return step_sched(xs, row, Tt, ldt, n_valid, alpha, mom);
-        if (!backprop(at(xs, row), Tt, ldt, n_valid)) return FALSE;
         const double scale = 1.0 / (double)n_valid;
+        return backprop(at(xs, row), Tt, ldt, n_valid) && clip_factor(scale) && update(scale, lr, alpha, mom);
+    }
+    /* ADAM: the advance plus one launch over every layer; a device rate ([lr_schedule], [clip]):
+     * one launch over every layer; plain BP / BPM: one launch per layer with the host's rate */
+    BOOL update(double scale, double lr, double alpha, bool mom) {
+        if (adam) {
+            if (hpnn_adam_advance_dev(adam_state.get(), s) ||
+                hpnn_adam_fp_clip(F64, adam_table.get(), L, scale, adam_state.get(), clip_dev(), s))
+                return FALSE;
+            return hpnn_debug_check("batched Adam step (fp)") == 0;
+        }
+        if (sched || clip) {
+            if (hpnn_sgd_sched_fp_clip(F64, sched_table.get(), L, scale, alpha, mom ? 1 : 0, sched_state.get(),
+                                       clip_dev(), s))
+                return FALSE;
+            return hpnn_debug_check("batched scheduled step (fp)") == 0;
+        }
         for (int l = 0; l < L; l++)
             if (hpnn_update_fp(F64, W[l], V[l], slab[l], S[l], (long)N[l] * M[l], (long)N[l] * M[l], lr, alpha, scale,
                                mom ? 1 : 0, s))
@@ -956,92 +959,6 @@ struct BatchedFP {
     }
     bool has_dpx() const { return false; }
     void detach_dpx() {}
-
-    BOOL download(kernel_ann *k) { return download_from(k, nullptr); }
-    /* [keep_best]: as Batched::masters / download_from (unpadded, any shape); with ADAM the second
-     * moment follows the first, and the device state is one more segment behind the last layer */
-    std::vector<std::pair<const void *, size_t>> masters() const {
-        std::vector<std::pair<const void *, size_t>> v;
-        for (int l = 0; l < L; l++)
-            for (const T *b : {W[l], V[l], A2[l]})
-                if (b) v.push_back({b, (size_t)N[l] * M[l] * sizeof(T)});
-        if (adam) v.push_back({adam_state.get(), sizeof(hpnn_adam_state)});
-        /* [lr_schedule]: the schedule state, always the last segment */
-        if (sched) v.push_back({sched_state.get(), sizeof(hpnn_lr_state)});
-        return v;
-    }
-    BOOL download_from(kernel_ann *k, void *const *src) {
-        HIPCHK(hipStreamSynchronize(s));
-        if (V[0]) ann_momentum_init(k);
-        if (adam) ann_adam_init(k);
-        for (int l = 0, j = 0; l < L; l++) {
-            layer_ann *ly = layer_of(k, l);
-            const size_t nw = (size_t)N[l] * M[l];
-            std::vector<T> tmp(nw);
-            HIPCHK(hipMemcpy(tmp.data(), src ? (const T *)src[j] : W[l], nw * sizeof(T), hipMemcpyDeviceToHost));
-            j++;
-            for (size_t i = 0; i < nw; i++) ly->weights[i] = (DOUBLE)tmp[i];
-            if (!V[l]) continue;
-            HIPCHK(hipMemcpy(tmp.data(), src ? (const T *)src[j] : V[l], nw * sizeof(T), hipMemcpyDeviceToHost));
-            j++;
-            for (size_t i = 0; i < nw; i++) k->dw[l][i] = (DOUBLE)tmp[i];
-            if (!A2[l]) continue;
-            HIPCHK(hipMemcpy(tmp.data(), src ? (const T *)src[j] : A2[l], nw * sizeof(T), hipMemcpyDeviceToHost));
-            j++;
-            for (size_t i = 0; i < nw; i++) k->dv[l][i] = (DOUBLE)tmp[i];
-        }
-        if (adam) {
-            hpnn_adam_state st;
-            HIPCHK(hipMemcpy(&st, src ? src[3 * L] : (const void *)adam_state.get(), sizeof st, hipMemcpyDeviceToHost));
-            k->adam_t = st.t;
-            k->adam_p1 = st.p1;
-            k->adam_p2 = st.p2;
-        }
-        return TRUE;
-    }
-
-    BOOL get_state(std::vector<char> &out) {
-        out.clear();
-        HIPCHK(hipStreamSynchronize(s));
-        for (int l = 0; l < L; l++)
-            for (T *b : {W[l], V[l], A2[l]}) {
-                if (!b) continue;
-                const size_t n = (size_t)N[l] * M[l] * sizeof(T), o = out.size();
-                out.resize(o + n);
-                HIPCHK(hipMemcpy(out.data() + o, b, n, hipMemcpyDeviceToHost));
-            }
-        if (adam) {
-            const size_t o = out.size();
-            out.resize(o + sizeof(hpnn_adam_state));
-            HIPCHK(hipMemcpy(out.data() + o, adam_state.get(), sizeof(hpnn_adam_state), hipMemcpyDeviceToHost));
-        }
-        return TRUE;
-    }
-    BOOL set_state(const char *in) {
-        size_t o = 0;
-        for (int l = 0; l < L; l++)
-            for (T *b : {W[l], V[l], A2[l]}) {
-                if (!b) continue;
-                const size_t n = (size_t)N[l] * M[l] * sizeof(T);
-                HIPCHK(hipMemcpy(b, in + o, n, hipMemcpyHostToDevice));
-                o += n;
-            }
-        if (adam) HIPCHK(hipMemcpy(adam_state.get(), in + o, sizeof(hpnn_adam_state), hipMemcpyHostToDevice));
-        return TRUE;
-    }
-
-    BOOL upload_momentum(const kernel_ann *k) {
-        if (!k->dw) return TRUE;
-        for (int l = 0; l < L; l++) {
-            if (!V[l]) continue;
-            const size_t nw = (size_t)N[l] * M[l];
-            std::vector<T> tmp(nw);
-            for (size_t i = 0; i < nw; i++) tmp[i] = (T)k->dw[l][i];
-            HIPCHK(hipMemcpyAsync(V[l], tmp.data(), nw * sizeof(T), hipMemcpyHostToDevice, s));
-            HIPCHK(hipStreamSynchronize(s));
-        }
-        return TRUE;
-    }
 };
 
 /* the one dtype switch: calls f(NetTag<Net>()) with the adapter of `dt` */

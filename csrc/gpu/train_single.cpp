@@ -7,11 +7,94 @@
 #include <chrono>
 #include <map>
 
+#include "../core/export_records.h"
 #include "batched_net.h"
 
 using namespace hpnn::eng;
 
 namespace {
+
+/* the device side of a run that collect() reads back (no two members of one type) */
+template <class Net>
+struct RunDev {
+    Net &net;
+    hipStream_t s;
+    const hpnn_batched_opts *o;
+    const std::vector<UINT> &vsched; /* the absolute epoch of every scheduled validation pass */
+    const BestSnap *best;            /* null without [keep_best] */
+    const DevHistory<hpnn_val_record> &vh;
+    const DevHistory<double> &lrh;
+    const DevHistory<hpnn_clip_record> &clh;
+};
+
+/* what collect() reads: the best state and the histories, each up to the last epoch that counts */
+struct RunRecords {
+    hpnn_best_state hb = {};
+    std::vector<hpnn_val_record> vrec; /* with per-epoch metrics the replay loop reads pass vdone itself */
+    size_t vdone = 0;
+    std::vector<hpnn_cg_record> crec;
+    double cg_f0 = 0.0; /* [train] CG: the FP64 loss of the last iteration run */
+    std::vector<double> lrec;
+    std::vector<hpnn_clip_record> clrec;
+    hpnn_lr_state lrs; /* the schedule state of the returned kernel */
+};
+
+/* after the last of the e epochs run: every read-back, once, with its "filed" check */
+template <class Net>
+BOOL collect(const RunDev<Net> &d, int e, bool metrics, RunRecords *r) {
+    const hpnn_batched_opts *o = d.o;
+    hpnn_best_state &hb = r->hb;
+    std::vector<hpnn_val_record> &vrec = r->vrec;
+    r->lrs = o->lrs;
+    if (d.best && (hipStreamSynchronize(d.s) != hipSuccess ||
+                   hipMemcpy(&hb, d.best->state.get(), sizeof hb, hipMemcpyDeviceToHost) != hipSuccess))
+        return FALSE;
+    /* the passes up to the stopping one: the best pass and the stale ones behind it (those the
+     * replays filed after it are not reported) */
+    const size_t judged = hb.valid ? (size_t)hb.index + 1 + hb.stale : (size_t)hb.stale;
+    const bool validate = !d.vsched.empty();
+    if (validate && !metrics) {
+        /* the whole history, once; the cursor tells how many passes were filed */
+        unsigned int filed = 0;
+        if (!d.vh.read(d.s, &vrec, &filed)) return FALSE;
+        if (hb.stop ? filed < judged || judged > vrec.size() : filed != vrec.size()) {
+            NN_ERROR(stderr, "batched GPU training: %u validation records filed, %zu scheduled%s\n", filed,
+                     vrec.size(), hb.stop ? " (stopped early)" : "");
+            return FALSE;
+        }
+        r->vdone = hb.stop ? judged : vrec.size();
+    }
+    if (validate) vrec.resize(std::min(r->vdone, vrec.size()));
+    /* the epochs of the call that count: after a stop those up to the stopping pass's */
+    const size_t counted = hb.stop && !vrec.empty() ? d.vsched[vrec.size() - 1] - o->epoch0 : (size_t)e;
+    if constexpr (Net::has_cg) {
+        if (o->train == NN_TRAIN_CG) {
+            if (!d.net.read_cg(r->crec)) return FALSE;
+            if (r->crec.size() < (size_t)e) {
+                NN_ERROR(stderr, "batched GPU training: %zu CG records filed, %d iterations run\n", r->crec.size(), e);
+                return FALSE;
+            }
+            if (e > 0) r->cg_f0 = r->crec[e - 1].f0;
+            r->crec.resize(counted);
+        }
+    }
+    auto read = [&](const auto &h, auto *rec, const char *what) {
+        unsigned int filed = 0;
+        if (!h.read(d.s, rec, &filed)) return false;
+        if (filed < (unsigned int)e) {
+            NN_ERROR(stderr, "batched GPU training: %u %s filed, %d epochs run\n", filed, what, e);
+            return false;
+        }
+        rec->resize(counted);
+        return true;
+    };
+    /* [lr_schedule]: the rates, and the state of the best pass under [keep_best]; [clip]: the records */
+    if (o->sched && !(read(d.lrh, &r->lrec, "learning rates") &&
+                      d.net.read_schedule(hb.valid ? d.best->dst.data() : nullptr, &r->lrs)))
+        return FALSE;
+    return o->clip <= 0.0 || read(d.clh, &r->clrec, "clip records");
+}
+
 
 template <class Net>
 BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, const hpnn_batched_opts *o,
@@ -75,20 +158,11 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
         NN_OUT(stdout, "batched GPU training: Adam, beta1 %g beta2 %g epsilon %g decay %g\n", o->beta1, o->beta2,
                o->eps, o->decay);
     }
-    DevBuf<double> lrhist;
-    DevBuf<unsigned int> lrcur;
-    if (sched) {
-        HIPCHK(lrhist.alloc(o->epochs ? o->epochs : 1));
-        HIPCHK(lrcur.alloc(1));
-        HIPCHK(hipMemset(lrcur.get(), 0, sizeof(unsigned int)));
-    }
-    DevBuf<hpnn_clip_record> cliphist;
-    DevBuf<unsigned int> clipcur;
-    if (clip) {
-        HIPCHK(cliphist.alloc(o->epochs ? o->epochs : 1));
-        HIPCHK(clipcur.alloc(1));
-        HIPCHK(hipMemset(clipcur.get(), 0, sizeof(unsigned int)));
-    }
+    /* one rate ([lr_schedule]) and one clip record ([clip]) per epoch of the call */
+    DevHistory<double> lrh;
+    DevHistory<hpnn_clip_record> clh;
+    if (sched && !lrh.init(o->epochs)) return FALSE;
+    if (clip && !clh.init(o->epochs)) return FALSE;
     const int n_batches = (int)((n + B - 1) / B);
     int rows_p = (n_batches - 1) * B + net.Bp; /* last batch reads Bp rows */
     ResidentSet<TT> tr;
@@ -137,17 +211,14 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
     const bool validate = o->validate && o->Xv && o->Tv && o->nv;
     const int nval = validate ? (int)o->nv : 0;
     ResidentSet<TT> va;
-    DevBuf<hpnn_val_record> vhist;
-    DevBuf<unsigned int> vcur;
+    DevHistory<hpnn_val_record> vh;
     std::vector<UINT> vsched;
     if (validate) {
         vsched.resize(hpnn_validation_schedule(o->epoch0, o->epochs, o->validate, nullptr));
         hpnn_validation_schedule(o->epoch0, o->epochs, o->validate, vsched.data());
         int vrows = 0;
         if (!va.upload(net, o->Xv, o->Tv, o->nv, n_in, n_out, &vrows, o->type, s, true)) return FALSE;
-        HIPCHK(vhist.alloc(vsched.size() + 1));
-        HIPCHK(vcur.alloc(1));
-        HIPCHK(hipMemset(vcur.get(), 0, sizeof(unsigned int)));
+        if (!vh.init(vsched.size(), 1)) return FALSE;
         NN_OUT(stdout, "batched GPU training: %d held-out samples validated every %u epochs\n", nval, o->validate);
     }
     /* [keep_best]: behind the commit a one-thread launch judges the record just filed against
@@ -160,17 +231,17 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
     const bool keep = validate && o->keep_best != 0;
     BestSnap best;
     if (keep) {
-        if (!best.init(net.masters(), s)) return FALSE;
+        if (!best.init(net.segs, s)) return FALSE;
         NN_OUT(stdout, "batched GPU training: the best validation pass (%s) is kept\n",
                o->keep_best == NN_KEEP_ACC ? "acc" : "loss");
     }
     auto validation = [&]() -> bool {
         if (net.evaluate(va.xs, va.T.get(), n_out, nval) &&
-            hpnn_validate_commit(net.vacc(), vhist.get(), vcur.get(), (unsigned int)vsched.size(), s) == 0 &&
+            hpnn_validate_commit(net.vacc(), vh.hist(), vh.cursor(), vh.cap(), s) == 0 &&
             /* plateau sees the pass before the snapshot: the best state holds this pass */
-            (!sched || hpnn_lr_plateau_dev(vhist.get(), vcur.get(), net.lr_dev(), s) == 0) &&
-            (!keep || (hpnn_best_commit(vhist.get(), vcur.get(), best.state.get(), (int)o->keep_best, o->patience,
-                                        s) == 0 &&
+            (!sched || hpnn_lr_plateau_dev(vh.hist(), vh.cursor(), net.lr_dev(), s) == 0) &&
+            (!keep || (hpnn_best_commit(vh.hist(), vh.cursor(), best.state.get(), (int)o->keep_best, o->patience, s) ==
+                           0 &&
                        hpnn_snapshot_if(best.table.get(), (int)best.segs.size(), best.take(), s) == 0)))
             return true;
         NN_ERROR(stderr, "batched GPU training: the validation pass could not be launched\n");
@@ -190,7 +261,7 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
             if (cg) return net.iterate_cg(xs, Td, n_out, (int)n);
         }
         /* the first launch of every epoch: the rate of this epoch into the device state */
-        if (sched && hpnn_lr_advance_dev(net.lr_dev(), net.adam_dev(), lrhist.get(), lrcur.get(), o->epochs, s)) {
+        if (sched && hpnn_lr_advance_dev(net.lr_dev(), net.adam_dev(), lrh.hist(), lrh.cursor(), lrh.cap(), s)) {
             NN_ERROR(stderr, "batched GPU training: the schedule advance could not be launched\n");
             return false;
         }
@@ -201,14 +272,10 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
         for (int b = 0; b < n_batches; b++) {
             int start, nv, total;
             hpnn_dp_shard(b, B, (int)n, 0, B, &start, &nv, &total);
-            if (adam) {
-                if (!net.step_adam(xs, start, Td + (size_t)start * n_out, n_out, nv)) return false;
-                continue;
-            }
             if (!net.step(xs, start, Td + (size_t)start * n_out, n_out, nv, o->lr, o->alpha, mom)) return false;
         }
         /* the last launch of every epoch: its clip record into the device history */
-        if (clip && !net.clip_commit(cliphist.get(), clipcur.get(), o->epochs)) {
+        if (clip && !net.clip_commit(clh.hist(), clh.cursor(), clh.cap())) {
             NN_ERROR(stderr, "batched GPU training: the clip commit could not be launched\n");
             return false;
         }
@@ -278,8 +345,10 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
         if (d[4]) stopped = true;
         return true;
     };
-    std::vector<hpnn_val_record> vrec(vsched.size());
-    size_t vdone = 0;
+    RunRecords rec;
+    std::vector<hpnn_val_record> &vrec = rec.vrec;
+    size_t &vdone = rec.vdone;
+    vrec.resize(vsched.size());
     int e = 0;
     while (e < E && ok && !stopped) {
         const int ne = std::min(epg, E - e);
@@ -304,7 +373,7 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
                                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(),
                                (UINT64)n * e);
         if (ok && metrics && val_due(e - 1) && vdone < vrec.size()) {
-            ok = validation() && hipMemcpyAsync(&vrec[vdone], vhist.get() + vdone, sizeof(hpnn_val_record),
+            ok = validation() && hipMemcpyAsync(&vrec[vdone], vh.hist() + vdone, sizeof(hpnn_val_record),
                                                 hipMemcpyDeviceToHost, s) == hipSuccess &&
                  (!patient || hipMemcpyAsync(&hstop, best.stop(), 4, hipMemcpyDeviceToHost, s) == hipSuccess) &&
                  hipStreamSynchronize(s) == hipSuccess;
@@ -319,116 +388,26 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
     /* stopped before the last epoch: the statistics of the last epoch that ran */
     if (ok && !metrics && e < E) ok = net.read_stats(&ep_loss, &ep_hits);
     auto t1 = std::chrono::steady_clock::now();
-    hpnn_best_state hb;
-    memset(&hb, 0, sizeof hb);
-    if (ok && keep)
-        ok = hipStreamSynchronize(s) == hipSuccess &&
-             hipMemcpy(&hb, best.state.get(), sizeof hb, hipMemcpyDeviceToHost) == hipSuccess;
-    /* the passes up to the stopping one: the best pass and the stale ones behind it (those the
-     * replays filed after it are not reported) */
-    const size_t judged = hb.valid ? (size_t)hb.index + 1 + hb.stale : (size_t)hb.stale;
-    if (ok && validate && !metrics) {
-        /* the whole history, once; the cursor tells how many passes were filed */
-        unsigned int filed = 0;
-        ok = hipMemcpy(&filed, vcur.get(), sizeof filed, hipMemcpyDeviceToHost) == hipSuccess &&
-             hipMemcpy(vrec.data(), vhist.get(), vrec.size() * sizeof(hpnn_val_record), hipMemcpyDeviceToHost) ==
-                 hipSuccess;
-        if (ok && (hb.stop ? filed < judged || judged > vrec.size() : filed != vrec.size())) {
-            NN_ERROR(stderr, "batched GPU training: %u validation records filed, %zu scheduled%s\n", filed,
-                     vrec.size(), hb.stop ? " (stopped early)" : "");
-            ok = FALSE;
-        }
-        vdone = hb.stop ? judged : vrec.size();
-    }
-    if (ok && validate) vrec.resize(std::min(vdone, vrec.size()));
-    /* [train] CG: the history, once; the epoch's loss is the FP64 f0 of its record.  After a stop
-     * the iterations that ran past the stopping pass are not reported */
-    std::vector<hpnn_cg_record> crec;
-    if constexpr (Net::has_cg) {
-        if (ok && cg) {
-            ok = net.read_cg(crec);
-            if (ok && crec.size() < (size_t)e) {
-                NN_ERROR(stderr, "batched GPU training: %zu CG records filed, %d iterations run\n", crec.size(), e);
-                ok = FALSE;
-            }
-            if (ok && e > 0) ep_loss = crec[e - 1].f0 * (double)n;
-            if (ok) crec.resize(hb.stop && !vrec.empty() ? vsched[vrec.size() - 1] - o->epoch0 : (size_t)e);
-        }
-    }
-    /* [lr_schedule]: the history, once, up to the last epoch that counts (the stopping pass's epoch
-     * after an early stop), and the state of the returned kernel */
-    std::vector<double> lrec;
-    hpnn_lr_state lrs_out = o->lrs;
-    if (ok && sched) {
-        unsigned int filed = 0;
-        lrec.resize(o->epochs);
-        ok = hipStreamSynchronize(s) == hipSuccess &&
-             hipMemcpy(&filed, lrcur.get(), sizeof filed, hipMemcpyDeviceToHost) == hipSuccess &&
-             hipMemcpy(lrec.data(), lrhist.get(), lrec.size() * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
-        if (ok && filed < (unsigned int)e) {
-            NN_ERROR(stderr, "batched GPU training: %u learning rates filed, %d epochs run\n", filed, e);
-            ok = FALSE;
-        }
-        if (ok) lrec.resize(hb.stop && !vrec.empty() ? vsched[vrec.size() - 1] - o->epoch0 : (size_t)e);
-        if (ok) ok = net.read_schedule(hb.valid ? best.dst.data() : nullptr, &lrs_out);
-    }
-    /* [clip]: the history, once, up to the last epoch that counts, as the rates */
-    std::vector<hpnn_clip_record> clrec;
-    if (ok && clip) {
-        unsigned int filed = 0;
-        clrec.resize(o->epochs);
-        ok = hipStreamSynchronize(s) == hipSuccess &&
-             hipMemcpy(&filed, clipcur.get(), sizeof filed, hipMemcpyDeviceToHost) == hipSuccess &&
-             hipMemcpy(clrec.data(), cliphist.get(), clrec.size() * sizeof(hpnn_clip_record), hipMemcpyDeviceToHost) ==
-                 hipSuccess;
-        if (ok && filed < (unsigned int)e) {
-            NN_ERROR(stderr, "batched GPU training: %u clip records filed, %d epochs run\n", filed, e);
-            ok = FALSE;
-        }
-        if (ok) clrec.resize(hb.stop && !vrec.empty() ? vsched[vrec.size() - 1] - o->epoch0 : (size_t)e);
-    }
+    const RunDev<Net> dev{net, s, o, vsched, keep ? &best : nullptr, vh, lrh, clh};
+    if (ok) ok = collect(dev, e, metrics, &rec);
+    const hpnn_best_state &hb = rec.hb;
     graphs.clear();
     if (ok) ok = net.download_from(k, hb.valid ? best.dst.data() : nullptr);
     if (ok && st) {
+        if (cg && e > 0) ep_loss = rec.cg_f0 * (double)n;
         fill_stats(st, std::chrono::duration<double>(t1 - t0).count(), n, (UINT)e, ep_loss, ep_hits);
         st->epochs_run = (UINT)e;
         st->best_epoch = hb.valid ? vsched[hb.index] : 0;
         st->best_index = hb.valid ? hb.index : 0;
         st->stop_epoch = hb.stop && !vrec.empty() ? vsched[vrec.size() - 1] : 0;
-        st->cg = NULL;
-        st->n_cg = (UINT)crec.size();
-        if (!crec.empty()) {
-            st->cg = (hpnn_cg_record *)malloc(crec.size() * sizeof(hpnn_cg_record));
-            if (!st->cg) ok = FALSE;
-            else memcpy(st->cg, crec.data(), crec.size() * sizeof(hpnn_cg_record));
-        }
-        st->lrs = lrs_out;
-        st->lr_hist = NULL;
-        st->n_lr = (UINT)lrec.size();
-        if (!lrec.empty()) {
-            st->lr_hist = (DOUBLE *)malloc(lrec.size() * sizeof(DOUBLE));
-            if (!st->lr_hist) ok = FALSE;
-            else memcpy(st->lr_hist, lrec.data(), lrec.size() * sizeof(DOUBLE));
-        }
-        st->clip_hist = NULL;
-        st->n_clip = (UINT)clrec.size();
-        if (!clrec.empty()) {
-            st->clip_hist = (hpnn_clip_record *)malloc(clrec.size() * sizeof(hpnn_clip_record));
-            if (!st->clip_hist) ok = FALSE;
-            else memcpy(st->clip_hist, clrec.data(), clrec.size() * sizeof(hpnn_clip_record));
-        }
-        st->val = NULL;
-        st->n_val = (UINT)vrec.size();
-        if (!vrec.empty()) {
-            st->val = (hpnn_validation_record *)malloc(vrec.size() * sizeof(hpnn_validation_record));
-            if (!st->val) ok = FALSE;
-            for (size_t i = 0; ok && i < vrec.size(); i++) {
-                st->val[i].epoch = vsched[i];
-                st->val[i].loss = vrec[i].loss_sum / (double)nval;
-                st->val[i].correct = vrec[i].hits;
-                st->val[i].n = (UINT)nval;
-            }
-        }
+        st->lrs = rec.lrs;
+        std::vector<hpnn_validation_record> val(vrec.size());
+        for (size_t i = 0; i < val.size(); i++)
+            val[i] = {vsched[i], vrec[i].loss_sum / (double)nval, vrec[i].hits, (UINT)nval};
+        ok = export_records(rec.crec, &st->cg, &st->n_cg);
+        ok = export_records(rec.lrec, &st->lr_hist, &st->n_lr) && ok;
+        ok = export_records(rec.clrec, &st->clip_hist, &st->n_clip) && ok;
+        ok = export_records(val, &st->val, &st->n_val) && ok;
     }
     /* device FP64 copy of the online engine (if any) is now stale */
     hpnn_gpu_mark_host_dirty(k);

@@ -617,6 +617,35 @@ def test_keep_best_equals_the_best_epochs_run(gpu, data, dtype):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_keep_best_with_adam_plateau_and_clip_equals_the_best_epochs_run(gpu, data, dtype):
+    """the one snapshot that carries both trailing segments, the Adam state and the schedule state,
+    behind the three per layer; the rate and the epochs were chosen on the FP64 CPU engine: best
+    pass 5, plateau cuts before epochs 7 and 8, the stop at pass 8 of 12, 11 of 24 steps clipped"""
+    d = data[0]
+    epochs, lr, sched = 12, 0.03, dict(kind="plateau", gamma=0.5, patience=1)
+    kw = dict(train="ADAM", dtype=dtype, validate=1, lr=lr)
+    Q.write_conf(d, epochs=epochs, **kw)
+    huge = Q.train(d, "gpu", clip=1e300, lr_schedule=sched)  # unclipped: the norms of its own records
+    assert huge["ok"]
+    c = float(np.median([r["norm_last"] for r in huge["clip"]] + [r["norm_max"] for r in huge["clip"]]))
+    kept = Q.train(d, "gpu", clip=c, lr_schedule=sched, keep_best="loss", patience=3)
+    assert kept["ok"]
+    b = kept["best"]["epoch"]
+    clipped, steps = sum(r["clipped"] for r in kept["clip"]), sum(r["steps"] for r in kept["clip"])
+    print(f"{dtype}: max_norm {c:.6g}, best epoch {b}, {len(kept['val'])} passes, clipped {clipped}/{steps}, "
+          f"rates {kept['lr']}")
+    assert 1 < b < epochs, "the fixture is at fault: the best pass is the first or the last"
+    assert min(kept["lr"]) < lr, "the fixture is at fault: no plateau cut"
+    assert 0 < clipped < steps, "the fixture is at fault: every step or no step clipped"
+    assert kept["epochs_done"] == b and len(kept["clip"]) == len(kept["lr"]) == len(kept["val"])
+    Q.write_conf(d, epochs=b, **kw)
+    plain = Q.train(d, "gpu", clip=c, lr_schedule=sched)
+    assert plain["raw"] == kept["raw"] and plain["clip"] == kept["clip"][:b]
+    assert [Q.bits(x) for x in plain["lr"]] == [Q.bits(x) for x in kept["lr"][:b]]
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("env,msg", [
     ({"HPNN_LOOPBACK_RANKS": "2"}, "[clip] is not supported by data-parallel batched training"),
     ({"HPNN_PARALLEL": "tp"}, "[clip] is not supported by tensor-parallel batched training"),
