@@ -18,8 +18,9 @@
  *                                  random()*n/RAND_MAX == n overflow is
  *                                  rejected instead of indexing past the end)
  *   nn_run_kernel                 :1306-1536
- * Extensions: [mode] online|batched, [dtype], [device], [batch], [epochs], [shuffle], [validate],
- * [keep_best], [patience], [lr], [momentum] conf keys; batched training on CPU (FP64) or GPU.
+ * Extensions: batched training on the CPU (FP64) or the GPU, and the conf keys that go with it.
+ * Every conf key, the reference's and the extensions', is one row of CONF_KEYS (conf_keys.h): the
+ * row is what nn_load_conf reads the key with and what nn_dump_conf writes it with.
  */
 #include <libhpnn/ann.h>
 #include <ctype.h>
@@ -35,7 +36,9 @@
 #include <libhpnn/observe.h>
 #include <omp.h>
 
+#include "conf_keys.h"
 #include "dataset.h"
+#include "lr_running.h"
 #include "runtime_internal.h"
 #include "../gpu/engine.h"
 
@@ -65,6 +68,34 @@ extern "C" void _NN(init, conf)(nn_def *conf) {
     conf->lr_gamma = conf->lr_end = conf->lr_min = NAN; /* not set */
 }
 
+/* The per-epoch histories of the last nn_train_kernel call ([validate], [train] CG, [lr_schedule],
+ * [clip]): malloc'ed by the engine, owned by the conf from adopt_histories until drop_histories. */
+template <class T>
+static void drop(T *&array, UINT &count) {
+    free(array);
+    array = NULL;
+    count = 0;
+}
+
+static void drop_histories(nn_def *conf) {
+    drop(conf->validation, conf->n_validation);
+    drop(conf->cg_history, conf->n_cg_history);
+    drop(conf->lr_history, conf->n_lr_history);
+    drop(conf->clip_history, conf->n_clip_history);
+}
+
+static void adopt_histories(nn_def *conf, const hpnn_batched_stats *st) {
+    drop_histories(conf);
+    conf->validation = st->val;
+    conf->n_validation = st->n_val;
+    conf->cg_history = st->cg;
+    conf->n_cg_history = st->n_cg;
+    conf->lr_history = st->lr_hist;
+    conf->n_lr_history = st->n_lr;
+    conf->clip_history = st->clip_hist;
+    conf->n_clip_history = st->n_clip;
+}
+
 extern "C" void _NN(free, kernel)(nn_def *conf) {
     if (!conf || !conf->kernel) return;
     ann_kernel_free(KERN(conf));
@@ -78,24 +109,8 @@ extern "C" void _NN(deinit, conf)(nn_def *conf) {
     free(conf->f_kernel);
     free(conf->samples);
     free(conf->tests);
-    free(conf->validation);
-    conf->validation = NULL;
-    conf->n_validation = 0;
-    free(conf->cg_history);
-    conf->cg_history = NULL;
-    conf->n_cg_history = 0;
-    free(conf->lr_history);
-    conf->lr_history = NULL;
-    conf->n_lr_history = 0;
-    free(conf->clip_history);
-    conf->clip_history = NULL;
-    conf->n_clip_history = 0;
+    drop_histories(conf);
     conf->name = conf->f_kernel = conf->samples = conf->tests = NULL;
-}
-
-static void set_str(CHAR **dst, const CHAR *src) {
-    free(*dst);
-    *dst = src ? strdup(src) : NULL;
 }
 
 extern "C" void _NN(set, name)(nn_def *c, const CHAR *n) {
@@ -230,275 +245,54 @@ extern "C" const DOUBLE *_NN(get, lr_history)(nn_def *c, UINT *n) {
 extern "C" UINT _NN(return, last_pass)(void) { return g_last_pass; }
 extern "C" UINT _NN(return, last_total)(void) { return g_last_total; }
 
-/* ---- conf parsing helpers ---- */
-static std::string trim(const std::string &s) {
-    size_t a = 0, b = s.size();
-    while (a < b && isspace((unsigned char)s[a])) a++;
-    while (b > a && isspace((unsigned char)s[b - 1])) b--;
-    return s.substr(a, b - a);
-}
-/* strip a trailing '#' comment */
-static std::string value_of(const char *after) {
-    std::string v(after);
-    size_t h = v.find('#');
-    if (h != std::string::npos) v = v.substr(0, h);
-    return trim(v);
-}
-
-static bool parse_uint_list(const std::string &v, std::vector<UINT> &out) {
-    const char *p = v.c_str();
-    char *e;
-    out.clear();
-    while (*p) {
-        while (*p && isspace((unsigned char)*p)) p++;
-        if (!*p) break;
-        if (!isdigit((unsigned char)*p)) return false;
-        out.push_back((UINT)strtoul(p, &e, 10));
-        p = e;
-    }
-    return !out.empty();
-}
-
+/* ------------------------------------------------------------------ */
+/* the conf keys                                                       */
+/* ------------------------------------------------------------------ */
 extern "C" nn_def *_NN(load, conf)(const CHAR *filename) {
-    nn_def *conf = (nn_def *)calloc(1, sizeof(nn_def));
-    _NN(init, conf)(conf);
-    UINT n_in = 0, n_out = 0;
-    std::vector<UINT> hid;
     FILE *fp = fopen(filename, "r");
-    char *buf = NULL;
-    size_t cap = 0;
     if (!fp) {
         NN_ERROR(stderr, "Error opening configuration file: %s\n", filename);
-        free(conf);
         return NULL;
     }
-#define CONF_FAIL(...)                                                     \
-    do {                                                                   \
-        NN_ERROR(stderr, "Malformed NN configuration file!\n");            \
-        NN_ERROR(stderr, __VA_ARGS__);                                     \
-        goto fail;                                                         \
-    } while (0)
-    while (hpnn_readline(fp, &buf, &cap)) {
+    ConfLoad l = {(nn_def *)calloc(1, sizeof(nn_def)), 0, 0, {}, NULL};
+    _NN(init, conf)(l.conf);
+    char *buf = NULL;
+    size_t cap = 0;
+    bool ok = true;
+    while (ok && hpnn_readline(fp, &buf, &cap)) {
         const char *lb = strchr(buf, '[');
-        if (!lb) continue;
-        const char *rb = strchr(lb, ']');
+        const char *rb = lb ? strchr(lb, ']') : NULL;
         if (!rb) continue;
-        std::string key(lb + 1, rb - lb - 1);
-        std::string v = value_of(rb + 1);
-        auto is = [&](const char *k) { return key.compare(0, strlen(k), k) == 0; };
-        if (is("name")) {
-            set_str(&conf->name, v.c_str());
-        } else if (is("type")) {
-            switch (v.empty() ? 'A' : toupper(v[0])) {
-                case 'L': conf->type = NN_TYPE_LNN; break;
-                case 'S': conf->type = NN_TYPE_SNN; break;
-                default: conf->type = NN_TYPE_ANN; break;
-            }
-        } else if (is("init")) {
-            if (v.find("generate") != std::string::npos || v.find("GENERATE") != std::string::npos) {
-                NN_OUT(stdout, "generating kernel!\n");
-                conf->need_init = TRUE;
-            } else {
-                NN_OUT(stdout, "loading kernel!\n");
-                conf->need_init = FALSE;
-                if (v.empty()) CONF_FAIL("[init] can't read filename: %s\n", buf);
-                set_str(&conf->f_kernel, v.c_str());
-            }
-        } else if (is("seed")) {
-            if (v.empty() || !isdigit((unsigned char)v[0])) CONF_FAIL("[seed] value: %s\n", v.c_str());
-            conf->seed = (UINT)strtoul(v.c_str(), NULL, 10);
-        } else if (is("input")) {
-            if (v.empty() || !isdigit((unsigned char)v[0])) CONF_FAIL("[input] value: %s\n", v.c_str());
-            n_in = (UINT)strtoul(v.c_str(), NULL, 10);
-        } else if (is("hidden")) {
-            if (!parse_uint_list(v, hid)) CONF_FAIL("[hidden] value: %s\n", v.c_str());
-        } else if (is("output")) {
-            if (v.empty() || !isdigit((unsigned char)v[0])) CONF_FAIL("[output] value: %s\n", v.c_str());
-            n_out = (UINT)strtoul(v.c_str(), NULL, 10);
-        } else if (is("train")) {
-            std::string u = v;
-            for (auto &ch : u) ch = (char)toupper(ch);
-            if (!u.empty() && u[0] == 'B') conf->train = (u.size() > 2 && u[2] == 'M') ? NN_TRAIN_BPM : NN_TRAIN_BP;
-            else if (!u.empty() && u[0] == 'C') conf->train = NN_TRAIN_CG;
-            else if (!u.empty() && u[0] == 'A') conf->train = NN_TRAIN_ADAM;
-            else if (!u.empty() && u[0] == 'S') conf->train = NN_TRAIN_SPLX;
-            else conf->train = NN_TRAIN_UKN;
-        } else if (is("sample_dir") || is("samples")) {
-            set_str(&conf->samples, v.c_str());
-        } else if (is("test_dir") || is("tests")) {
-            set_str(&conf->tests, v.c_str());
-        } else if (is("mode")) {
-            conf->mode = (!v.empty() && toupper(v[0]) == 'B') ? NN_MODE_BATCHED : NN_MODE_ONLINE;
-        } else if (is("dtype")) {
-            std::string u = v;
-            for (auto &ch : u) ch = (char)tolower(ch);
-            if (u == "bf16") conf->dtype = NN_DTYPE_BF16;
-            else if (u == "f32" || u == "fp32" || u == "float") conf->dtype = NN_DTYPE_F32;
-            else if (u == "f64" || u == "fp64" || u == "double") conf->dtype = NN_DTYPE_F64;
-            else CONF_FAIL("[dtype] unknown: %s (f64 | f32 | bf16)\n", v.c_str()); /* docs/PARITY.md */
-        } else if (is("shuffle")) {
-            std::string u = v;
-            for (auto &ch : u) ch = (char)tolower(ch);
-            if (u == "epoch") conf->shuffle = NN_SHUFFLE_EPOCH;
-            else if (u == "once") conf->shuffle = NN_SHUFFLE_ONCE;
-            else CONF_FAIL("[shuffle] unknown: %s (once | epoch)\n", v.c_str());
-        } else if (is("validate")) {
-            char *end = NULL;
-            const unsigned long every = strtoul(v.c_str(), &end, 10);
-            if (v.empty() || !isdigit((unsigned char)v[0]) || every == 0 || every > 0xffffffffUL)
-                CONF_FAIL("[validate] value: %s (epochs between validation passes, >= 1)\n", v.c_str());
-            conf->validate = (UINT)every;
-        } else if (is("keep_best")) {
-            std::string u = v;
-            for (auto &ch : u) ch = (char)tolower(ch);
-            if (u == "loss") conf->keep_best = NN_KEEP_LOSS;
-            else if (u == "acc") conf->keep_best = NN_KEEP_ACC;
-            else CONF_FAIL("[keep_best] unknown: %s (loss | acc)\n", v.c_str());
-        } else if (is("patience")) {
-            const unsigned long passes = strtoul(v.c_str(), NULL, 10);
-            if (v.empty() || !isdigit((unsigned char)v[0]) || passes == 0 || passes > 0xffffffffUL)
-                CONF_FAIL("[patience] value: %s (validation passes without improvement, >= 1)\n", v.c_str());
-            conf->patience = (UINT)passes;
-        } else if (is("device")) {
-            std::string u = v;
-            for (auto &ch : u) ch = (char)tolower(ch);
-            conf->device = u == "cpu" ? NN_DEVICE_CPU : (u == "gpu" ? NN_DEVICE_GPU : NN_DEVICE_AUTO);
-        } else if (is("batch")) {
-            conf->batch = (UINT)strtoul(v.c_str(), NULL, 10);
-            if (!conf->batch) conf->batch = 1;
-        } else if (is("epochs")) {
-            conf->epochs = (UINT)strtoul(v.c_str(), NULL, 10);
-            if (!conf->epochs) conf->epochs = 1;
-        } else if (is("parallel")) {
-            std::string u = v;
-            for (auto &ch : u) ch = (char)tolower(ch);
-            conf->parallel = u == "tp" ? NN_PARALLEL_TP : NN_PARALLEL_DP;
-        } else if (is("clip")) {
-            char *end = NULL;
-            const DOUBLE x = strtod(v.c_str(), &end);
-            if (v.empty() || end == v.c_str() || !hpnn_clip_valid(x))
-                CONF_FAIL("[clip] value: %s (the largest gradient norm, finite and > 0; 0: off)\n", v.c_str());
-            conf->clip = x;
-        } else if (is("lr_schedule")) {
-            std::string u = v;
-            for (auto &ch : u) ch = (char)tolower(ch);
-            if (u == "constant") conf->lr_schedule = NN_LR_CONSTANT;
-            else if (u == "step") conf->lr_schedule = NN_LR_STEP;
-            else if (u == "linear") conf->lr_schedule = NN_LR_LINEAR;
-            else if (u == "plateau") conf->lr_schedule = NN_LR_PLATEAU;
-            else CONF_FAIL("[lr_schedule] unknown: %s (constant | step | linear | plateau)\n", v.c_str());
-        } else if (is("lr_gamma") || is("lr_end") || is("lr_min")) {
-            /* checked before [lr]: the keys are matched by prefix */
-            char *end = NULL;
-            const DOUBLE x = strtod(v.c_str(), &end);
-            const bool gam = key[3] == 'g', fin = x - x == 0.0;
-            if (v.empty() || end == v.c_str() || !fin || (gam ? !(x > 0.0 && x <= 1.0) : key[3] == 'm' && x < 0.0))
-                CONF_FAIL("[%s] value: %s (%s)\n", key.c_str(), v.c_str(),
-                          gam ? "0 < gamma <= 1" : key[3] == 'm' ? ">= 0" : "a finite rate");
-            (gam ? conf->lr_gamma : key[3] == 'm' ? conf->lr_min : conf->lr_end) = x;
-        } else if (is("lr_period") || is("lr_span") || is("lr_patience") || is("warmup")) {
-            char *end = NULL;
-            const unsigned long x = strtoul(v.c_str(), &end, 10);
-            const bool wu = key[0] == 'w';
-            if (v.empty() || !isdigit((unsigned char)v[0]) || (!wu && x == 0) || x > 0xffffffffUL)
-                CONF_FAIL("[%s] value: %s (epochs%s)\n", key.c_str(), v.c_str(), wu ? ", >= 0" : ", >= 1");
-            (wu ? conf->warmup : key[4] == 'e' ? conf->lr_period : key[3] == 's' ? conf->lr_span : conf->lr_patience) =
-                (UINT)x;
-        } else if (is("lr")) {
-            conf->lr = strtod(v.c_str(), NULL);
-        } else if (is("momentum")) {
-            conf->momentum = strtod(v.c_str(), NULL);
-        } else if (is("beta1") || is("beta2") || is("epsilon") || is("decay")) {
-            /* [train] ADAM; no earlier key is a prefix of these ([batch] is not one of [beta1]) */
-            char *end = NULL;
-            const DOUBLE x = strtod(v.c_str(), &end);
-            const bool beta = key[0] == 'b';
-            const bool bad = v.empty() || end == v.c_str() || x != x ||
-                             (beta ? (x < 0.0 || x >= 1.0) : key[0] == 'e' ? !(x > 0.0) : x < 0.0);
-            if (bad)
-                CONF_FAIL("[%s] value: %s (%s)\n", key.c_str(), v.c_str(),
-                          beta ? "0 <= beta < 1" : key[0] == 'e' ? "> 0" : ">= 0");
-            (beta ? (key.compare(0, 5, "beta1") == 0 ? conf->beta1 : conf->beta2)
-                  : key[0] == 'e' ? conf->epsilon : conf->decay) = x;
-        }
+        const std::string key(lb + 1, rb - lb - 1);
+        l.line = buf;
+        if (const ConfKey *row = find_key(key)) ok = load_key(l, *row, key, value_of(rb + 1));
     }
     fclose(fp);
-    fp = NULL;
-    if (conf->type == NN_TYPE_UKN) CONF_FAIL("[type] unknown or missing...\n");
-    if (conf->need_init) {
-        if (n_in == 0) CONF_FAIL("[input] wrong or missing...\n");
-        if (hid.empty()) CONF_FAIL("[hidden] wrong or missing...\n");
-        if (n_out == 0) CONF_FAIL("[output] wrong or missing...\n");
-        for (UINT h : hid)
-            if (h == 0) CONF_FAIL("[hidden] some have a 0 neuron content!\n");
-        if (!_NN(generate, kernel)(conf, n_in, (UINT)hid.size(), n_out, hid.data())) {
-            NN_ERROR(stderr, "FAILED to generate NN kernel!\n");
-            goto fail;
-        }
-    } else {
-        if (!_NN(load, kernel)(conf)) {
-            NN_ERROR(stderr, "FAILED to load the NN kernel!\n");
-            goto fail;
-        }
-    }
+    ok = ok && finish_load(l);
     free(buf);
-    return conf;
-fail:
-#undef CONF_FAIL
-    if (fp) fclose(fp);
-    free(buf);
-    _NN(deinit, conf)(conf);
-    free(conf);
+    if (ok) return l.conf;
+    _NN(deinit, conf)(l.conf);
+    free(l.conf);
     return NULL;
 }
 
 extern "C" void _NN(dump, conf)(nn_def *conf, FILE *fp) {
     if (!conf) return;
-    static const char *tn[] = {"ANN", "LNN", "SNN"};
-    static const char *trn[] = {"BP", "BPM", "CG", "SPLX", "ADAM"};
     _OUT(fp, "# NN configuration (libhpnn-mi355x)\n");
-    _OUT(fp, "[name] %s\n", conf->name ? conf->name : "noname");
-    _OUT(fp, "[type] %s\n", (conf->type >= 0 && conf->type <= 2) ? tn[conf->type] : "UKN");
-    if (conf->need_init || !conf->f_kernel) _OUT(fp, "[init] generate\n");
-    else _OUT(fp, "[init] %s\n", conf->f_kernel);
-    _OUT(fp, "[seed] %u\n", conf->seed);
-    kernel_ann *k = KERN(conf);
-    if (k) {
-        _OUT(fp, "[inputs] %u\n", k->n_inputs);
-        _OUT(fp, "[hiddens]");
-        for (UINT i = 0; i < k->n_hiddens; i++) _OUT(fp, " %u", k->hiddens[i].n_neurons);
-        _OUT(fp, "\n[outputs] %u\n", k->n_outputs);
+    for (const ConfKey &row : CONF_KEYS) {
+        if (row.batched && conf->mode != NN_MODE_BATCHED) continue;
+        if (row.kind == OTHER) {
+            if (row.dump) row.dump(conf, fp);
+        } else if (row.kind == COUNT) {
+            if (field_of<UINT>(conf, row)) _OUT(fp, "[%s] %u\n", row.name, field_of<UINT>(conf, row));
+        } else if (row.kind == REAL) {
+            if (row.set(field_of<DOUBLE>(conf, row))) _OUT(fp, "[%s] %.17g\n", row.name, field_of<DOUBLE>(conf, row));
+        } else {
+            const int value = field_of<int>(conf, row);
+            const char *w = value != row.unset ? word_of(row.words, value) : NULL;
+            if (w) _OUT(fp, "[%s] %s\n", row.name, w);
+        }
     }
-    _OUT(fp, "[train] %s\n", (conf->train >= 0 && conf->train <= 4) ? trn[conf->train] : "UKN");
-    if (conf->samples) _OUT(fp, "[sample_dir] %s\n", conf->samples);
-    if (conf->tests) _OUT(fp, "[test_dir] %s\n", conf->tests);
-    if (conf->mode == NN_MODE_BATCHED) {
-        static const char *dn[] = {"f64", "f32", "bf16"};
-        _OUT(fp, "[mode] batched\n[batch] %u\n[epochs] %u\n[dtype] %s\n", conf->batch, conf->epochs,
-             dn[conf->dtype]);
-        if (conf->parallel == NN_PARALLEL_TP) _OUT(fp, "[parallel] tp\n");
-    }
-    if (conf->shuffle == NN_SHUFFLE_EPOCH) _OUT(fp, "[shuffle] epoch\n");
-    if (conf->validate) _OUT(fp, "[validate] %u\n", conf->validate);
-    if (conf->keep_best) _OUT(fp, "[keep_best] %s\n", conf->keep_best == NN_KEEP_ACC ? "acc" : "loss");
-    if (conf->patience) _OUT(fp, "[patience] %u\n", conf->patience);
-    if (conf->lr > 0) _OUT(fp, "[lr] %.17g\n", conf->lr);
-    if (conf->momentum >= 0) _OUT(fp, "[momentum] %.17g\n", conf->momentum);
-    if (conf->beta1 == conf->beta1) _OUT(fp, "[beta1] %.17g\n", conf->beta1);
-    if (conf->beta2 == conf->beta2) _OUT(fp, "[beta2] %.17g\n", conf->beta2);
-    if (conf->epsilon == conf->epsilon) _OUT(fp, "[epsilon] %.17g\n", conf->epsilon);
-    if (conf->decay == conf->decay) _OUT(fp, "[decay] %.17g\n", conf->decay);
-    static const char *lrn[] = {"constant", "step", "linear", "plateau"};
-    if (conf->lr_schedule >= NN_LR_CONSTANT && conf->lr_schedule <= NN_LR_PLATEAU)
-        _OUT(fp, "[lr_schedule] %s\n", lrn[conf->lr_schedule]);
-    if (conf->lr_gamma == conf->lr_gamma) _OUT(fp, "[lr_gamma] %.17g\n", conf->lr_gamma);
-    if (conf->lr_period) _OUT(fp, "[lr_period] %u\n", conf->lr_period);
-    if (conf->lr_span) _OUT(fp, "[lr_span] %u\n", conf->lr_span);
-    if (conf->lr_end == conf->lr_end) _OUT(fp, "[lr_end] %.17g\n", conf->lr_end);
-    if (conf->lr_min == conf->lr_min) _OUT(fp, "[lr_min] %.17g\n", conf->lr_min);
-    if (conf->lr_patience) _OUT(fp, "[lr_patience] %u\n", conf->lr_patience);
-    if (conf->warmup) _OUT(fp, "[warmup] %u\n", conf->warmup);
-    if (conf->clip > 0.0) _OUT(fp, "[clip] %.17g\n", conf->clip);
 }
 
 /* ------------------------------------------------------------------ */
@@ -673,341 +467,277 @@ static DOUBLE default_alpha(const nn_def *conf) { return conf->momentum >= 0 ? c
 /* ------------------------------------------------------------------ */
 /* training                                                            */
 /* ------------------------------------------------------------------ */
-extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
-    if (!conf || !conf->kernel || !conf->samples || conf->type == NN_TYPE_UKN) return FALSE;
-    kernel_ann *k = KERN(conf);
-    if (conf->train != NN_TRAIN_BP && conf->train != NN_TRAIN_BPM && conf->train != NN_TRAIN_CG &&
-        conf->train != NN_TRAIN_ADAM) {
+/* one metrics event; engine ("gpu" | "cpu") leads its fields, NULL: the event has no engine field */
+__attribute__((format(printf, 3, 4))) static void emit_event(const char *event, const char *engine,
+                                                             const char *fmt, ...) {
+    if (!hpnn_metrics_active()) return;
+    char buf[384];
+    const int n = engine ? snprintf(buf, sizeof buf, "\"engine\": \"%s\", ", engine) : 0;
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf + n, sizeof buf - n, fmt, ap);
+    va_end(ap);
+    hpnn_metrics_emit(event, buf);
+}
+
+static nn_lr_schedule schedule_kind(nn_def *conf) {
+    nn_lr_schedule kind = NN_LR_NONE;
+    _NN(get, lr_schedule)(conf, &kind, NULL, NULL, NULL, NULL, NULL, NULL, NULL);
+    return kind;
+}
+
+#define REFUSE(...)                                                        \
+    do {                                                                   \
+        NN_ERROR(stderr, __VA_ARGS__);                                     \
+        return true;                                                       \
+    } while (0)
+
+/* step 1: what a call is refused for before a sample is read ... */
+static bool refused(nn_def *conf) {
+    const bool batched = conf->mode == NN_MODE_BATCHED, cg = conf->train == NN_TRAIN_CG;
+    if (conf->train != NN_TRAIN_BP && conf->train != NN_TRAIN_BPM && !cg && conf->train != NN_TRAIN_ADAM) {
         NN_ERROR(stdout, "unimplemented training type!\n");
-        return FALSE;
+        return true;
     }
-    if (conf->train == NN_TRAIN_CG) {
-        /* one CG iteration sums over the whole sample set: there is none in online mode */
-        if (conf->mode != NN_MODE_BATCHED) {
-            NN_ERROR(stderr, "[train] CG needs [mode] batched (one iteration per epoch over the whole sample set); "
-                             "online mode trains with BP or BPM\n");
-            return FALSE;
-        }
-        if (conf->dtype == NN_DTYPE_BF16) {
-            NN_ERROR(stderr, "[train] CG: the line search compares losses that the BF16 forward cannot resolve; "
-                             "use [dtype] f32 or f64\n");
-            return FALSE;
-        }
-    }
-    DOUBLE beta1 = 0.0, beta2 = 0.0, epsilon = 0.0, decay = 0.0;
+    /* one CG iteration sums over the whole sample set: there is none in online mode */
+    if (cg && !batched)
+        REFUSE("[train] CG needs [mode] batched (one iteration per epoch over the whole sample set); "
+               "online mode trains with BP or BPM\n");
+    if (cg && conf->dtype == NN_DTYPE_BF16)
+        REFUSE("[train] CG: the line search compares losses that the BF16 forward cannot resolve; "
+               "use [dtype] f32 or f64\n");
     if (conf->train == NN_TRAIN_ADAM) {
         /* the moments are those of a minibatch sequence: there is none in online mode */
-        if (conf->mode != NN_MODE_BATCHED) {
-            NN_ERROR(stderr, "[train] ADAM needs [mode] batched (its moments run over minibatch steps); "
-                             "online mode trains with BP or BPM\n");
-            return FALSE;
-        }
+        if (!batched)
+            REFUSE("[train] ADAM needs [mode] batched (its moments run over minibatch steps); "
+                   "online mode trains with BP or BPM\n");
+        DOUBLE beta1, beta2, epsilon, decay;
         _NN(get, adam)(conf, &beta1, &beta2, &epsilon, &decay);
-        if (!hpnn_adam_valid(0.0, beta1, beta2, epsilon, decay)) {
-            NN_ERROR(stderr, "[train] ADAM: beta1 %g, beta2 %g, epsilon %g, decay %g are out of range "
-                             "(0 <= beta < 1, epsilon > 0, decay >= 0)\n", beta1, beta2, epsilon, decay);
-            return FALSE;
-        }
+        if (!hpnn_adam_valid(0.0, beta1, beta2, epsilon, decay))
+            REFUSE("[train] ADAM: beta1 %g, beta2 %g, epsilon %g, decay %g are out of range "
+                   "(0 <= beta < 1, epsilon > 0, decay >= 0)\n", beta1, beta2, epsilon, decay);
         if (conf->momentum >= 0) NN_OUT(stdout, "[train] ADAM: [momentum] is unused (the moments decay with [beta1], [beta2])\n");
     }
-    /* [lr_schedule]: the keys as a training call uses them; the state itself is filled below, once
-     * the rate and the progress are known */
-    nn_lr_schedule lr_kind = NN_LR_NONE;
-    DOUBLE lr_gamma = 0.0, lr_end = 0.0, lr_min = 0.0;
-    UINT lr_period = 0, lr_span = 0, lr_patience = 0, lr_warmup = 0;
-    _NN(get, lr_schedule)(conf, &lr_kind, &lr_gamma, &lr_period, &lr_span, &lr_end, &lr_min, &lr_patience, &lr_warmup);
-    if (lr_kind != NN_LR_NONE && conf->mode == NN_MODE_BATCHED) {
-        if (conf->train == NN_TRAIN_CG) {
-            NN_ERROR(stderr, "[lr_schedule] is not supported by [train] CG (the line search chooses its own step); "
-                             "use [train] BP, BPM or ADAM\n");
-            return FALSE;
-        }
-        if (lr_kind == NN_LR_PLATEAU && !conf->validate) {
-            NN_ERROR(stderr, "[lr_schedule] plateau needs [validate] N: there is no validation loss to watch\n");
-            return FALSE;
-        }
-    }
+    const nn_lr_schedule kind = schedule_kind(conf);
+    if (kind != NN_LR_NONE && batched && cg)
+        REFUSE("[lr_schedule] is not supported by [train] CG (the line search chooses its own step); "
+               "use [train] BP, BPM or ADAM\n");
+    if (kind == NN_LR_PLATEAU && batched && !conf->validate)
+        REFUSE("[lr_schedule] plateau needs [validate] N: there is no validation loss to watch\n");
     /* [clip]: a finite bound >= 0 (0: off); batched BP / BPM / ADAM on one device or the CPU */
-    if (!hpnn_clip_valid(conf->clip)) {
-        NN_ERROR(stderr, "[clip] %g is out of range (the largest gradient norm, finite and > 0; 0: off)\n", conf->clip);
-        return FALSE;
-    }
-    if (conf->clip > 0.0 && conf->mode == NN_MODE_BATCHED && conf->train == NN_TRAIN_CG) {
-        NN_ERROR(stderr, "[clip] is not supported by [train] CG (the line search chooses its own step); "
-                         "use [train] BP, BPM or ADAM\n");
-        return FALSE;
-    }
-    HpnnTraceRange tr("nn_train_kernel");
-    HpnnSamples src;
-    if (!src.open(conf->samples)) {
-        NN_ERROR(stderr, "can't open sample directory: %s\n", conf->samples);
-        return FALSE;
-    }
-    if (conf->seed == 0) conf->seed = (UINT)time(NULL);
-    const bool gpu = use_gpu(conf);
-    const DOUBLE lr = default_lr(conf, gpu);
-    const DOUBLE alpha = default_alpha(conf);
+    if (!hpnn_clip_valid(conf->clip))
+        REFUSE("[clip] %g is out of range (the largest gradient norm, finite and > 0; 0: off)\n", conf->clip);
+    if (conf->clip > 0.0 && batched && cg)
+        REFUSE("[clip] is not supported by [train] CG (the line search chooses its own step); "
+               "use [train] BP, BPM or ADAM\n");
+    return false;
+}
 
-    if (conf->mode == NN_MODE_BATCHED) {
-        std::vector<UINT> order = seeded_order((UINT)src.size(), conf->seed);
-        std::vector<DOUBLE> X, T;
-        UINT n;
-        {
-            HpnnTraceRange tl("load_samples");
-            n = (UINT)src.load(order, k->n_inputs, k->n_outputs, _NN(return, omp_threads)(), X, T);
-        }
-        if (n == 0) return FALSE;
-        /* [validate] N: the held-out set of [test_dir] (directory or pack file), in name order */
-        std::vector<DOUBLE> Xv, Tv;
-        UINT nv = 0;
-        free(conf->validation);
-        conf->validation = NULL;
-        conf->n_validation = 0;
-        conf->best_epoch = 0;
-        free(conf->cg_history);
-        conf->cg_history = NULL;
-        conf->n_cg_history = 0;
-        free(conf->lr_history);
-        conf->lr_history = NULL;
-        conf->n_lr_history = 0;
-        free(conf->clip_history);
-        conf->clip_history = NULL;
-        conf->n_clip_history = 0;
-        if (conf->keep_best && !conf->validate) {
-            NN_ERROR(stderr, "[keep_best] needs [validate] N: there is no validation pass to keep the best of\n");
-            return FALSE;
-        }
-        if (conf->patience && !conf->keep_best) {
-            NN_ERROR(stderr, "[patience] needs [keep_best] loss | acc: the metric that has to improve\n");
-            return FALSE;
-        }
-        if (conf->validate) {
-            HpnnSamples vsrc;
-            if (!conf->tests || !vsrc.open(conf->tests)) {
-                NN_ERROR(stderr, "[validate] needs a [test_dir] that can be opened: %s\n",
-                         conf->tests ? conf->tests : "(not set)");
-                return FALSE;
-            }
-            std::vector<UINT> vorder(vsrc.size());
-            for (UINT i = 0; i < (UINT)vorder.size(); i++) vorder[i] = i;
-            HpnnTraceRange tl("load_validation_samples");
-            nv = (UINT)vsrc.load(vorder, k->n_inputs, k->n_outputs, _NN(return, omp_threads)(), Xv, Tv);
-            if (nv == 0) {
-                NN_ERROR(stderr, "[validate]: no usable sample in [test_dir] %s\n", conf->tests);
-                return FALSE;
-            }
-        }
-        hpnn_batched_opts o;
-        memset(&o, 0, sizeof(o));
-        o.type = conf->type;
-        o.train = conf->train;
-        o.dtype = conf->dtype;
-        o.batch = conf->batch;
-        o.epochs = conf->epochs;
-        o.lr = lr;
-        o.alpha = conf->train == NN_TRAIN_BPM ? alpha : 0.0;
-        o.seed = conf->seed;
-        o.resume = conf->resume && k->dw != NULL;
-        o.beta1 = beta1;
-        o.beta2 = beta2;
-        o.eps = epsilon;
-        o.decay = decay;
-        o.epoch0 = conf->epochs_done;
-        o.shuffle = conf->shuffle == NN_SHUFFLE_EPOCH ? 1 : 0;
-        o.validate = conf->validate;
-        o.Xv = nv ? Xv.data() : NULL;
-        o.Tv = nv ? Tv.data() : NULL;
-        o.nv = nv;
-        o.keep_best = (UINT)conf->keep_best;
-        o.patience = conf->patience;
-        if (lr_kind != NN_LR_NONE) {
-            o.sched = 1;
-            hpnn_lr_state_init(&o.lrs, (unsigned int)lr_kind, lr, lr_gamma, lr_period, lr_span, lr_end, lr_min,
-                               lr_patience, lr_warmup, conf->epochs_done);
-            if (!hpnn_lr_valid(&o.lrs)) {
-                NN_ERROR(stderr, "[lr_schedule]: needs finite [lr] and [lr_end], 0 < [lr_gamma] <= 1, [lr_period] >= 1, "
-                                 "[lr_min] >= 0, [lr_span] >= 1 for linear and [lr_patience] >= 1 for plateau\n");
-                return FALSE;
-            }
-            /* plateau continues from the running fields a state file left in the kernel */
-            if (lr_kind == NN_LR_PLATEAU && k->lr_loaded) {
-                o.lrs.scale = k->lr_scale;
-                o.lrs.best = k->lr_best;
-                o.lrs.stale = k->lr_stale;
-                o.lrs.cuts = k->lr_cuts;
-                o.lrs.valid = k->lr_valid;
-            }
-            static const char *lrn[] = {"constant", "step", "linear", "plateau"};
-            NN_OUT(stdout, "batched %s training: learning rate schedule %s, lr %g gamma %g period %u span %u end %g "
-                           "min %g patience %u warmup %u\n", gpu ? "GPU" : "CPU", lrn[lr_kind], lr, lr_gamma,
-                   lr_period, lr_span, lr_end, lr_min, lr_patience, lr_warmup);
-        }
-        o.clip = conf->clip;
-        if (o.clip > 0.0)
-            NN_OUT(stdout, "batched %s training: gradient clipping: max norm %g\n", gpu ? "GPU" : "CPU", o.clip);
-        k->lr_loaded = 0;
-        UINT ng = 1;
-        _NN(get, n_gpu)(&ng);
-        o.n_gpu = ng ? ng : 1;
-        {
-            const char *pe = getenv("HPNN_PARALLEL");
-            o.tp = (pe ? (pe[0] == 't' || pe[0] == 'T') : conf->parallel == NN_PARALLEL_TP) ? 1 : 0;
-        }
-        hpnn_batched_stats st;
-        memset(&st, 0, sizeof(st));
-        BOOL ok;
-        {
-            HpnnTraceRange tb(gpu ? "train_batched_gpu" : "train_batched_cpu");
-            ok = gpu ? hpnn_gpu_train_batched(k, X.data(), T.data(), n, &o, &st)
-                     : hpnn_cpu_train_batched(k, X.data(), T.data(), n, &o, &st);
-        }
-        if (ok && conf->keep_best && st.best_epoch) {
-            /* the kernel is the one of the best pass's epoch: the progress is that epoch's too */
-            conf->samples_seen += (UINT64)n * (st.best_epoch - conf->epochs_done);
-            conf->epochs_done = st.best_epoch;
-        } else if (ok && conf->keep_best) {
-            NN_WARN(stderr, "[keep_best]: no validation pass could be taken (every loss a NaN); "
-                            "the weights after the last epoch run are returned\n");
-            conf->epochs_done += st.epochs_run;
-            conf->samples_seen += (UINT64)n * st.epochs_run;
-        } else if (ok) {
-            conf->epochs_done += conf->epochs;
-            conf->samples_seen += st.samples;
-        }
-        NN_OUT(stdout, "BATCHED TRAINING: %llu samples in %.6f s (%.1f samples/s) loss=%.10f acc=%u/%u\n",
-               (unsigned long long)st.samples, st.seconds, st.seconds > 0 ? st.samples / st.seconds : 0.0,
-               st.epoch_loss, st.correct, n);
-        for (UINT i = 0; ok && i < st.n_cg; i++) {
-            const hpnn_cg_record &r = st.cg[i];
-            NN_OUT(stdout, "CG: epoch %u loss=%.10f beta=%.10g alpha=%.10g trial=%d%s\n", o.epoch0 + i + 1, r.f0, r.beta,
-                   r.alpha, r.trial == HPNN_CG_NONE ? -1 : (int)r.trial, (r.flags & HPNN_CG_FAILED) ? " FAILED" : "");
-            if (hpnn_metrics_active()) {
-                char buf[384];
-                snprintf(buf, sizeof buf,
-                         "\"engine\": \"%s\", \"epoch\": %u, \"f0\": %.17g, \"f1\": %.17g, \"beta\": %.17g, "
-                         "\"alpha\": %.17g, \"trial\": %d, \"flags\": %u",
-                         gpu ? "gpu" : "cpu", o.epoch0 + i + 1, r.f0, r.f1, r.beta, r.alpha,
-                         r.trial == HPNN_CG_NONE ? -1 : (int)r.trial, r.flags);
-                hpnn_metrics_emit("cg", buf);
-            }
-        }
-        for (UINT i = 0; ok && i < st.n_lr; i++) {
-            NN_OUT(stdout, "LR: epoch %u lr=%.17g\n", o.epoch0 + i + 1, st.lr_hist[i]);
-            if (hpnn_metrics_active()) {
-                char buf[128];
-                snprintf(buf, sizeof buf, "\"engine\": \"%s\", \"epoch\": %u, \"lr\": %.17g", gpu ? "gpu" : "cpu",
-                         o.epoch0 + i + 1, st.lr_hist[i]);
-                hpnn_metrics_emit("lr", buf);
-            }
-        }
-        for (UINT i = 0; ok && i < st.n_clip; i++) {
-            const hpnn_clip_record &r = st.clip_hist[i];
-            NN_OUT(stdout, "CLIP: epoch %u steps=%u clipped=%u max_norm=%.17g last_norm=%.17g\n", o.epoch0 + i + 1,
-                   r.steps, r.clipped, r.norm_max, r.norm_last);
-            if (hpnn_metrics_active()) {
-                char buf[256];
-                snprintf(buf, sizeof buf,
-                         "\"engine\": \"%s\", \"epoch\": %u, \"steps\": %u, \"clipped\": %u, \"max_norm\": %.17g, "
-                         "\"last_norm\": %.17g",
-                         gpu ? "gpu" : "cpu", o.epoch0 + i + 1, r.steps, r.clipped, r.norm_max, r.norm_last);
-                hpnn_metrics_emit("clip", buf);
-            }
-        }
-        if (ok && o.sched) {
-            /* the schedule state of the returned kernel: nn_dump_state saves plateau's */
-            k->lr_scale = st.lrs.scale;
-            k->lr_best = st.lrs.best;
-            k->lr_stale = st.lrs.stale;
-            k->lr_cuts = st.lrs.cuts;
-            k->lr_valid = st.lrs.valid;
-        }
-        for (UINT i = 0; ok && i < st.n_val; i++)
-            NN_OUT(stdout, "VALIDATION: epoch %u loss=%.10f acc=%u/%u\n", st.val[i].epoch, st.val[i].loss,
-                   st.val[i].correct, st.val[i].n);
-        if (ok && conf->keep_best && st.best_epoch && st.best_index < st.n_val) {
-            const hpnn_validation_record &b = st.val[st.best_index];
-            conf->best_epoch = b.epoch;
-            conf->best_loss = b.loss;
-            conf->best_correct = b.correct;
-            conf->best_n = b.n;
-            NN_OUT(stdout, "BEST: epoch %u loss=%.10f acc=%u/%u\n", b.epoch, b.loss, b.correct, b.n);
-            if (hpnn_metrics_active()) {
-                char buf[256];
-                snprintf(buf, sizeof buf,
-                         "\"engine\": \"%s\", \"epoch\": %u, \"loss\": %.17g, \"correct\": %u, \"n\": %u, "
-                         "\"metric\": \"%s\"",
-                         gpu ? "gpu" : "cpu", b.epoch, b.loss, b.correct, b.n,
-                         conf->keep_best == NN_KEEP_ACC ? "acc" : "loss");
-                hpnn_metrics_emit("best", buf);
-            }
-        }
-        if (ok && st.stop_epoch) {
-            NN_OUT(stdout, "EARLY STOP: epoch %u (no improvement in %u passes)\n", st.stop_epoch, conf->patience);
-            if (hpnn_metrics_active()) {
-                char buf[128];
-                snprintf(buf, sizeof buf, "\"engine\": \"%s\", \"epoch\": %u, \"patience\": %u", gpu ? "gpu" : "cpu",
-                         st.stop_epoch, conf->patience);
-                hpnn_metrics_emit("early_stop", buf);
-            }
-        }
-        if (ok) {
-            conf->validation = st.val;
-            conf->n_validation = st.n_val;
-            conf->cg_history = st.cg;
-            conf->n_cg_history = st.n_cg;
-            conf->lr_history = st.lr_hist;
-            conf->n_lr_history = st.n_lr;
-            conf->clip_history = st.clip_hist;
-            conf->n_clip_history = st.n_clip;
-        } else {
-            free(st.val);
-            free(st.cg);
-            free(st.lr_hist);
-            free(st.clip_hist);
-        }
-        if (hpnn_metrics_active()) {
-            char buf[384];
-            snprintf(buf, sizeof buf,
-                     "\"engine\": \"%s\", \"ok\": %s, \"samples\": %llu, \"seconds\": %.6f, \"samples_per_s\": %.3f, "
-                     "\"loss\": %.10g, \"correct\": %u, \"n\": %u, \"epochs_done\": %u",
-                     gpu ? "gpu" : "cpu", ok ? "true" : "false", (unsigned long long)st.samples, st.seconds,
-                     st.seconds > 0 ? st.samples / st.seconds : 0.0, st.epoch_loss, st.correct, n, conf->epochs_done);
-            hpnn_metrics_emit("train_batched", buf);
-        }
-        return ok;
-    }
+/* ... and, in batched mode, once the training samples are loaded; [validate] N: the held-out set of
+ * [test_dir] (directory or pack file), in name order */
+static bool refused_validation(const nn_def *conf, const kernel_ann *k, std::vector<DOUBLE> &Xv,
+                               std::vector<DOUBLE> &Tv, UINT &nv) {
+    if (conf->keep_best && !conf->validate)
+        REFUSE("[keep_best] needs [validate] N: there is no validation pass to keep the best of\n");
+    if (conf->patience && !conf->keep_best)
+        REFUSE("[patience] needs [keep_best] loss | acc: the metric that has to improve\n");
+    if (!conf->validate) return false;
+    HpnnSamples vsrc;
+    if (!conf->tests || !vsrc.open(conf->tests))
+        REFUSE("[validate] needs a [test_dir] that can be opened: %s\n", conf->tests ? conf->tests : "(not set)");
+    std::vector<UINT> vorder(vsrc.size());
+    for (UINT i = 0; i < (UINT)vorder.size(); i++) vorder[i] = i;
+    HpnnTraceRange tl("load_validation_samples");
+    nv = (UINT)vsrc.load(vorder, k->n_inputs, k->n_outputs, _NN(return, omp_threads)(), Xv, Tv);
+    if (nv == 0) REFUSE("[validate]: no usable sample in [test_dir] %s\n", conf->tests);
+    return false;
+}
 
-    /* online (reference) mode */
-    if (conf->validate) {
-        static bool warned_v = false; /* no epochs here to validate between */
-        if (!warned_v) NN_WARN(stderr, "[validate] has no effect in online mode (ignored)\n");
-        warned_v = true;
+/* step 2: the engine's options from the conf, the schedule state and its announcement included;
+ * false: the schedule keys do not make a schedule */
+static bool batched_opts(nn_def *conf, kernel_ann *k, bool gpu, DOUBLE lr, DOUBLE alpha, hpnn_batched_opts &o) {
+    memset(&o, 0, sizeof(o));
+    o.type = conf->type;
+    o.train = conf->train;
+    o.dtype = conf->dtype;
+    o.batch = conf->batch;
+    o.epochs = conf->epochs;
+    o.lr = lr;
+    o.alpha = conf->train == NN_TRAIN_BPM ? alpha : 0.0;
+    o.seed = conf->seed;
+    o.resume = conf->resume && k->dw != NULL;
+    if (conf->train == NN_TRAIN_ADAM) _NN(get, adam)(conf, &o.beta1, &o.beta2, &o.eps, &o.decay);
+    o.epoch0 = conf->epochs_done;
+    o.shuffle = conf->shuffle == NN_SHUFFLE_EPOCH ? 1 : 0;
+    o.validate = conf->validate;
+    o.keep_best = (UINT)conf->keep_best;
+    o.patience = conf->patience;
+    nn_lr_schedule kind;
+    DOUBLE gamma, lr_end, lr_min;
+    UINT period, span, patience, warmup;
+    _NN(get, lr_schedule)(conf, &kind, &gamma, &period, &span, &lr_end, &lr_min, &patience, &warmup);
+    if (kind != NN_LR_NONE) {
+        o.sched = 1;
+        hpnn_lr_state_init(&o.lrs, (unsigned int)kind, lr, gamma, period, span, lr_end, lr_min, patience, warmup,
+                           conf->epochs_done);
+        if (!hpnn_lr_valid(&o.lrs)) {
+            NN_ERROR(stderr, "[lr_schedule]: needs finite [lr] and [lr_end], 0 < [lr_gamma] <= 1, [lr_period] >= 1, "
+                             "[lr_min] >= 0, [lr_span] >= 1 for linear and [lr_patience] >= 1 for plateau\n");
+            return false;
+        }
+        /* plateau continues from the running fields a state file left in the kernel */
+        if (kind == NN_LR_PLATEAU && k->lr_loaded) hpnn_lr_running_get(k, &o.lrs);
+        NN_OUT(stdout, "batched %s training: learning rate schedule %s, lr %g gamma %g period %u span %u end %g "
+                       "min %g patience %u warmup %u\n", gpu ? "GPU" : "CPU", word_of(LR_WORDS, kind), lr, gamma, period,
+               span, lr_end, lr_min, patience, warmup);
     }
-    if (conf->keep_best) {
-        static bool warned_k = false; /* no validation pass here */
-        if (!warned_k) NN_WARN(stderr, "[keep_best] has no effect in online mode (ignored)\n");
-        warned_k = true;
+    o.clip = conf->clip;
+    if (o.clip > 0.0)
+        NN_OUT(stdout, "batched %s training: gradient clipping: max norm %g\n", gpu ? "GPU" : "CPU", o.clip);
+    k->lr_loaded = 0;
+    UINT ng = 1;
+    _NN(get, n_gpu)(&ng);
+    o.n_gpu = ng ? ng : 1;
+    const char *pe = getenv("HPNN_PARALLEL");
+    o.tp = (pe ? (pe[0] == 't' || pe[0] == 'T') : conf->parallel == NN_PARALLEL_TP) ? 1 : 0;
+    return true;
+}
+#undef REFUSE
+
+/* [keep_best]: the record of the best pass, NULL when none was taken */
+static const hpnn_validation_record *best_record(const nn_def *conf, const hpnn_batched_stats &st) {
+    return conf->keep_best && st.best_epoch && st.best_index < st.n_val ? &st.val[st.best_index] : NULL;
+}
+
+/* step 3: the progress of the returned kernel after a call that went well */
+static void book_progress(nn_def *conf, const hpnn_batched_stats &st, UINT n) {
+    if (conf->keep_best && st.best_epoch) {
+        /* the kernel is the one of the best pass's epoch: the progress is that epoch's too */
+        conf->samples_seen += (UINT64)n * (st.best_epoch - conf->epochs_done);
+        conf->epochs_done = st.best_epoch;
+    } else if (conf->keep_best) {
+        NN_WARN(stderr, "[keep_best]: no validation pass could be taken (every loss a NaN); "
+                        "the weights after the last epoch run are returned\n");
+        conf->epochs_done += st.epochs_run;
+        conf->samples_seen += (UINT64)n * st.epochs_run;
+    } else {
+        conf->epochs_done += conf->epochs;
+        conf->samples_seen += st.samples;
     }
-    if (conf->patience) {
-        static bool warned_p = false;
-        if (!warned_p) NN_WARN(stderr, "[patience] has no effect in online mode (ignored)\n");
-        warned_p = true;
+    if (const hpnn_validation_record *b = best_record(conf, st)) {
+        conf->best_epoch = b->epoch;
+        conf->best_loss = b->loss;
+        conf->best_correct = b->correct;
+        conf->best_n = b->n;
     }
-    if (lr_kind != NN_LR_NONE) {
-        static bool warned_l = false; /* no epochs here to change the rate between */
-        if (!warned_l) NN_WARN(stderr, "[lr_schedule] has no effect in online mode (ignored)\n");
-        warned_l = true;
+}
+
+/* step 4: the report of a call that went well: one function per kind of record writes its stdout
+ * line and its metrics event (the engines emit the "validation" events themselves) */
+static void report_cg(const char *engine, UINT epoch, const hpnn_cg_record &r) {
+    const int trial = r.trial == HPNN_CG_NONE ? -1 : (int)r.trial;
+    NN_OUT(stdout, "CG: epoch %u loss=%.10f beta=%.10g alpha=%.10g trial=%d%s\n", epoch, r.f0, r.beta, r.alpha, trial,
+           (r.flags & HPNN_CG_FAILED) ? " FAILED" : "");
+    emit_event("cg", engine, "\"epoch\": %u, \"f0\": %.17g, \"f1\": %.17g, \"beta\": %.17g, \"alpha\": %.17g, "
+               "\"trial\": %d, \"flags\": %u", epoch, r.f0, r.f1, r.beta, r.alpha, trial, r.flags);
+}
+static void report_lr(const char *engine, UINT epoch, DOUBLE lr) {
+    NN_OUT(stdout, "LR: epoch %u lr=%.17g\n", epoch, lr);
+    emit_event("lr", engine, "\"epoch\": %u, \"lr\": %.17g", epoch, lr);
+}
+static void report_clip(const char *engine, UINT epoch, const hpnn_clip_record &r) {
+    NN_OUT(stdout, "CLIP: epoch %u steps=%u clipped=%u max_norm=%.17g last_norm=%.17g\n", epoch, r.steps, r.clipped,
+           r.norm_max, r.norm_last);
+    emit_event("clip", engine, "\"epoch\": %u, \"steps\": %u, \"clipped\": %u, \"max_norm\": %.17g, \"last_norm\": %.17g",
+               epoch, r.steps, r.clipped, r.norm_max, r.norm_last);
+}
+static void report_validation(const hpnn_validation_record &r) {
+    NN_OUT(stdout, "VALIDATION: epoch %u loss=%.10f acc=%u/%u\n", r.epoch, r.loss, r.correct, r.n);
+}
+static void report_best(const char *engine, const hpnn_validation_record &b, nn_keep_best metric) {
+    NN_OUT(stdout, "BEST: epoch %u loss=%.10f acc=%u/%u\n", b.epoch, b.loss, b.correct, b.n);
+    emit_event("best", engine, "\"epoch\": %u, \"loss\": %.17g, \"correct\": %u, \"n\": %u, \"metric\": \"%s\"", b.epoch,
+               b.loss, b.correct, b.n, word_of(KEEP_WORDS, metric));
+}
+static void report_early_stop(const char *engine, UINT epoch, UINT patience) {
+    NN_OUT(stdout, "EARLY STOP: epoch %u (no improvement in %u passes)\n", epoch, patience);
+    emit_event("early_stop", engine, "\"epoch\": %u, \"patience\": %u", epoch, patience);
+}
+static void report_batched(const nn_def *conf, const hpnn_batched_stats &st, const char *engine, UINT epoch0) {
+    for (UINT i = 0; i < st.n_cg; i++) report_cg(engine, epoch0 + i + 1, st.cg[i]);
+    for (UINT i = 0; i < st.n_lr; i++) report_lr(engine, epoch0 + i + 1, st.lr_hist[i]);
+    for (UINT i = 0; i < st.n_clip; i++) report_clip(engine, epoch0 + i + 1, st.clip_hist[i]);
+    for (UINT i = 0; i < st.n_val; i++) report_validation(st.val[i]);
+    if (const hpnn_validation_record *b = best_record(conf, st)) report_best(engine, *b, conf->keep_best);
+    if (st.stop_epoch) report_early_stop(engine, st.stop_epoch, conf->patience);
+}
+
+static BOOL train_batched(nn_def *conf, HpnnSamples &src, bool gpu, DOUBLE lr, DOUBLE alpha) {
+    kernel_ann *k = KERN(conf);
+    const char *engine = gpu ? "gpu" : "cpu";
+    std::vector<UINT> order = seeded_order((UINT)src.size(), conf->seed);
+    std::vector<DOUBLE> X, T, Xv, Tv;
+    UINT n, nv = 0;
+    {
+        HpnnTraceRange tl("load_samples");
+        n = (UINT)src.load(order, k->n_inputs, k->n_outputs, _NN(return, omp_threads)(), X, T);
     }
-    if (conf->clip > 0.0) {
-        static bool warned_c = false; /* no minibatch gradient here whose norm could be bounded */
-        if (!warned_c) NN_WARN(stderr, "[clip] has no effect in online mode (ignored)\n");
-        warned_c = true;
+    if (n == 0) return FALSE;
+    drop_histories(conf);
+    conf->best_epoch = 0;
+    hpnn_batched_opts o;
+    if (refused_validation(conf, k, Xv, Tv, nv) || !batched_opts(conf, k, gpu, lr, alpha, o)) return FALSE;
+    o.Xv = nv ? Xv.data() : NULL;
+    o.Tv = nv ? Tv.data() : NULL;
+    o.nv = nv;
+    hpnn_batched_stats st;
+    memset(&st, 0, sizeof(st));
+    BOOL ok;
+    {
+        HpnnTraceRange tb(gpu ? "train_batched_gpu" : "train_batched_cpu");
+        ok = gpu ? hpnn_gpu_train_batched(k, X.data(), T.data(), n, &o, &st)
+                 : hpnn_cpu_train_batched(k, X.data(), T.data(), n, &o, &st);
     }
-    if (conf->shuffle == NN_SHUFFLE_EPOCH) {
-        static bool warned = false; /* no epochs here: every sample is trained to convergence once */
-        if (!warned) NN_WARN(stderr, "[shuffle] epoch has no effect in online mode (ignored)\n");
-        warned = true;
+    adopt_histories(conf, &st);
+    if (!ok) drop_histories(conf); /* a failed call leaves none; st's arrays are gone with them */
+    if (ok) book_progress(conf, st, n);
+    /* the schedule state of the returned kernel: nn_dump_state saves plateau's */
+    if (ok && o.sched) hpnn_lr_running_put(k, &st.lrs);
+    NN_OUT(stdout, "BATCHED TRAINING: %llu samples in %.6f s (%.1f samples/s) loss=%.10f acc=%u/%u\n",
+           (unsigned long long)st.samples, st.seconds, st.seconds > 0 ? st.samples / st.seconds : 0.0, st.epoch_loss,
+           st.correct, n);
+    if (ok) report_batched(conf, st, engine, o.epoch0);
+    emit_event("train_batched", engine, "\"ok\": %s, \"samples\": %llu, \"seconds\": %.6f, \"samples_per_s\": %.3f, "
+               "\"loss\": %.10g, \"correct\": %u, \"n\": %u, \"epochs_done\": %u", ok ? "true" : "false",
+               (unsigned long long)st.samples, st.seconds, st.seconds > 0 ? st.samples / st.seconds : 0.0, st.epoch_loss,
+               st.correct, n, conf->epochs_done);
+    return ok;
+}
+
+/* the keys of batched training mean nothing in online (reference) mode: no epochs to validate,
+ * reshuffle or change the rate between, no minibatch gradient whose norm could be bounded.  Each
+ * is said once per process. */
+static void warn_ignored_online(nn_def *conf) {
+    const struct {
+        bool set;
+        const char *key;
+    } ignored[] = {{conf->validate != 0, "[validate]"},
+                   {conf->keep_best != NN_KEEP_OFF, "[keep_best]"},
+                   {conf->patience != 0, "[patience]"},
+                   {schedule_kind(conf) != NN_LR_NONE, "[lr_schedule]"},
+                   {conf->clip > 0.0, "[clip]"},
+                   {conf->shuffle == NN_SHUFFLE_EPOCH, "[shuffle] epoch"}};
+    static bool warned[sizeof ignored / sizeof ignored[0]];
+    for (size_t i = 0; i < sizeof ignored / sizeof ignored[0]; i++) {
+        if (!ignored[i].set) continue;
+        if (!warned[i]) NN_WARN(stderr, "%s has no effect in online mode (ignored)\n", ignored[i].key);
+        warned[i] = true;
     }
+}
+
+static BOOL train_online(nn_def *conf, HpnnSamples &src, bool gpu, DOUBLE lr, DOUBLE alpha) {
+    kernel_ann *k = KERN(conf);
+    warn_ignored_online(conf);
     std::vector<UINT> order = seeded_order((UINT)src.size(), conf->seed);
     UINT n_ok = 0, n_done = 0;
     for (UINT idx : order) {
@@ -1030,14 +760,9 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
         NN_COUT(stdout, ok ? " SUCCESS!\n" : " FAIL!\n");
         fflush(stdout);
         if (r > 0.1) NN_DBG(stdout, "bad optimization!\n");
-        if (hpnn_metrics_active()) {
-            char buf[384];
-            snprintf(buf, sizeof buf,
-                     "\"file\": \"%s\", \"init\": %.10g, \"first_ok\": %s, \"n_iter\": %u, \"final\": %.10g, "
-                     "\"success\": %s",
-                     f.c_str(), e0, first ? "true" : "false", it, r, ok ? "true" : "false");
-            hpnn_metrics_emit("train_sample", buf);
-        }
+        emit_event("train_sample", NULL, "\"file\": \"%s\", \"init\": %.10g, \"first_ok\": %s, \"n_iter\": %u, "
+                   "\"final\": %.10g, \"success\": %s", f.c_str(), e0, first ? "true" : "false", it, r,
+                   ok ? "true" : "false");
         n_ok += ok ? 1 : 0;
         n_done++;
         conf->samples_seen++;
@@ -1049,12 +774,24 @@ extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
         }
     }
     if (gpu) hpnn_gpu_sync_host(k);
-    if (hpnn_metrics_active()) {
-        char buf[128];
-        snprintf(buf, sizeof buf, "\"samples\": %u, \"success\": %u", n_done, n_ok);
-        hpnn_metrics_emit("train_online", buf);
-    }
+    emit_event("train_online", NULL, "\"samples\": %u, \"success\": %u", n_done, n_ok);
     return TRUE;
+}
+
+extern "C" BOOL _NN(train, kernel)(nn_def *conf) {
+    if (!conf || !conf->kernel || !conf->samples || conf->type == NN_TYPE_UKN) return FALSE;
+    if (refused(conf)) return FALSE;
+    HpnnTraceRange tr("nn_train_kernel");
+    HpnnSamples src;
+    if (!src.open(conf->samples)) {
+        NN_ERROR(stderr, "can't open sample directory: %s\n", conf->samples);
+        return FALSE;
+    }
+    if (conf->seed == 0) conf->seed = (UINT)time(NULL);
+    const bool gpu = use_gpu(conf);
+    const DOUBLE lr = default_lr(conf, gpu), alpha = default_alpha(conf);
+    return conf->mode == NN_MODE_BATCHED ? train_batched(conf, src, gpu, lr, alpha)
+                                         : train_online(conf, src, gpu, lr, alpha);
 }
 
 /* ------------------------------------------------------------------ */
@@ -1161,10 +898,6 @@ extern "C" void _NN(run, kernel)(nn_def *conf) {
             free(out);
         }
     }
-    if (hpnn_metrics_active()) {
-        char buf[128];
-        snprintf(buf, sizeof buf, "\"pass\": %u, \"total\": %u, \"accuracy\": %.6f", g_last_pass, g_last_total,
-                 g_last_total ? (double)g_last_pass / g_last_total : 0.0);
-        hpnn_metrics_emit("run", buf);
-    }
+    emit_event("run", NULL, "\"pass\": %u, \"total\": %u, \"accuracy\": %.6f", g_last_pass, g_last_total,
+               g_last_total ? (double)g_last_pass / g_last_total : 0.0);
 }

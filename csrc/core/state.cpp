@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "dataset.h"
+#include "lr_running.h"
 #include "runtime_internal.h"
 #include "../gpu/engine.h"
 
@@ -207,12 +208,16 @@ extern "C" BOOL _NN(load, state)(nn_def *conf, const CHAR *filename) {
         r.get(&ap1, 8);
         r.get(&ap2, 8);
     }
-    DOUBLE ls = 1.0, lb = 0.0;
-    UINT lw[4] = {0, 0, 0, 0};
+    hpnn_lr_state fresh, filed; /* the running fields: scale 1, nothing judged; and the file's */
+    hpnn_lr_state_init(&fresh, HPNN_LR_PLATEAU, 0.0, 0.0, 0, 0, 0.0, 0.0, 0, 0, 0);
+    filed = fresh;
     if (has_sched) {
-        r.get(&ls, 8);
-        r.get(&lb, 8);
-        for (UINT &x : lw) x = r.u32();
+        r.get(&filed.scale, 8);
+        r.get(&filed.best, 8);
+        filed.stale = r.u32();
+        filed.cuts = r.u32();
+        filed.valid = r.u32();
+        r.u32();
     }
     if (!r.ok || r.off != buf.size() - 8) {
         NN_ERROR(stderr, "state file %s: bad size\n", filename);
@@ -246,11 +251,7 @@ extern "C" BOOL _NN(load, state)(nn_def *conf, const CHAR *filename) {
         NN_WARN(stderr, "state file %s holds a plateau schedule but [lr_schedule] is not plateau: it is ignored\n",
                 filename);
     k->lr_loaded = has_sched && want_sched ? 1u : 0u;
-    k->lr_scale = k->lr_loaded ? ls : 1.0;
-    k->lr_best = k->lr_loaded ? lb : 0.0;
-    k->lr_stale = k->lr_loaded ? lw[0] : 0u;
-    k->lr_cuts = k->lr_loaded ? lw[1] : 0u;
-    k->lr_valid = k->lr_loaded ? lw[2] : 0u;
+    hpnn_lr_running_put(k, k->lr_loaded ? &filed : &fresh);
     hpnn_gpu_mark_host_dirty(k);
     conf->seed = seed;
     conf->epochs_done = epochs;

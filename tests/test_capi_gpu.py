@@ -294,3 +294,24 @@ def test_run_nn_sharded_evaluation_matches(tmp_path, dtype):
     lines = lambda out: [x for x in out.splitlines() if "BEST CLASS" in x or re.match(r"^\s*\d+ \|", x)]  # noqa
     assert sum("BEST CLASS" in x for x in lines(one)) == 301
     assert lines(one) == lines(three) == lines(streams)
+
+
+def test_batched_gpu_report_matches_record(tmp_path):
+    """The report of one batched call on the GPU engine (BPM, [dtype] f32, -V 1 -K loss -P 1
+    -L plateau -C 0.5 on the 6-5-4-3 net of capi_record_common) against capi_record_gpu.json, which
+    the commit before the stepwise nn_train_kernel wrote.  Every floating-point field is masked (the
+    engines add their loss slots with atomics); compared are the kinds of line and their order, the
+    epoch numbers and integer fields, and of the metrics file the event names, the field names and
+    their order, the integers and "engine": "gpu"."""
+    import json
+    from tests import capi_record_common as crc
+    with open(crc.RECORD_GPU) as f:
+        want = json.load(f)
+    got = crc.run_gpu_bpm(str(tmp_path))
+    assert got["rc"] == want["rc"] == 0, got["stderr"]
+    assert got["stderr"] == want["stderr"]
+    assert got["stdout"].splitlines() == want["stdout"].splitlines()
+    assert got["metrics"] == want["metrics"]
+    engines = [dict(e).get("engine") for e in got["metrics"]]
+    # 4 epochs x (epoch, validation, lr, clip) + best + train_batched
+    assert len(engines) == 18 and set(engines) == {"gpu"}
