@@ -38,6 +38,7 @@
 
 #include "conf_keys.h"
 #include "dataset.h"
+#include "export_records.h"
 #include "lr_running.h"
 #include "runtime_internal.h"
 #include "../gpu/engine.h"
@@ -77,11 +78,21 @@ static void drop(T *&array, UINT &count) {
     count = 0;
 }
 
+/* [confusion]: what the last nn_train_kernel or nn_run_kernel call tallied */
+static void drop_confusion(nn_def *conf) {
+    UINT cells = 0;
+    drop(conf->class_history, conf->n_class_history);
+    drop(conf->confusion_last, cells);
+    drop(conf->confusion_best, cells);
+    conf->n_classes = conf->confusion_launches = 0;
+}
+
 static void drop_histories(nn_def *conf) {
     drop(conf->validation, conf->n_validation);
     drop(conf->cg_history, conf->n_cg_history);
     drop(conf->lr_history, conf->n_lr_history);
     drop(conf->clip_history, conf->n_clip_history);
+    drop_confusion(conf);
 }
 
 static void adopt_histories(nn_def *conf, const hpnn_batched_stats *st) {
@@ -94,6 +105,12 @@ static void adopt_histories(nn_def *conf, const hpnn_batched_stats *st) {
     conf->n_lr_history = st->n_lr;
     conf->clip_history = st->clip_hist;
     conf->n_clip_history = st->n_clip;
+    conf->n_classes = st->n_classes;
+    conf->class_history = st->class_hist;
+    conf->n_class_history = st->n_class_hist;
+    conf->confusion_last = st->confusion_last;
+    conf->confusion_best = st->confusion_best;
+    conf->confusion_launches = st->confusion_launches;
 }
 
 extern "C" void _NN(free, kernel)(nn_def *conf) {
@@ -237,6 +254,41 @@ extern "C" DOUBLE _NN(get, clip)(nn_def *c) { return c ? c->clip : 0.0; }
 extern "C" const nn_clip_record *_NN(get, clip_history)(nn_def *c, UINT *n) {
     if (n) *n = c && c->clip_history ? c->n_clip_history : 0;
     return c ? (const nn_clip_record *)c->clip_history : NULL;
+}
+extern "C" void _NN(set, confusion)(nn_def *c, BOOL on) {
+    if (c) c->confusion = on ? 1 : 0;
+}
+extern "C" void _NN(get, confusion)(nn_def *c, BOOL *on) {
+    if (c && on) *on = c->confusion ? TRUE : FALSE;
+}
+extern "C" BOOL _NN(return, confusion)(nn_def *c) { return c && c->confusion ? TRUE : FALSE; }
+extern "C" UINT _NN(get, confusion_matrix)(nn_def *c, int which, UINT max_cells, UINT *cells) {
+    if (!c || !c->n_classes || (which != NN_CONFUSION_LAST && which != NN_CONFUSION_BEST)) return 0;
+    const UINT *m = which == NN_CONFUSION_BEST ? c->confusion_best : c->confusion_last;
+    if (!m) return 0;
+    const unsigned long long all = hpnn_confusion_cells(c->n_classes);
+    if (cells) memcpy(cells, m, sizeof(UINT) * (size_t)(all < max_cells ? all : max_cells));
+    return c->n_classes;
+}
+extern "C" UINT _NN(get, class_history)(nn_def *c, UINT pass, UINT *support, UINT *hit, UINT *predicted) {
+    if (!c || !c->class_history || pass >= c->n_class_history) return 0;
+    const UINT n = c->n_classes, *r = c->class_history + (size_t)pass * 3 * n;
+    if (support) memcpy(support, r, sizeof(UINT) * n);
+    if (hit) memcpy(hit, r + n, sizeof(UINT) * n);
+    if (predicted) memcpy(predicted, r + 2 * (size_t)n, sizeof(UINT) * n);
+    return n;
+}
+extern "C" UINT _NN(return, confusion_launches)(nn_def *c) { return c ? c->confusion_launches : 0; }
+extern "C" BOOL _NN(dump, confusion_matrix)(nn_def *c, int which, const CHAR *filename) {
+    const UINT n = _NN(get, confusion_matrix)(c, which, 0, NULL);
+    if (!n || !filename) return FALSE;
+    FILE *fp = fopen(filename, "w");
+    if (!fp) return FALSE;
+    const UINT *m = which == NN_CONFUSION_BEST ? c->confusion_best : c->confusion_last;
+    _OUT(fp, "# %u\n", n);
+    for (UINT t = 0; t < n; t++)
+        for (UINT g = 0; g <= n; g++) _OUT(fp, "%u%c", m[(size_t)t * (n + 1) + g], g == n ? '\n' : ' ');
+    return fclose(fp) == 0;
 }
 extern "C" const DOUBLE *_NN(get, lr_history)(nn_def *c, UINT *n) {
     if (n) *n = c && c->lr_history ? c->n_lr_history : 0;
@@ -541,6 +593,8 @@ static bool refused_validation(const nn_def *conf, const kernel_ann *k, std::vec
         REFUSE("[keep_best] needs [validate] N: there is no validation pass to keep the best of\n");
     if (conf->patience && !conf->keep_best)
         REFUSE("[patience] needs [keep_best] loss | acc: the metric that has to improve\n");
+    if (conf->confusion && !conf->validate)
+        REFUSE("[confusion] needs [validate] N: there is no validation pass to tally\n");
     if (!conf->validate) return false;
     HpnnSamples vsrc;
     if (!conf->tests || !vsrc.open(conf->tests))
@@ -591,6 +645,7 @@ static bool batched_opts(nn_def *conf, kernel_ann *k, bool gpu, DOUBLE lr, DOUBL
                        "min %g patience %u warmup %u\n", gpu ? "GPU" : "CPU", word_of(LR_WORDS, kind), lr, gamma, period,
                span, lr_end, lr_min, patience, warmup);
     }
+    o.confusion = conf->confusion ? 1 : 0;
     o.clip = conf->clip;
     if (o.clip > 0.0)
         NN_OUT(stdout, "batched %s training: gradient clipping: max norm %g\n", gpu ? "GPU" : "CPU", o.clip);
@@ -654,6 +709,12 @@ static void report_clip(const char *engine, UINT epoch, const hpnn_clip_record &
 static void report_validation(const hpnn_validation_record &r) {
     NN_OUT(stdout, "VALIDATION: epoch %u loss=%.10f acc=%u/%u\n", r.epoch, r.loss, r.correct, r.n);
 }
+/* rec: support, hit, predicted of the pass (n words each) */
+static void report_classes(UINT epoch, const UINT *rec, UINT n) {
+    const int w = hpnn_worst_class(rec, rec + n, (int)n);
+    NN_OUT(stdout, "CLASSES: epoch %u bacc=%.10f worst=%d recall=%u/%u\n", epoch,
+           hpnn_balanced_accuracy(rec, rec + n, (int)n), w, w < 0 ? 0 : rec[n + w], w < 0 ? 0 : rec[w]);
+}
 static void report_best(const char *engine, const hpnn_validation_record &b, nn_keep_best metric) {
     NN_OUT(stdout, "BEST: epoch %u loss=%.10f acc=%u/%u\n", b.epoch, b.loss, b.correct, b.n);
     emit_event("best", engine, "\"epoch\": %u, \"loss\": %.17g, \"correct\": %u, \"n\": %u, \"metric\": \"%s\"", b.epoch,
@@ -667,7 +728,11 @@ static void report_batched(const nn_def *conf, const hpnn_batched_stats &st, con
     for (UINT i = 0; i < st.n_cg; i++) report_cg(engine, epoch0 + i + 1, st.cg[i]);
     for (UINT i = 0; i < st.n_lr; i++) report_lr(engine, epoch0 + i + 1, st.lr_hist[i]);
     for (UINT i = 0; i < st.n_clip; i++) report_clip(engine, epoch0 + i + 1, st.clip_hist[i]);
-    for (UINT i = 0; i < st.n_val; i++) report_validation(st.val[i]);
+    for (UINT i = 0; i < st.n_val; i++) {
+        report_validation(st.val[i]);
+        if (st.class_hist && i < st.n_class_hist)
+            report_classes(st.val[i].epoch, st.class_hist + (size_t)i * 3 * st.n_classes, st.n_classes);
+    }
     if (const hpnn_validation_record *b = best_record(conf, st)) report_best(engine, *b, conf->keep_best);
     if (st.stop_epoch) report_early_stop(engine, st.stop_epoch, conf->patience);
 }
@@ -726,6 +791,7 @@ static void warn_ignored_online(nn_def *conf) {
                    {conf->patience != 0, "[patience]"},
                    {schedule_kind(conf) != NN_LR_NONE, "[lr_schedule]"},
                    {conf->clip > 0.0, "[clip]"},
+                   {conf->confusion != 0, "[confusion]"},
                    {conf->shuffle == NN_SHUFFLE_EPOCH, "[shuffle] epoch"}};
     static bool warned[sizeof ignored / sizeof ignored[0]];
     for (size_t i = 0; i < sizeof ignored / sizeof ignored[0]; i++) {
@@ -801,6 +867,13 @@ extern "C" void _NN(run, kernel)(nn_def *conf) {
     g_last_pass = g_last_total = 0;
     if (!conf || !conf->kernel || !conf->tests || conf->type == NN_TYPE_UKN) return;
     kernel_ann *k = KERN(conf);
+    /* [confusion]: the (truth, guess) pairs of the PASS / FAIL lines below, tallied on the host
+     * through the rule header and kept as the "last" matrix */
+    std::vector<UINT> tally;
+    if (conf->confusion) {
+        drop_confusion(conf);
+        tally.assign((size_t)hpnn_confusion_cells(k->n_outputs), 0u);
+    }
     HpnnSamples src;
     if (!src.open(conf->tests)) {
         NN_ERROR(stderr, "can't open test directory: %s\n", conf->tests);
@@ -886,6 +959,7 @@ extern "C" void _NN(run, kernel)(nn_def *conf) {
             NN_COUT(stdout, " BEST CLASS idx=%u P=%15.10f", guess + 1, res * 100);
         }
         g_last_total++;
+        if (conf->confusion) hpnn_confusion_count(tally.data(), (int)truth, (int)guess, (int)k->n_outputs);
         if (guess == truth) {
             g_last_pass++;
             NN_COUT(stdout, " [PASS]\n");
@@ -900,4 +974,6 @@ extern "C" void _NN(run, kernel)(nn_def *conf) {
     }
     emit_event("run", NULL, "\"pass\": %u, \"total\": %u, \"accuracy\": %.6f", g_last_pass, g_last_total,
                g_last_total ? (double)g_last_pass / g_last_total : 0.0);
+    UINT cells = 0;
+    if (conf->confusion && export_records(tally, &conf->confusion_last, &cells)) conf->n_classes = k->n_outputs;
 }

@@ -79,6 +79,7 @@ static constexpr ConfWord DTYPE_WORDS[] = {{"f64", NN_DTYPE_F64}, {"f32", NN_DTY
                                            {"float", NN_DTYPE_F32}, {NULL, 0}};
 static constexpr ConfWord SHUFFLE_WORDS[] = {{"once", NN_SHUFFLE_ONCE}, {"epoch", NN_SHUFFLE_EPOCH}, {NULL, 0}};
 static constexpr ConfWord KEEP_WORDS[] = {{"loss", NN_KEEP_LOSS}, {"acc", NN_KEEP_ACC}, {NULL, 0}};
+static constexpr ConfWord ONOFF_WORDS[] = {{"on", 1}, {"off", 0}, {NULL, 0}};
 static constexpr ConfWord LR_WORDS[] = {{"constant", NN_LR_CONSTANT}, {"step", NN_LR_STEP}, {"linear", NN_LR_LINEAR},
                                         {"plateau", NN_LR_PLATEAU}, {NULL, 0}};
 
@@ -298,6 +299,7 @@ static constexpr ConfKey CONF_KEYS[] = {
     typed(count("lr_patience", FIELD(lr_patience), 1, "epochs, >= 1")),
     typed(count("warmup", FIELD(warmup), 0, "epochs, >= 0")),
     real("clip", FIELD(clip), is_clip, "the largest gradient norm, finite and > 0; 0: off", is_positive),
+    word("confusion", FIELD(confusion), ONOFF_WORDS, "on | off", 0),
 };
 
 static constexpr bool name_is_prefix(const char *a, const char *b) {

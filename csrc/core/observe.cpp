@@ -7,6 +7,7 @@
  * CUDA_TRACE_V array sums (ann.h:29-33, common.h:486-490).
  */
 #include <libhpnn/observe.h>
+#include <libhpnn/confusion.h>
 #include <dlfcn.h>
 #include <hip/hip_runtime_api.h>
 #include <stdio.h>
@@ -187,6 +188,22 @@ extern "C" void hpnn_metrics_validation(const char *engine, UINT epoch, double l
     snprintf(buf, sizeof buf, "\"engine\": \"%s\", \"epoch\": %u, \"loss\": %.10g, \"correct\": %u, \"n\": %u, "
              "\"accuracy\": %.6f", engine, epoch, loss, correct, n, n ? (double)correct / n : 0.0);
     hpnn_metrics_emit("validation", buf);
+}
+
+extern "C" void hpnn_metrics_classes(const char *engine, UINT epoch, const UINT *rec, UINT n_out) {
+    if (!hpnn_metrics_active() || !rec) return;
+    std::string b = "\"engine\": \"" + std::string(engine) + "\", \"epoch\": " + std::to_string(epoch) +
+                    ", \"n_out\": " + std::to_string(n_out);
+    static const char *names[3] = {"support", "hit", "predicted"};
+    for (int a = 0; a < 3; a++) {
+        b += std::string(", \"") + names[a] + "\": [";
+        for (UINT c = 0; c < n_out; c++) b += (c ? ", " : "") + std::to_string(rec[(size_t)a * n_out + c]);
+        b += "]";
+    }
+    char t[64];
+    snprintf(t, sizeof t, ", \"balanced_accuracy\": %.17g", hpnn_balanced_accuracy(rec, rec + n_out, (int)n_out));
+    b += t;
+    hpnn_metrics_emit("classes", b.c_str());
 }
 
 /* ---------------------------------------------------------------- debug */

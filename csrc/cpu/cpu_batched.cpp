@@ -155,8 +155,9 @@ extern "C" UINT hpnn_validation_schedule(UINT epoch0, UINT epochs, UINT validate
 
 /* [validate]: forward only over the held-out set with the current weights (FP64; the oracle of
  * the GPU engines' validation pass): mean loss per sample and argmax hits (first maximum) */
+/* M (may be NULL; [confusion]): the pass's matrix [n_out][n_out + 1], zero on entry */
 static void cpu_validate(kernel_ann *k, nn_type type, const DOUBLE *X, const DOUBLE *T, UINT n,
-                         hpnn_validation_record *r, DOUBLE *loss_sum) {
+                         hpnn_validation_record *r, DOUBLE *loss_sum, unsigned int *M = NULL) {
     DOUBLE sum = 0.0;
     UINT hits = 0;
     for (UINT s = 0; s < n; s++) {
@@ -170,6 +171,7 @@ static void cpu_validate(kernel_ann *k, nn_type type, const DOUBLE *X, const DOU
             if (t[i] > t[tr]) tr = i;
         }
         hits += (g == tr);
+        if (M) hpnn_confusion_count(M, (int)tr, (int)g, (int)k->n_outputs);
     }
     r->loss = sum / (DOUBLE)n;
     r->correct = hits;
@@ -258,6 +260,12 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
     std::vector<std::vector<DOUBLE>> bestW, bestV, bestA;
     hpnn_adam_state best_ast = ast;
     hpnn_lr_state best_lrs = lrs;
+    /* [confusion]: the oracle of kernels_confusion.hip -- the matrix of every pass through the rule
+     * header, its per-class record, the last and the best pass's matrix */
+    const bool confusion = validate && o->confusion != 0;
+    const size_t cells = (size_t)hpnn_confusion_cells(k->n_outputs);
+    std::vector<unsigned int> cm, cm_best, pch;
+    if (confusion) NN_OUT(stdout, "batched CPU training: per-class metrics of every validation pass\n");
     bool have_best = false, stop = false;
     DOUBLE best_sum = 0.0;
     UINT best_hits = 0, best_index = 0, stale = 0, epochs_run = 0;
@@ -316,9 +324,16 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
             hpnn_validation_record r;
             r.epoch = o->epoch0 + e + 1;
             DOUBLE sum = 0.0;
-            cpu_validate(k, o->type, o->Xv, o->Tv, o->nv, &r, &sum);
+            if (confusion) cm.assign(cells, 0u);
+            cpu_validate(k, o->type, o->Xv, o->Tv, o->nv, &r, &sum, confusion ? cm.data() : NULL);
             hpnn_metrics_validation("cpu", r.epoch, r.loss, r.correct, r.n);
             val.push_back(r);
+            if (confusion) {
+                pch.resize(pch.size() + 3 * (size_t)k->n_outputs);
+                unsigned int *rec = pch.data() + pch.size() - 3 * (size_t)k->n_outputs;
+                hpnn_confusion_classes(cm.data(), (int)k->n_outputs, rec);
+                hpnn_metrics_classes("cpu", r.epoch, rec, k->n_outputs);
+            }
             if (sched) hpnn_lr_plateau(&lrs, sum); /* before the snapshot: the best state holds this pass */
             if (keep && hpnn_best_improves((int)o->keep_best, have_best, sum, r.correct, best_sum, best_hits)) {
                 have_best = true;
@@ -326,6 +341,7 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
                 best_hits = r.correct;
                 best_index = (UINT)val.size() - 1;
                 stale = 0;
+                cm_best = cm;
                 bestW.resize(L);
                 bestV.resize(mom || adam ? L : 0);
                 bestA.resize(adam ? L : 0);
@@ -373,6 +389,15 @@ extern "C" BOOL hpnn_cpu_train_batched(kernel_ann *k, const DOUBLE *X, const DOU
         if (!export_records(val, &st->val, &st->n_val) || !export_records(lrh, &st->lr_hist, &st->n_lr) ||
             !export_records(clh, &st->clip_hist, &st->n_clip) || !export_records(cgh, &st->cg, &st->n_cg))
             return FALSE;
+        if (confusion) {
+            UINT words = 0, n_cells = 0;
+            st->n_classes = k->n_outputs;
+            if (!export_records(pch, &st->class_hist, &words) ||
+                !export_records(cm, &st->confusion_last, &n_cells) ||
+                !export_records(have_best ? cm_best : std::vector<unsigned int>(), &st->confusion_best, &n_cells))
+                return FALSE;
+            st->n_class_hist = (UINT)val.size(); /* records of 3 n_outputs words */
+        }
     }
     /* [keep_best]: the kernel as it was after the best pass's epoch */
     for (UINT l = 0; have_best && l < L; l++) {

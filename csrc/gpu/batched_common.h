@@ -219,11 +219,14 @@ struct BestSnap {
     DevBuf<hpnn_best_state> state;
     std::vector<hpnn_snap_seg> segs;
     std::vector<void *> dst;
-    BOOL init(const std::vector<StateSeg> &src, hipStream_t s) {
+    /* extra (may be null): one more segment behind the net's, with a destination of its own (the
+     * matrix of the kept pass under [confusion]) */
+    BOOL init(const std::vector<StateSeg> &src, hipStream_t s, const hpnn_snap_seg *extra = nullptr) {
         size_t total = 0;
         for (const StateSeg &g : src) total += (g.bytes + 255) / 256 * 256;
         HIPCHK(mem.alloc(total ? total : 256));
-        HIPCHK(table.alloc(src.size() ? src.size() : 1));
+        const size_t n_segs = src.size() + (extra ? 1 : 0);
+        HIPCHK(table.alloc(n_segs ? n_segs : 1));
         HIPCHK(state.alloc(1));
         HIPCHK(hipMemsetAsync(state.get(), 0, sizeof(hpnn_best_state), s));
         size_t off = 0;
@@ -232,14 +235,75 @@ struct BestSnap {
             dst.push_back(mem.get() + off);
             off += (g.bytes + 255) / 256 * 256;
         }
+        if (extra) segs.push_back(*extra);
         if (hpnn_snapshot_table(table.get(), segs.data(), (int)segs.size(), s)) {
-            NN_ERROR(stderr, "[keep_best]: the snapshot table was refused (alignment or too many layers)\n");
+            NN_ERROR(stderr, "[keep_best]: the snapshot table was refused (alignment, or more than %d segments: the "
+                             "layers' weights and moments%s)\n", HPNN_SNAP_MAX_SEGS,
+                     extra ? " and the [confusion] matrix" : "");
             return FALSE;
         }
         return hpnn_best_preload(s) == 0;
     }
     unsigned int *take() const { return &state.get()->take; }
     unsigned int *stop() const { return &state.get()->stop; }
+};
+
+/* [confusion]: the matrix of the pass being tallied (M), of the last pass filed (last) and of the
+ * kept pass (best, under [keep_best]), the per-class history (cap records of 3 n_out words, filed
+ * at the validation cursor) and the guess of every held-out row; allocated only when the key is on */
+struct ClassTally {
+    DevBuf<unsigned int> M, last, best, hist;
+    DevBuf<int> guess;
+    int n_out = 0;
+    size_t cap = 0;
+    unsigned int launches = 0; /* issued by add / commit: a captured launch counts once, not per replay */
+    hipStream_t s = nullptr;
+    size_t cells() const { return (size_t)n_out * ((size_t)n_out + 1); }
+    BOOL init(int n_out_, size_t passes, size_t guess_rows, bool keep, hipStream_t st) {
+        n_out = n_out_;
+        cap = passes;
+        s = st;
+        HIPCHK(M.alloc(cells()));
+        HIPCHK(last.alloc(cells()));
+        HIPCHK(hist.alloc(passes ? passes * 3 * (size_t)n_out : 1));
+        HIPCHK(guess.alloc(guess_rows ? guess_rows : 1));
+        HIPCHK(hipMemsetAsync(M.get(), 0, cells() * sizeof(unsigned int), s));
+        HIPCHK(hipMemsetAsync(last.get(), 0, cells() * sizeof(unsigned int), s));
+        if (keep) {
+            HIPCHK(best.alloc(cells()));
+            HIPCHK(hipMemsetAsync(best.get(), 0, cells() * sizeof(unsigned int), s));
+        }
+        return hpnn_confusion_preload(s) == 0;
+    }
+    /* the segment last -> best of the [keep_best] snapshot table */
+    hpnn_snap_seg seg() const { return {last.get(), best.get(), (unsigned long long)(cells() * sizeof(unsigned int))}; }
+    bool add(long row, int rows, const int *labels, const void *T, int ldt, int t_kind) {
+        launches++;
+        const void *t = labels ? (const void *)(labels + row) : (const void *)((const char *)T + (size_t)row * ldt *
+                                                                             (t_kind == HPNN_CONFUSION_F64 ? 8 : 4));
+        return hpnn_confusion_add(guess.get() + row, t, ldt, labels ? HPNN_CONFUSION_LABELS : t_kind, rows, n_out,
+                                  M.get(), s) == 0;
+    }
+    bool commit(const unsigned int *cursor) {
+        launches++;
+        return hpnn_confusion_commit(M.get(), n_out, hist.get(), last.get(), cursor, (unsigned int)cap, s) == 0;
+    }
+    /* synchronises; the first `passes` records and the matrices (best: only when asked for) */
+    BOOL read(size_t passes, std::vector<unsigned int> *rec, std::vector<unsigned int> *mlast,
+              std::vector<unsigned int> *mbest) const {
+        HIPCHK(hipStreamSynchronize(s));
+        rec->resize(passes * 3 * (size_t)n_out);
+        if (passes) HIPCHK(hipMemcpy(rec->data(), hist.get(), rec->size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+        if (mlast) {
+            mlast->resize(cells());
+            HIPCHK(hipMemcpy(mlast->data(), last.get(), cells() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+        }
+        if (mbest) {
+            mbest->resize(cells());
+            HIPCHK(hipMemcpy(mbest->data(), best.get(), cells() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+        }
+        return TRUE;
+    }
 };
 
 /* data-parallel step over RCCL: one bucket per layer goes into an async all-reduce on the

@@ -354,18 +354,24 @@ struct Batched : NetState<Batched> {
         return upload_bf16(src, rows, cols, *rows_p, p.Kp[0], &vs->x, s);
     }
     float *vacc() { return p.vstats; }
-    BOOL evaluate(const XSet &vs, const float *T, int ldt, int nv) {
+    /* guess (may be null): [the rows upload_val padded the set to] int32, the guess of every row;
+     * chunk(row, rows): called behind the launches of every chunk ([confusion] tallies it) */
+    template <class Chunk>
+    BOOL evaluate(const XSet &vs, const float *T, int ldt, int nv, int *guess, Chunk &&chunk) {
         int r = 0;
         if (p.eval_is_fused()) {
-            r = p.evaluate(at(vs, 0), vs.lab, vs.lab ? nullptr : T, ldt, nv, p.vstats, nullptr, s);
+            r = p.evaluate(at(vs, 0), vs.lab, vs.lab ? nullptr : T, ldt, nv, p.vstats, guess, s);
+            if (!r && !chunk(0L, nv)) r = -5;
         } else {
             for (long row = 0; row < nv && !r; row += p.Bp) {
                 hpnn::XIn v;
                 v.x = (const char *)vs.x + row * vs.row_bytes;
                 v.rowmajor = 1;
                 const int *lb = vs.lab ? vs.lab + row : nullptr;
-                r = p.evaluate(v, lb, lb ? nullptr : T + (size_t)row * ldt, ldt, std::min((long)p.Bp, nv - row),
-                               p.vstats, nullptr, s);
+                const int rows = (int)std::min((long)p.Bp, nv - row);
+                r = p.evaluate(v, lb, lb ? nullptr : T + (size_t)row * ldt, ldt, rows, p.vstats,
+                               guess ? guess + row : nullptr, s);
+                if (!r && !chunk(row, rows)) r = -5;
             }
         }
         if (r) NN_ERROR(stderr, "batched validation pass failed: %d\n", r);
@@ -743,13 +749,17 @@ struct BatchedFP : NetState<BatchedFP<T>> {
         return clip && hpnn_clip_commit_dev(clip_state.get(), hist, cursor, cap, s) == 0;
     }
 
-    BOOL evaluate(const XSet &vs, const T *Tt, int ldt, int nv) {
+    /* guess (may be null): [nv] int32, the guess of every row; chunk(row, rows): called behind the
+     * launches of every chunk ([confusion] tallies it) */
+    template <class Chunk>
+    BOOL evaluate(const XSet &vs, const T *Tt, int ldt, int nv, int *guess, Chunk &&chunk) {
         for (long row = 0; row < nv; row += Bp) {
             const int rows = (int)std::min((long)Bp, nv - row);
             if (!forward(at(vs, row), rows)) return FALSE;
-            if (hpnn_output_fp_eval(F64, Z, N[L - 1], Tt + (size_t)row * ldt, ldt, nullptr, vslots, rows, rows, n_out,
-                                    type, s))
+            if (hpnn_output_fp_eval(F64, Z, N[L - 1], Tt + (size_t)row * ldt, ldt, guess ? guess + row : nullptr,
+                                    vslots, rows, rows, n_out, type, s))
                 return FALSE;
+            if (!chunk(row, rows)) return FALSE;
         }
         return TRUE;
     }

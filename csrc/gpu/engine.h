@@ -18,6 +18,7 @@
 #include <libhpnn/adam.h>
 #include <libhpnn/lrsched.h>
 #include <libhpnn/clip.h>
+#include <libhpnn/confusion.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -80,6 +81,10 @@ typedef struct {
     /* [clip] c (single-device engines and the CPU oracle; 0: off): the gradient of every step is
      * rescaled when its global L2 norm exceeds c (<libhpnn/clip.h>); BP, BPM and ADAM */
     DOUBLE clip;
+    /* [confusion] (1: on; single-device engines and the CPU oracle; needs validate > 0): every
+     * validation pass also tallies its confusion matrix and per-class record
+     * (<libhpnn/confusion.h>) */
+    UINT confusion;
 } hpnn_batched_opts;
 
 /* one validation pass: the absolute epoch it followed, the mean loss per sample and the argmax
@@ -122,6 +127,17 @@ typedef struct {
      * steps, the largest and the last norm), malloc'ed by the engine (the caller frees clip_hist) */
     hpnn_clip_record *clip_hist;
     UINT n_clip;
+    /* [confusion]: n_classes = the net's outputs (0: off); one per-class record (support, hit,
+     * predicted: 3 n_classes words) per validation record of val; the matrix
+     * [n_classes][n_classes + 1] of the last pass reported and of the best pass (NULL: none); all
+     * malloc'ed by the engine (the caller frees them); confusion_launches: the tally launches the
+     * driver issued, captured ones once per capture and not per replay (0 when off) */
+    UINT n_classes;
+    UINT *class_hist;
+    UINT n_class_hist;
+    UINT *confusion_last;
+    UINT *confusion_best;
+    UINT confusion_launches;
 } hpnn_batched_stats;
 
 /* the improvement rule of [keep_best] (one definition for every engine; the device form is

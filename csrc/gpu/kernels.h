@@ -389,6 +389,29 @@ int hpnn_snapshot_if(const hpnn_snap_seg *segs, int n_segs, const unsigned int *
  * synchronise: loads the unit's code object before a capture */
 int hpnn_best_empty_launch(hipStream_t stream);
 int hpnn_best_preload(hipStream_t stream);
+/* ---- per-class validation metrics (kernels_confusion.hip; [confusion], rule in
+ * <libhpnn/confusion.h>) ----
+ * Every launch is capturable and allocates nothing.  M: uint32 [n_out][n_out + 1], zero before the
+ * first add of a pass.
+ * add: the rows of one evaluation chunk into M.  guess [rows] int32 as the evaluation kernels write
+ * it (-1: not a sample, >= n_out: the "none" column); targets by t_kind: int32 labels [rows] (ldt
+ * unused; a label outside [0, n_out) skips its row), or dense FP32 / FP64 rows ldt elements apart
+ * (the target class is the lowest index of the largest value).  One unsigned atomic add per sample
+ * into M in global memory: the result does not depend on the grid.  -1: refused. */
+#define HPNN_CONFUSION_MAX_NOUT 4096
+#define HPNN_CONFUSION_LABELS 0
+#define HPNN_CONFUSION_F32 1
+#define HPNN_CONFUSION_F64 2
+int hpnn_confusion_add(const int *guess, const void *targets, int ldt, int t_kind, int rows, int n_out,
+                       unsigned int *M, hipStream_t stream);
+/* commit: one workgroup, in front of hpnn_validate_commit on the same stream (*cursor = the index
+ * of the pass being filed; it is not advanced here): the per-class record support[n_out],
+ * hit[n_out], predicted[n_out] into pc_hist[*cursor] (records of 3 n_out words; dropped when
+ * *cursor >= cap or pc_hist is NULL), M copied to last (may be NULL), M zeroed */
+int hpnn_confusion_commit(unsigned int *M, int n_out, unsigned int *pc_hist, unsigned int *last,
+                          const unsigned int *cursor, unsigned int cap, hipStream_t stream);
+/* loads the unit's code object (an empty launch and a synchronise) before a capture */
+int hpnn_confusion_preload(hipStream_t stream);
 /* ---- conjugate-gradient trainer (kernels_cg.hip; [train] CG, rules in <libhpnn/cg.h>) ----
  * Every launch is capturable, allocates nothing and reads its scalars (beta, the steps a_j) from
  * the DEVICE state when it runs.  f64 selects double, else float.  A segment is one layer:

@@ -25,6 +25,7 @@ struct RunDev {
     const DevHistory<hpnn_val_record> &vh;
     const DevHistory<double> &lrh;
     const DevHistory<hpnn_clip_record> &clh;
+    const ClassTally *tally; /* null without [confusion] */
 };
 
 /* what collect() reads: the best state and the histories, each up to the last epoch that counts */
@@ -37,6 +38,9 @@ struct RunRecords {
     std::vector<double> lrec;
     std::vector<hpnn_clip_record> clrec;
     hpnn_lr_state lrs; /* the schedule state of the returned kernel */
+    /* [confusion]: one per-class record per pass of vrec; the matrix of the last of them (empty when
+     * the device went on past it after a stop) and of the best pass (empty: none) */
+    std::vector<unsigned int> pcrec, mlast, mbest;
 };
 
 /* after the last of the e epochs run: every read-back, once, with its "filed" check */
@@ -92,7 +96,19 @@ BOOL collect(const RunDev<Net> &d, int e, bool metrics, RunRecords *r) {
     if (o->sched && !(read(d.lrh, &r->lrec, "learning rates") &&
                       d.net.read_schedule(hb.valid ? d.best->dst.data() : nullptr, &r->lrs)))
         return FALSE;
-    return o->clip <= 0.0 || read(d.clh, &r->clrec, "clip records");
+    if (o->clip > 0.0 && !read(d.clh, &r->clrec, "clip records")) return FALSE;
+    if (d.tally) {
+        /* the device cursor after the last replay: `last` is the pass of that cursor, which is the
+         * last pass reported unless the replays ran on past a stopping pass */
+        unsigned int filed = 0;
+        if (hipStreamSynchronize(d.s) != hipSuccess ||
+            hipMemcpy(&filed, d.vh.cursor(), sizeof filed, hipMemcpyDeviceToHost) != hipSuccess)
+            return FALSE;
+        const bool last_is_reported = !vrec.empty() && filed == vrec.size();
+        if (!d.tally->read(vrec.size(), &r->pcrec, &r->mlast, hb.valid ? &r->mbest : nullptr)) return FALSE;
+        if (!last_is_reported) r->mlast.clear();
+    }
+    return TRUE;
 }
 
 
@@ -213,11 +229,11 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
     ResidentSet<TT> va;
     DevHistory<hpnn_val_record> vh;
     std::vector<UINT> vsched;
+    int vrows_p = 0; /* the rows the held-out set is padded to */
     if (validate) {
         vsched.resize(hpnn_validation_schedule(o->epoch0, o->epochs, o->validate, nullptr));
         hpnn_validation_schedule(o->epoch0, o->epochs, o->validate, vsched.data());
-        int vrows = 0;
-        if (!va.upload(net, o->Xv, o->Tv, o->nv, n_in, n_out, &vrows, o->type, s, true)) return FALSE;
+        if (!va.upload(net, o->Xv, o->Tv, o->nv, n_in, n_out, &vrows_p, o->type, s, true)) return FALSE;
         if (!vh.init(vsched.size(), 1)) return FALSE;
         NN_OUT(stdout, "batched GPU training: %d held-out samples validated every %u epochs\n", nval, o->validate);
     }
@@ -230,13 +246,27 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
      * stopping pass's replay plus one more replay run past it, changing nothing that is returned */
     const bool keep = validate && o->keep_best != 0;
     BestSnap best;
+    /* [confusion]: the evaluation also writes every row's guess, a tally launch behind every chunk
+     * adds guess and target class into the pass's matrix, and in front of the commit one launch
+     * files the per-class record at the validation cursor, keeps the matrix as "last" and zeroes
+     * it; under [keep_best] last -> best is one more segment of the snapshot */
+    const bool confusion = validate && o->confusion != 0;
+    ClassTally tally;
+    if (confusion && !tally.init(n_out, vsched.size(), (size_t)vrows_p, keep, s)) return FALSE;
+    const hpnn_snap_seg tally_seg = confusion && keep ? tally.seg() : hpnn_snap_seg{};
     if (keep) {
-        if (!best.init(net.segs, s)) return FALSE;
+        if (!best.init(net.segs, s, confusion ? &tally_seg : nullptr)) return FALSE;
         NN_OUT(stdout, "batched GPU training: the best validation pass (%s) is kept\n",
                o->keep_best == NN_KEEP_ACC ? "acc" : "loss");
     }
+    if (confusion) NN_OUT(stdout, "batched GPU training: per-class metrics of every validation pass\n");
+    const int t_kind = sizeof(TT) == 8 ? HPNN_CONFUSION_F64 : HPNN_CONFUSION_F32;
+    auto tally_chunk = [&](long row, int rows) -> bool {
+        return !confusion || tally.add(row, rows, va.xs.lab, va.T.get(), n_out, t_kind);
+    };
     auto validation = [&]() -> bool {
-        if (net.evaluate(va.xs, va.T.get(), n_out, nval) &&
+        if (net.evaluate(va.xs, va.T.get(), n_out, nval, confusion ? tally.guess.get() : nullptr, tally_chunk) &&
+            (!confusion || tally.commit(vh.cursor())) &&
             hpnn_validate_commit(net.vacc(), vh.hist(), vh.cursor(), vh.cap(), s) == 0 &&
             /* plateau sees the pass before the snapshot: the best state holds this pass */
             (!sched || hpnn_lr_plateau_dev(vh.hist(), vh.cursor(), net.lr_dev(), s) == 0) &&
@@ -380,6 +410,12 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
             if (ok)
                 hpnn_metrics_validation("gpu", o->epoch0 + e, vrec[vdone].loss_sum / (double)nval, vrec[vdone].hits,
                                         (UINT)nval);
+            if (ok && confusion) {
+                std::vector<unsigned int> pc((size_t)3 * n_out);
+                ok = hipMemcpy(pc.data(), tally.hist.get() + vdone * pc.size(), pc.size() * sizeof(unsigned int),
+                               hipMemcpyDeviceToHost) == hipSuccess;
+                if (ok) hpnn_metrics_classes("gpu", o->epoch0 + e, pc.data(), (UINT)n_out);
+            }
             vdone++;
             if (ok && hstop) stopped = true;
         }
@@ -388,7 +424,7 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
     /* stopped before the last epoch: the statistics of the last epoch that ran */
     if (ok && !metrics && e < E) ok = net.read_stats(&ep_loss, &ep_hits);
     auto t1 = std::chrono::steady_clock::now();
-    const RunDev<Net> dev{net, s, o, vsched, keep ? &best : nullptr, vh, lrh, clh};
+    const RunDev<Net> dev{net, s, o, vsched, keep ? &best : nullptr, vh, lrh, clh, confusion ? &tally : nullptr};
     if (ok) ok = collect(dev, e, metrics, &rec);
     const hpnn_best_state &hb = rec.hb;
     graphs.clear();
@@ -408,6 +444,15 @@ BOOL train_single_t(kernel_ann *k, const DOUBLE *X, const DOUBLE *T, UINT n, con
         ok = export_records(rec.lrec, &st->lr_hist, &st->n_lr) && ok;
         ok = export_records(rec.clrec, &st->clip_hist, &st->n_clip) && ok;
         ok = export_records(val, &st->val, &st->n_val) && ok;
+        if (confusion) {
+            UINT words = 0, cells = 0;
+            st->n_classes = (UINT)n_out;
+            ok = export_records(rec.pcrec, &st->class_hist, &words) && ok;
+            st->n_class_hist = (UINT)val.size(); /* records of 3 n_out words */
+            ok = export_records(rec.mlast, &st->confusion_last, &cells) && ok;
+            ok = export_records(rec.mbest, &st->confusion_best, &cells) && ok;
+            st->confusion_launches = tally.launches;
+        }
     }
     /* device FP64 copy of the online engine (if any) is now stale */
     hpnn_gpu_mark_host_dirty(k);

@@ -584,6 +584,25 @@ PYBIND11_MODULE(_native, m) {
         return hpnn_snapshot_if((const hpnn_snap_seg *)P(segs), n_segs, (const unsigned int *)P(take), S(stream));
     });
     m.def("best_empty_launch", [](uptr stream) { return hpnn_best_empty_launch(S(stream)); });
+    /* [confusion] (kernels_confusion.hip); each returns the launcher's code (0, or -1: refused) */
+    m.def("confusion_add", [](uptr guess, uptr targets, int ldt, int t_kind, int rows, int n_out, uptr M, uptr stream) {
+        return hpnn_confusion_add((const int *)P(guess), P(targets), ldt, t_kind, rows, n_out, (unsigned int *)P(M),
+                                  S(stream));
+    });
+    m.def("confusion_commit", [](uptr M, int n_out, uptr pc_hist, uptr last, uptr cursor, unsigned int cap, uptr stream) {
+        return hpnn_confusion_commit((unsigned int *)P(M), n_out, (unsigned int *)P(pc_hist), (unsigned int *)P(last),
+                                     (const unsigned int *)P(cursor), cap, S(stream));
+    });
+    m.def("confusion_preload", [](uptr stream) { return hpnn_confusion_preload(S(stream)); });
+    /* the rule of <libhpnn/confusion.h> on host arrays (the C side of the tests) */
+    m.def("balanced_accuracy", [](const std::vector<unsigned int> &support, const std::vector<unsigned int> &hit) {
+        if (support.size() != hit.size()) throw std::runtime_error("balanced_accuracy: support and hit differ in length");
+        return hpnn_balanced_accuracy(support.data(), hit.data(), (int)support.size());
+    });
+    m.def("worst_class", [](const std::vector<unsigned int> &support, const std::vector<unsigned int> &hit) {
+        if (support.size() != hit.size()) throw std::runtime_error("worst_class: support and hit differ in length");
+        return hpnn_worst_class(support.data(), hit.data(), (int)support.size());
+    });
     /* [train] CG (kernels_cg.hip); each returns the launcher's code (0, or -1: refused).  A segment
      * is (w, w0, g, gprev, d, slab, S, sstride, n) with device addresses (0 = unused) */
     m.attr("CG_STATE_BYTES") = (int)sizeof(hpnn_cg_state);

@@ -23,6 +23,7 @@ NN_DEVICE = {"auto": 0, "cpu": 1, "gpu": 2}
 NN_LR_SCHEDULE = {None: -1, "constant": 0, "step": 1, "linear": 2, "plateau": 3}
 NN_SHUFFLE = {"once": 0, "epoch": 1}
 NN_KEEP_BEST = {"off": 0, "loss": 1, "acc": 2}
+NN_CONFUSION = {"last": 0, "best": 1}
 CG_FAILED, CG_RESTART, CG_VERTEX, CG_TOOK7 = 1, 2, 4, 8  # flags of a CG record (include/libhpnn/cg.h)
 
 
@@ -80,6 +81,9 @@ def lib():
             "nn_get_lr_history": (ctypes.POINTER(d), [vp, ctypes.POINTER(u)]),
             "nn_set_clip": (None, [vp, d]), "nn_get_clip": (d, [vp]),
             "nn_get_clip_history": (ctypes.POINTER(ClipRecord), [vp, ctypes.POINTER(u)]),
+            "nn_set_confusion": (None, [vp, i]), "nn_return_confusion": (i, [vp]),
+            "nn_get_confusion_matrix": (u, [vp, i, u, vp]), "nn_get_class_history": (u, [vp, u, vp, vp, vp]),
+            "nn_return_confusion_launches": (u, [vp]), "nn_dump_confusion_matrix": (i, [vp, i, cp]),
             "nn_return_last_pass": (u, []), "nn_return_last_total": (u, []),
             "nn_return_version": (cp, []), "nn_return_type": (i, [vp]), "nn_return_train": (i, [vp]),
             "nn_dump_state": (i, [vp, cp]), "nn_load_state": (i, [vp, cp]), "nn_return_epochs_done": (u, [vp]),
@@ -136,7 +140,8 @@ class Network:
 
     # configuration
     def set(self, mode=None, dtype=None, device=None, batch=None, epochs=None, lr=None, momentum=None, seed=None,
-            shuffle=None, validate=None, keep_best=None, patience=None, adam=None, lr_schedule=None, clip=None):
+            shuffle=None, validate=None, keep_best=None, patience=None, adam=None, lr_schedule=None, clip=None,
+            confusion=None):
         if mode is not None:
             self.L.nn_set_mode(self.ptr, NN_MODE[mode])
         if dtype is not None:
@@ -184,7 +189,52 @@ class Network:
             if not (c >= 0.0 and c != float("inf")):
                 raise ValueError(f"clip: {clip!r} (a finite norm > 0; 0 turns it off)")
             self.L.nn_set_clip(self.ptr, c)
+        if confusion is not None:  # per-class metrics of every validation pass / of run() ([confusion] on | off)
+            self.L.nn_set_confusion(self.ptr, int(bool(confusion)))
         return self
+
+    @property
+    def confusion(self):
+        return bool(self.L.nn_return_confusion(self.ptr))
+
+    def confusion_matrix(self, which="last"):
+        """the confusion matrix of the last train() or run() call as a [n_out, n_out + 1] numpy uint32
+        array (row = target class, column = guess, the last column "none"): which "last" = the last
+        validation pass reported (or the run), "best" = the pass keep_best kept; None when there is
+        nothing to report"""
+        import numpy as np
+        w = NN_CONFUSION[which]
+        n = self.L.nn_get_confusion_matrix(self.ptr, w, 0, None)
+        if not n:
+            return None
+        m = np.zeros((n, n + 1), dtype=np.uint32)
+        self.L.nn_get_confusion_matrix(self.ptr, w, m.size, m.ctypes.data)
+        return m
+
+    def class_history(self):
+        """one dict per validation pass of the last train() call under [confusion]: numpy uint32
+        arrays support, hit and predicted (one entry per class) and balanced_accuracy"""
+        import numpy as np
+        from . import ops
+        out = []
+        while True:
+            n = self.L.nn_get_class_history(self.ptr, len(out), None, None, None)
+            if not n:
+                return out
+            a = [np.zeros(n, dtype=np.uint32) for _ in range(3)]
+            self.L.nn_get_class_history(self.ptr, len(out), *[x.ctypes.data for x in a])
+            out.append({"support": a[0], "hit": a[1], "predicted": a[2],
+                        "balanced_accuracy": ops.balanced_accuracy(a[0], a[1])})
+
+    @property
+    def confusion_launches(self):
+        """the tally launches the last train() call issued on the GPU, a captured launch counted once
+        however often its graph is replayed (0 with the key off)"""
+        return self.L.nn_return_confusion_launches(self.ptr)
+
+    def dump_confusion_matrix(self, path, which="last"):
+        if not self.L.nn_dump_confusion_matrix(self.ptr, NN_CONFUSION[which], path.encode()):
+            raise OSError(f"nn_dump_confusion_matrix({path}) failed: nothing to report, or the file cannot be written")
 
     @property
     def clip(self):

@@ -108,6 +108,8 @@ class MLP:
             raise ValueError(f"optimizer {optimizer!r} (sgd | adam)")
         self.adam = optimizer == "adam"
         adam_cfg = (float(lr), float(betas[0]), float(betas[1]), float(eps), float(decay)) if self.adam else None
+        self._best = None  # keep_best(): the best state
+        self._cm = self._cm_last = self._cm_best = self._pc_hist = None  # confusion(True): the tally's tensors
         self.sched = lr_schedule is not None
         sched_cfg = None
         if self.sched:
@@ -591,6 +593,15 @@ class MLP:
             raise ValueError("evaluate needs labels or dense targets T")
         vst = self.buf[("vstats", -1)]
         ldt = T.stride(0) if T is not None else 0
+        tally = self._cm is not None  # confusion(True): every chunk is tallied, which needs its guesses
+        asked, guess = guess, guess or tally
+
+        def tallied(g, r0=0, n=n_valid):
+            """the caller's return value: the guesses only when asked for"""
+            if tally:
+                ops.confusion_add(g[r0:], self._cm, labels=None if labels is None else labels[r0:],
+                                  T=None if labels is not None else T[r0:], rows=n)
+            return g if asked else None
         if not self._gpu:
             A = self._rowmajor(X)[:n_valid]
             for l in range(self.L - 1):
@@ -606,7 +617,7 @@ class MLP:
                 return None
             g = torch.full((rows,), -1, dtype=torch.int32)
             g[:n_valid] = Z[:, :self.n_out].argmax(1).to(torch.int32)
-            return g
+            return tallied(g)
         if self.plan.eval_is_fused() and self._is_fm(X):
             if X.shape[1] * 16 != self.Kp[0]:
                 raise ValueError(f"fragment-major input {tuple(X.shape)} does not fit Kp0 {self.Kp[0]}")
@@ -615,7 +626,7 @@ class MLP:
             g = torch.empty(ops.pad_to(n_valid, 256), dtype=torch.int32, device=self.device) if guess else None
             self.plan.evaluate(X.data_ptr(), int(X.dtype == torch.uint8), float(getattr(X, "hpnn_fm_scale", 1.0)),
                                False, _p(labels), _p(T), ldt, n_valid, vst.data_ptr(), _p(g), _stream())
-            return g
+            return tallied(g)
         Xr = self._rowmajor(X)
         chunks = (n_valid + self.Bp - 1) // self.Bp
         if Xr.shape[0] < chunks * self.Bp:  # the per-layer kernels read whole Bp-row chunks
@@ -626,13 +637,58 @@ class MLP:
             self.plan.evaluate(Xr[r0:].data_ptr(), 0, 1.0, True, _p(None if labels is None else labels[r0:]),
                                _p(None if T is None else T[r0:]), ldt, min(self.Bp, n_valid - r0), vst.data_ptr(),
                                _p(None if g is None else g[r0:]), _stream())
-        return g
+            tallied(g, r0, min(self.Bp, n_valid - r0))
+        return g if asked else None
 
     # ------------------------------------------------------------------ keep the best pass
     def _masters(self):
         m = [t for l in range(self.L) for t in (self.W32[l], self.V32[l], self.A32[l]) if t is not None]
         m += [self.adam_state.view(torch.float32)] if self.adam else []
         return m + ([self.lr_state.view(torch.float32)] if self.sched else [])
+
+    # ------------------------------------------------------------------ per-class metrics
+    def confusion(self, enable=True, passes=64):
+        """[confusion] (docs/DESIGN.md 3.2l): with enable, every evaluate() call also adds its rows
+        into a device confusion matrix [n_out, n_out + 1] (ops.confusion_add per chunk), and
+        commit_confusion files a pass: the per-class record into a history of `passes` records,
+        the matrix kept as "last" and zeroed.  Under keep_best the kept pass's matrix survives as
+        "best" (one more segment of the snapshot).  enable=False frees everything: evaluate()
+        launches nothing more."""
+        if not enable:
+            self._cm = self._cm_last = self._cm_best = self._pc_hist = None
+        else:
+            self._cm = ops.confusion_matrix(self.n_out, self.device)
+            self._cm_last, self._cm_best = torch.zeros_like(self._cm), torch.zeros_like(self._cm)
+            self._pc_hist = torch.zeros(int(passes), 3 * self.n_out, dtype=torch.int32, device=self.device)
+        if self._best is not None:
+            self._snapshot_table()
+
+    def commit_confusion(self, cursor):
+        """in front of ops.validate_commit(vstats, hist, cursor) on the current stream: file the
+        matrix the evaluate() calls since the last commit tallied, at the record index `cursor`
+        holds (one launch, no host sync; capturable)"""
+        ops.confusion_commit(self._cm, self._pc_hist, self._cm_last, cursor)
+
+    def confusion_matrix(self, which="last"):
+        """the matrix of the last pass filed ("last") or of the pass keep_best kept ("best") as a
+        [n_out, n_out + 1] int64 CPU tensor; None when there is none (synchronises)"""
+        if which not in ("last", "best"):
+            raise ValueError(f"confusion_matrix: which {which!r} (last | best)")
+        if self._cm is None:
+            return None
+        if which == "best" and (self._best is None or not self.best_state()["valid"]):
+            return None
+        return (self._cm_last if which == "last" else self._cm_best).cpu().long() & 0xffffffff
+
+    def class_history(self, n):
+        """the first n per-class records filed: dicts of support, hit, predicted (synchronises)"""
+        return [ops.class_record(self._pc_hist, i) for i in range(n)]
+
+    def _snapshot_table(self):
+        pairs = list(zip(self._masters(), self._snap))
+        if self._cm is not None:
+            pairs.append((self._cm_last, self._cm_best))
+        self._snap_table = ops.snapshot_table(pairs)
 
     def keep_best(self, metric="loss", patience=0):
         """allocate the best state and the snapshot of the FP32 masters (and the momentum) for
@@ -642,7 +698,7 @@ class MLP:
         self._best_metric, self._best_patience = metric, int(patience)
         self._best = ops.best_state(self.device)
         self._snap = [torch.zeros_like(t) for t in self._masters()]
-        self._snap_table = ops.snapshot_table(list(zip(self._masters(), self._snap)))
+        self._snapshot_table()
 
     def commit_best(self, hist, cursor):
         """behind ops.validate_commit(vstats, hist, cursor) on the current stream: judge the

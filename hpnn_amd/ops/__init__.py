@@ -587,6 +587,115 @@ def snapshot_if(segs, take):
         raise RuntimeError(f"snapshot_if failed (rc={rc})")
 
 
+# --------------------------------------------------------------------------- [confusion]
+GUESS_PAD, GUESS_NONE = -1, 1 << 30  # HPNN_GUESS_PAD / HPNN_GUESS_NONE (include/libhpnn/confusion.h)
+_CONFUSION_KIND = {torch.int32: 0, torch.float32: 1, torch.float64: 2}
+
+
+def confusion_matrix(n_out, device="cpu"):
+    """a zeroed confusion matrix [n_out, n_out + 1] int32 (uint32 counts; the last column is "none")"""
+    return torch.zeros(n_out, n_out + 1, dtype=torch.int32, device=device)
+
+
+def confusion_add(guess, M, labels=None, T=None, rows=None):
+    """add the first `rows` rows (default: all of guess) of one evaluation chunk into the confusion
+    matrix M [n_out, n_out + 1] int32 (csrc/gpu/kernels_confusion.hip; the rule is
+    include/libhpnn/confusion.h): M[t, g] += 1 for every row of target class t guessed g.  guess:
+    int32 as the evaluation kernels write it (-1: not a sample; >= n_out: the "none" column).
+    Targets: int32 labels (a label outside [0, n_out) skips its row) or dense float32 / float64 rows
+    T (row stride >= n_out; the lowest index of the largest value).  Integer atomics only, so the
+    result is the same bits whatever the grid.  One capturable launch; on CPU tensors the same counts in PyTorch integers."""
+    if (labels is None) == (T is None):
+        raise ValueError("confusion_add needs labels or dense targets T, not both")
+    n_out = M.shape[0]
+    if M.dtype != torch.int32 or M.shape[1] != n_out + 1 or not M.is_contiguous():
+        raise ValueError("confusion_add: M is a contiguous [n_out, n_out + 1] int32 tensor")
+    tgt = labels if T is None else T
+    rows = guess.shape[0] if rows is None else int(rows)
+    if tgt.dtype not in _CONFUSION_KIND or (T is None) != (tgt.dtype == torch.int32):
+        raise ValueError(f"confusion_add: targets of dtype {tgt.dtype}")
+    if guess.dtype != torch.int32 or rows > guess.shape[0] or rows > tgt.shape[0] or rows < 0:
+        raise ValueError("confusion_add: guess is int32 with at least `rows` entries, as the targets")
+    if T is not None and (T.shape[1] < n_out or T.stride(1) != 1):
+        raise ValueError("confusion_add: T has at least n_out columns of stride 1")
+    if _cpu(guess):
+        g = guess[:rows].long()
+        if T is None:
+            t = labels[:rows].long()
+        else:  # the lowest index of the largest value; NaNs never compare, a NaN at [0] gives 0
+            x = T[:rows, :n_out]
+            clean = torch.where(torch.isnan(x), torch.full_like(x, float("-inf")), x)
+            col = torch.arange(n_out).expand_as(clean)
+            t = torch.where(clean == clean.max(1, keepdim=True).values, col, torch.full_like(col, n_out)).min(1).values
+            t = torch.where(torch.isnan(x[:, 0]), torch.zeros_like(t), t)
+        ok = (g >= 0) & (t >= 0) & (t < n_out)
+        cell = t[ok] * (n_out + 1) + g[ok].clamp(max=n_out)
+        counts = torch.bincount(cell, minlength=n_out * (n_out + 1))
+        M.view(-1).copy_(_u32((M.view(-1).long() & 0xffffffff) + counts))
+        return M
+    rc = native().confusion_add(guess.data_ptr(), tgt.data_ptr(), T.stride(0) if T is not None else 0,
+                                _CONFUSION_KIND[tgt.dtype], rows, n_out, M.data_ptr(), _stream())
+    if rc:
+        raise RuntimeError(f"confusion_add failed (rc={rc})")
+    return M
+
+
+def _u32(x):
+    """int64 values mod 2^32 as the int32 tensor with those bits"""
+    x = x & 0xffffffff
+    return torch.where(x >= 1 << 31, x - (1 << 32), x).to(torch.int32)
+
+
+def confusion_commit(M, pc_hist, last, cursor):
+    """file one pass, in front of validate_commit: the per-class record -- support (row sums), hit
+    (diagonal), predicted (column sums), n_out words each -- into pc_hist[cursor] (pc_hist: [cap,
+    3 * n_out] int32; a cursor at cap drops the record), M copied to `last` (may be None), M zeroed.
+    The cursor ([1] int32) is read, not advanced: validate_commit does that.  One capturable
+    one-workgroup launch; on CPU tensors the same in PyTorch integers."""
+    n_out = M.shape[0]
+    if pc_hist is not None and (pc_hist.dtype != torch.int32 or pc_hist.shape[1] != 3 * n_out or
+                                not pc_hist.is_contiguous()):
+        raise ValueError("confusion_commit: pc_hist is a contiguous [cap, 3 * n_out] int32 tensor")
+    if last is not None and (last.shape != M.shape or last.dtype != torch.int32 or not last.is_contiguous()):
+        raise ValueError("confusion_commit: last has the shape and dtype of M")
+    cap = 0 if pc_hist is None else pc_hist.shape[0]
+    if _cpu(M):
+        c = int(cursor[0]) & 0xffffffff
+        if c < cap:
+            m = M.long() & 0xffffffff
+            pc_hist[c, :n_out] = _u32(m.sum(1))
+            pc_hist[c, n_out:2 * n_out] = M.diagonal()
+            pc_hist[c, 2 * n_out:] = _u32(m[:, :n_out].sum(0))
+        if last is not None:
+            last.copy_(M)
+        M.zero_()
+        return pc_hist
+    rc = native().confusion_commit(M.data_ptr(), n_out, _ptr(pc_hist), _ptr(last), cursor.data_ptr(), cap, _stream())
+    if rc:
+        raise RuntimeError(f"confusion_commit failed (rc={rc})")
+    return pc_hist
+
+
+def class_record(pc_hist, index):
+    """record `index` of a per-class history as a dict of int lists: support, hit, predicted
+    (synchronises)"""
+    r = (pc_hist[index].cpu().long() & 0xffffffff).tolist()
+    n = len(r) // 3
+    return {"support": r[:n], "hit": r[n:2 * n], "predicted": r[2 * n:]}
+
+
+def balanced_accuracy(support, hit):
+    """the mean of hit[c] / support[c] over the classes with support, in float64, in class order,
+    additions and divisions only (hpnn_balanced_accuracy: the same bits as the C rule); 0.0 when no
+    class has support"""
+    total, classes = 0.0, 0.0
+    for s, h in zip([int(v) for v in support], [int(v) for v in hit]):
+        if s:
+            total = total + float(h) / float(s)
+            classes = classes + 1.0
+    return total / classes if classes > 0.0 else 0.0
+
+
 # --------------------------------------------------------------------------- [train] CG
 CG_TRIALS, CG_PARABOLA, CG_FINAL = 6, 6, 7  # HPNN_CG_TRIALS / _PARABOLA / _FINAL (include/libhpnn/cg.h)
 CG_NONE = 0xffffffff

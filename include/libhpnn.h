@@ -186,6 +186,18 @@ typedef struct {
     DOUBLE clip;
     UINT n_clip_history;
     void *clip_history;
+    /* -- [confusion] on | off: every validation pass of batched training, and nn_run_kernel, also
+     *    tally the confusion matrix (<libhpnn/confusion.h>); of the last call: the classes, one
+     *    per-class record (3 n_classes words) per validation record, the matrix of the last pass
+     *    and of the best one (NULL: none), the tally launches the GPU driver issued
+     *    (nn_get_confusion_matrix, nn_get_class_history) -- */
+    int confusion;
+    UINT n_classes;
+    UINT n_class_history;
+    UINT *class_history;
+    UINT *confusion_last;
+    UINT *confusion_best;
+    UINT confusion_launches;
 } nn_def;
 
 #define _NN(a, b) nn_##a##_##b
@@ -399,6 +411,33 @@ typedef struct {
 void _NN(set, clip)(nn_def *conf, DOUBLE max_norm);
 DOUBLE _NN(get, clip)(nn_def *conf);
 const nn_clip_record *_NN(get, clip_history)(nn_def *conf, UINT *n);
+/* [confusion] on | off: per-class validation metrics (<libhpnn/confusion.h>).  In batched training
+ * (one device or the CPU engine; needs [validate]) every validation pass also tallies its confusion
+ * matrix M[n_out][n_out + 1] -- M[t][g] = held-out samples of target class t guessed g, column
+ * n_out ("none") the rows in which no output compared -- on the device, inside the captured
+ * epochs; nn_train_kernel prints "CLASSES: epoch E bacc=B worst=c recall=h/s" behind every
+ * "VALIDATION:" line (B the balanced accuracy, c the supported class of lowest recall, lowest index
+ * on ties).  nn_run_kernel tallies the (truth, guess) pairs of its PASS / FAIL lines.  Online
+ * training ignores the key with one warning.
+ * nn_get_confusion_matrix: which = NN_CONFUSION_LAST (the last pass reported, or the last
+ * nn_run_kernel call) | NN_CONFUSION_BEST (the pass [keep_best] kept); copies at most max_cells
+ * cells (row-major, n_out (n_out + 1) of them) and returns n_out, 0 when there is nothing to report
+ * (after an early stop the GPU engine may have validated past the stopping pass: it then reports
+ * no last matrix).  nn_get_class_history: support (row sums), hit (diagonal) and predicted (column
+ * sums) of validation pass `pass` of the last nn_train_kernel call, n_out words each (any pointer
+ * may be NULL); returns n_out, 0 when there is no such pass. */
+#define NN_CONFUSION_LAST 0
+#define NN_CONFUSION_BEST 1
+void _NN(set, confusion)(nn_def *conf, BOOL on);
+void _NN(get, confusion)(nn_def *conf, BOOL *on);
+BOOL _NN(return, confusion)(nn_def *conf);
+UINT _NN(get, confusion_matrix)(nn_def *conf, int which, UINT max_cells, UINT *cells);
+UINT _NN(get, class_history)(nn_def *conf, UINT pass, UINT *support, UINT *hit, UINT *predicted);
+/* the tally launches the last nn_train_kernel call issued on the GPU: a launch captured into an
+ * epoch graph counts once, however often the graph is replayed (0 with the key off) */
+UINT _NN(return, confusion_launches)(nn_def *conf);
+/* the matrix as text: "# n_out", then one line per target class with n_out + 1 counts */
+BOOL _NN(dump, confusion_matrix)(nn_def *conf, int which, const CHAR *filename);
 /* the [shuffle] epoch permutation (libhpnn/shuffle.h): out[i] = index, in the order drawn once
  * from [seed], of the sample at position i of epoch `epoch` (epochs completed before it) */
 void hpnn_epoch_perm(UINT n, UINT seed, UINT epoch, UINT *out);

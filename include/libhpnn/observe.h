@@ -51,6 +51,9 @@ void hpnn_metrics_epoch(const char *engine, UINT epoch, double loss, UINT correc
                         UINT64 samples);
 /* "validation" record ([validate] N): the held-out set after `epoch` completed epochs */
 void hpnn_metrics_validation(const char *engine, UINT epoch, double loss, UINT correct, UINT n);
+/* [confusion]: the per-class record of a pass (support, hit, predicted: 3 n_out words) as a
+ * "classes" event behind its "validation" event */
+void hpnn_metrics_classes(const char *engine, UINT epoch, const UINT *rec, UINT n_out);
 
 /* debug mode */
 int hpnn_debug_enabled(void);

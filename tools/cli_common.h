@@ -18,6 +18,8 @@
  *   training (same as [lr_schedule]; its other keys come from the conf),
  *   -C c (train_nn only) clip the gradient of every batched step to the global norm c (same as
  *   [clip] c),
+ *   -X FILE per-class metrics: sets [confusion] on and writes the confusion matrix to FILE (train_nn:
+ *   of the best validation pass under -K, else of the last; run_nn: of its PASS / FAIL lines),
  *   -r FILE exact-resume state (loaded when present, written after training),
  *   -M FILE JSON-lines metrics (same as HPNN_METRICS=FILE),
  *   -T trace ranges + timing table (same as HPNN_TRACE=1).
@@ -46,6 +48,7 @@ typedef struct {
     double lr, alpha;
     const char *state;   /* -r */
     const char *metrics; /* -M */
+    const char *matrix;  /* -X */
     int help;
 } cli_opts;
 
@@ -96,7 +99,7 @@ static int cli_parse(int argc, char **argv, cli_opts *o, int allow_x) {
                 j++;
                 continue;
             }
-            if (strchr("OBSGbemdlarM", c) || (strchr("VKPLC", c) && allow_x)) {
+            if (strchr("OBSGbemdlarMX", c) || (strchr("VKPLC", c) && allow_x)) {
                 const char *val = a[j + 1] ? &a[j + 1] : (i + 1 < argc ? argv[++i] : NULL);
                 if (!val) {
                     _OUT(stderr, "syntax error: missing -%c parameter!\n", c);
@@ -151,6 +154,8 @@ static int cli_parse(int argc, char **argv, cli_opts *o, int allow_x) {
                     o->state = val;
                 } else if (c == 'M') {
                     o->metrics = val;
+                } else if (c == 'X') {
+                    o->matrix = val;
                 }
                 break; /* a value consumes the rest of the argument */
             }
@@ -182,7 +187,23 @@ static void cli_apply_conf(const cli_opts *o, nn_def *conf) {
     if (o->patience) _NN(set, patience)(conf, o->patience);
     if (o->lr_schedule >= 0) conf->lr_schedule = (nn_lr_schedule)o->lr_schedule; /* the other keys: the conf's */
     if (o->clip >= 0.0) _NN(set, clip)(conf, o->clip);
+    if (o->matrix) _NN(set, confusion)(conf, TRUE);
     if (o->lr > 0) _NN(set, learning_rate)(conf, o->lr);
     if (o->alpha >= 0) _NN(set, momentum)(conf, o->alpha);
+}
+
+/* -X FILE behind a training or evaluation call that went well: the best pass's matrix when one was
+ * kept, else the last.  A call that tallied nothing (online training ignores the key; after an
+ * early stop without -K the GPU engine may report no last matrix) writes no file and says so: that
+ * is no failure of the call.  Returns 0 unless the file could not be written */
+static int cli_write_matrix(const cli_opts *o, nn_def *conf) {
+    const int which = _NN(get, confusion_matrix)(conf, NN_CONFUSION_BEST, 0, NULL) ? NN_CONFUSION_BEST : NN_CONFUSION_LAST;
+    if (!_NN(get, confusion_matrix)(conf, which, 0, NULL)) {
+        _OUT(stderr, "-X: the call tallied no confusion matrix; %s is not written\n", o->matrix);
+        return 0;
+    }
+    if (_NN(dump, confusion_matrix)(conf, which, o->matrix)) return 0;
+    _OUT(stderr, "FAILED to write the confusion matrix to %s!\n", o->matrix);
+    return -1;
 }
 #endif

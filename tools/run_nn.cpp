@@ -19,6 +19,7 @@ static void dump_help(void) {
     _OUT(stdout, "-S N\tHIP streams per GPU.              *\n");
     _OUT(stdout, "-G N\tnumber of GPUs.                   *\n");
     _OUT(stdout, "-c \tforce the CPU engine.              *\n");
+    _OUT(stdout, "-X F\tconfusion matrix to F ([confusion]) *\n");
     _OUT(stdout, "****************************************\n");
     _OUT(stdout, "input: neural network conf file        *\n");
     _OUT(stdout, "(default ./nn.conf)                    *\n");
@@ -49,8 +50,9 @@ int main(int argc, char *argv[]) {
     _NN(run, kernel)(neural);
     if (_NN(return, verbose)() > 0)
         _OUT(stdout, "ACCURACY: %u/%u\n", _NN(return, last_pass)(), _NN(return, last_total)());
+    const int bad = o.matrix && cli_write_matrix(&o, neural);
     _NN(deinit, conf)(neural);
     free(neural);
     _NN(deinit, all)();
-    return 0;
+    return bad ? 1 : 0;
 }

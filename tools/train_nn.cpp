@@ -37,6 +37,7 @@ static void dump_help(void) {
     _OUT(stdout, "-P P\tstop after P validation passes without improvement (needs -K; [patience] P).\n");
     _OUT(stdout, "-L S\tlearning-rate schedule, S: constant | step | linear | plateau (batched mode; [lr_schedule]).\n");
     _OUT(stdout, "-C c\tclip the gradient of every step to the global L2 norm c (batched mode; [clip]).\n");
+    _OUT(stdout, "-X F\tper-class validation metrics; the confusion matrix goes to F (needs -V; [confusion] on).\n");
     _OUT(stdout, "-r F\texact-resume state file (read if present, written after training).\n");
     _OUT(stdout, "-M F\tJSON-lines metrics file.  -T trace ranges + timing table.\n");
     _OUT(stdout, "***********************************\n");
@@ -109,6 +110,7 @@ int main(int argc, char *argv[]) {
         }
         if (o.state && ok && !_NN(dump, state)(neural, o.state)) ok = FALSE;
     }
+    if (o.matrix && ok && task == 0 && cli_write_matrix(&o, neural)) ok = FALSE;
     if (hpnn_trace_enabled()) hpnn_trace_report(stdout);
     _NN(deinit, conf)(neural);
     free(neural);
